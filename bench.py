@@ -1,6 +1,6 @@
 """Benchmark of the north-star path: whole-volume multi-task tiled inference on a 256^3 volume.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--passes 3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--passes 3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,12 @@ stride 80, all 9 task heads, fused tail, the deformed atlas per tile, on-device 
 scripts/demo_test.py:107-119 stitches), input resident in HBM.  N>1 shards the tiles of the SAME volume
 over ranks (strong scaling) and gathers the masked tile outputs to rank 0 over RCCL.  Prints ONE JSON line
 on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step).
+--dump-outputs DIR writes the stitched maps of the last timed step as DIR/<key>.npy (float32; a fixed
+seeded sample of voxels when the volume exceeds the byte budget).  --full adds everything else the line
+has carried: per-volume latency, the dense volume, the instrumented roofline pass, BASELINE configs 4 and
+5, the synthesis and training blocks, the passes=1 mode and the CPU baseline.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one child process
 per device, before this process has made any GPU call) and relays rank 0's line.
@@ -36,6 +42,8 @@ KERNEL_GROUPS = {"conv_wino (all forms)": ["conv_wino", "conv_wino4", "conv_wino
                  "conv_upfold": ["conv_upfold"],
                  "conv_mfma family (direct)": ["conv_mfma", "conv_mfma_ws", "conv_mfma16"]}
 CPU_BASELINE_CACHE = os.path.join(ROOT, "gpurun_out", "cpu_baseline_last.json")
+DUMP_BYTES = 48 << 20          # --dump-outputs: bytes written over all keys (kept under 64 MB)
+DUMP_SEED = 7
 
 
 def make_volume(n, device):
@@ -607,6 +615,26 @@ def training_block(dev, size=128, reps=2):
             "loss": round(float(total), 4), "stepped": bool(ok), "reps": reps, "dtype": "f32 (split-f16 x3 matrix-core products)"}
 
 
+def dump_index(numel, n_keys):
+    """The flat voxel indices --dump-outputs writes per key (sorted, seeded), or None when every voxel fits DUMP_BYTES."""
+    per_key = DUMP_BYTES // (4 * n_keys)
+    if numel <= per_key:
+        return None
+    return torch.randperm(numel, generator=torch.Generator().manual_seed(DUMP_SEED))[:per_key].sort().values
+
+
+def dump_outputs(acc, out_dir):
+    """--dump-outputs: what the timed step hands its caller, the stitched {key: (D,H,W) fp32} maps, as out_dir/<key>.npy.
+    A volume whose keys together exceed DUMP_BYTES is written as the same seeded sample of flat voxel indices (sorted)
+    for every key, so that two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = dump_index(next(iter(acc.values())).numel(), len(acc))
+    for k, v in acc.items():
+        a = v if idx is None else v.reshape(-1)[idx.to(v.device)]
+        np.save(os.path.join(out_dir, k + ".npy"), a.float().cpu().numpy())
+
+
 def launch_ranks(n, argv):
     """--gpus N without a launcher: one child per device, started before this process makes any GPU call (a process
     that has initialised the GPU must not be replaced or forked into ranks).  Relays rank 0's JSON line."""
@@ -686,7 +714,16 @@ def main():
     ap.add_argument("--no-config5", action="store_true", help="skip the generator + training-iteration block (BASELINE config 5)")
     ap.add_argument("--roofline-reps", type=int, default=3,
                     help="back-to-back launches per HIP-event bracket in the instrumented conv pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the stitched maps of the last timed step to DIR/<key>.npy (float32, at most 48 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: latency, dense volume, roofline, configs 4 and 5, synthesis, "
+                         "training, passes=1 mode, CPU baseline (the --no-* options switch single blocks off)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.layer_table and not args.full:
+        ap.error("--layer-table is written by the roofline pass of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus, sys.argv[1:])
@@ -789,31 +826,35 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:                    # before any later step can overwrite the stitched maps
+        dump_outputs(acc, args.dump_outputs)
 
     # per-volume latency (volume resident -> all stitched outputs resident on rank 0): the same step with a
     # device sync (and a barrier) after every volume; median.  `value` above is the pipelined rate of K volumes back to back.
-    lat = []
-    for _ in range(min(args.steps, 10)):
-        if use_dist:
-            dist.barrier()
-        torch.cuda.synchronize()
-        ts = time.perf_counter()
-        step()
-        torch.cuda.synchronize()
-        if use_dist:
-            dist.barrier()
-        lat.append(time.perf_counter() - ts)
-    lat.sort()
-    lat_med = torch.tensor([lat[len(lat) // 2] if lat else 0.0], device=dev, dtype=torch.float64)
-    if world > 1:
-        dist.all_reduce(lat_med, op=dist.ReduceOp.MAX)
-    lat_med = float(lat_med.item())
+    lat_med = None
+    if args.full:
+        lat = []
+        for _ in range(min(args.steps, 10)):
+            if use_dist:
+                dist.barrier()
+            torch.cuda.synchronize()
+            ts = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            if use_dist:
+                dist.barrier()
+            lat.append(time.perf_counter() - ts)
+        lat.sort()
+        lat_med = torch.tensor([lat[len(lat) // 2] if lat else 0.0], device=dev, dtype=torch.float64)
+        if world > 1:
+            dist.all_reduce(lat_med, op=dist.ReduceOp.MAX)
+        lat_med = float(lat_med.item())
 
     # The same build, graphs and step on a volume WITHOUT an exact-zero background (uniform noise everywhere): no box, run or
     # voxel is left out, every shortcut that depends on the data (engine.mask_skip, uniform_skip, the compact rows) finds
     # nothing to skip.  Reported next to `value` so that the data-independent rate is on the line too.
     dense_ms = None
-    if not args.no_dense_check:
+    if args.full and not args.no_dense_check:
         dense = None
         if rank == 0:
             g = torch.Generator(device="cpu").manual_seed(5)
@@ -926,14 +967,14 @@ def main():
     # iteration per rank with the flat gradient all-reduce.  Both are deterministic in what they launch and collective in
     # the same places on every rank; neither is `value`.
     config4 = config5 = None
-    if not args.no_config4 and n == 256:
+    if args.full and not args.no_config4 and n == 256:
         config4 = config4_block(sess, dev, rank, world, use_dist, stride, win)
-    if not args.no_config5:
+    if args.full and not args.no_config5:
         config5 = config5_block(dev, rank, world, use_dist)
 
     kernels, groups, family, mine = {}, {}, {}, {}
     dense_family = None
-    if args.roofline_reps > 0:                      # 0: skip (used for rocprofv3 runs that should hold the timed steps only)
+    if args.full and args.roofline_reps > 0:        # 0: skip (used for rocprofv3 runs that should hold the timed steps only)
         kernels, groups, family, mine = conv_profile(None, args.layer_table)
         if not args.no_dense_check:
             g = torch.Generator(device="cpu").manual_seed(5)
@@ -946,7 +987,7 @@ def main():
     # workload (scripts/pmc_traffic.py: FETCH_SIZE x2 + WRITE_SIZE, separate passes, per MI355X_MICROARCH.md) is used --
     # and refused when the launch counts it recorded per kernel differ from this run's (a stale file)
     traffic_tab, traffic_note = {}, None
-    if os.path.exists(TRAFFIC_FILE) and world == 1:
+    if args.full and os.path.exists(TRAFFIC_FILE) and world == 1:
         try:
             tj = json.load(open(TRAFFIC_FILE))
             theirs = {k: int(v["launches"]) for k, v in tj["kernels"].items() if k in CONV_KERNELS}
@@ -958,7 +999,7 @@ def main():
                                 "(scripts/pmc_traffic.py)" % (os.path.relpath(TRAFFIC_FILE, ROOT), theirs, mine))
         except Exception as e:                                # noqa: BLE001
             traffic_note = "unreadable traffic file: %r" % (e,)
-    elif world > 1:
+    elif args.full and world > 1:
         traffic_note = "not reported for N > 1: the PMC summary is a one-rank run and the launches per rank differ"
     for k in kernels:
         kernels[k]["traffic"] = traffic_tab.get(k)
@@ -969,7 +1010,7 @@ def main():
                                                  for m in gv["kernels"]) / gv["launches_per_step"]
         gv["avg_launch_us"] = gv["ms_per_step"] * 1e3 * max(world, 1) / gv["launches_per_step"]
     dominant = max(groups, key=lambda k: groups[k]["ms_per_step"]) if groups else None
-    if rank == 0:
+    if rank == 0 and args.full:
         tile_vox = sum(TU.tile_cost(r) for r in ranges)
         flops_step = sum(conv_flops_tile([r[a][1] - r[a][0] for a in range(3)]) for r in ranges)
         # work the tile loop's mask makes unnecessary (engine.mask_skip): boxes of the last convolution and runs of 64
@@ -1011,6 +1052,7 @@ def main():
         uni2, uni3 = uni.get(("enc", 0, 1), 0.0), uni.get(("dec", 0), 0.0)
         uni_l1 = sum(v for k, v in uni.items() if k[1] == 1) / max(sum(1 for k in uni if k[1] == 1), 1)
         dk = groups.get(dominant, {})
+    if rank == 0:
         line = {
             "metric": "voxels/sec whole-volume multi-task inference, 256^3 tiled",
             "value": n ** 3 * args.steps / dt, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
@@ -1021,106 +1063,108 @@ def main():
             "backend": backend if use_dist else None,
             "devices": ["cuda:%d" % (0 if share else r) for r in range(world)],
             "timing": "value = K volumes back to back between two barrier+synchronize brackets (no sync between volumes, "
-                      "max over ranks); latency_ms_median = one volume at a time, synchronised after each",
-            "latency_ms_median": lat_med * 1e3,
-            "dense_volume": None if dense_ms is None else {
-                "ms_per_step": dense_ms, "value": n ** 3 / dense_ms * 1e3, "unit": "voxels/s",
-                "conv_family": dense_family,
-                "note": "the same build and graphs on a volume of uniform noise without a zero background: nothing is "
-                        "skipped (config.tile_mask describes what the headline volume, SURVEY config 3's ellipsoid with "
-                        "exact zeros outside, lets the exact shortcuts leave out); conv_family = the instrumented conv "
-                        "pass on this volume: the data-independent fraction of the MFMA peak"},
+                      "max over ranks)",
             "exchange": exchange,
             "config": {"workload": "%d^3 volume, reference tiling win160/stride80 -> %d tiles, UNet3D f64 x6 levels, "
                                    "9 heads (69 ch), fused tail + deformed atlas + on-device stitch of %s keys"
                                    % (n, len(ranges), n_keys),
                        "stitched_keys": n_keys,
-                       "tile_voxels_per_step": tile_vox, "tile_voxels_per_s": tile_vox * args.steps / dt,
-                       "algorithmic_tflop_per_step": flops_step / 1e12,
-                       "computed_tflop_per_step": computed_step / 1e12,
-                       "end_to_end_tflops": computed_step * args.steps / dt / 1e12,
-                       "tile_mask": {"skip": bool(eng.mask_skip), "tile_voxels_inside_mask_frac": inside / tile_vox,
-                                     "last_conv_voxels_computed_frac": conv_vox / tile_vox,
-                                     "head_voxels_computed_frac": head_vox / tile_vox,
-                                     "uniform_box_frac_enc0_conv2": uni2 / tile_vox,
-                                     "uniform_box_frac_dec4_conv1_skip": uni3 / tile_vox,
-                                     "uniform_box_frac_level1_layers": uni_l1 / (tile_vox / 8.0),
-                                     "note": "the tile loop keeps out * (tile input != 0) (scripts/demo_test.py:88-100); "
-                                             "the last convolution (4x4x16 boxes) and the heads (runs of 64 voxels) leave "
-                                             "out what holds no non-zero input; stitched results are bit-identical "
-                                             "(BFM_MASK_SKIP=0 computes everything); algorithmic_tflop_per_step is the "
-                                             "reference's dense work, computed_tflop_per_step and end_to_end_tflops what "
-                                             "was evaluated"},
                        "mfma_passes": args.passes,
                        "submission": "hipGraph replay per tile shape" if sess.use_graphs else "eager",
                        "parallelism": "tiles sharded over %d rank(s), gather to rank 0" % world,
                        "tiles_in_flight_per_gpu": sess.lanes if sess.use_graphs else 1},
-            "roofline": {"bound": "mfma", "kernel": dominant, "kernel_members": dk.get("kernels"),
-                         "achieved": dk.get("achieved"), "peak": peak, "unit": "TFLOP/s", "frac": dk.get("frac"),
-                         "mfma_issue_frac": dk.get("mfma_issue_frac"),
-                         "mfma_issue_note": "issued fp16 MFMA FLOPs / peak: the algorithmic FLOPs times the split passes times the "
-                                            "kernel's reduction (F(2,3) 18/27, F(4,3) 13.5/27, up-fold 8/27, direct 1); what the "
-                                            "matrix pipe sustains on random operands fed from LDS + L2 is 0.56 of the nameplate "
-                                            "(1 410 TFLOP/s, profiles/r02_mfma_sustained_micro.txt)",
-                         "traffic": dk.get("traffic_per_launch"), "traffic_source": traffic_note,
-                         "avg_launch_us": dk.get("avg_launch_us"),
-                         "algorithmic_bytes_per_launch": dk.get("algorithmic_bytes_per_launch"),
-                         "share_of_conv_time": dk.get("share_of_conv_time"),
-                         "per_group": groups, "per_kernel": kernels, "conv_family": family,
-                         "note": "top level = the GROUP of conv kernels with the largest share of the step's conv time (the "
-                                 "Winograd body runs under three launch names), every group under per_group, every kernel "
-                                 "name under per_kernel, the whole family under conv_family; achieved = algorithmic conv "
-                                 "FLOPs of the boxes a launch evaluates (2*27*Cin*Cout*voxels, also for Winograd / up-folded "
-                                 "layers; config.tile_mask says what the masked / uniform forms leave out) / summed launch "
-                                 "durations; durations from HIP events around %d back-to-back launches of each conv in an "
-                                 "instrumented eager replay of the step right after the timed region; the kernels issue "
-                                 "up to %dx the algorithmic FLOPs in f16 MFMA; conv_wino_uniform is a pair of kernels per "
-                                 "launch: conv_wino_rest (matrix-bound, the unflagged boxes) + a kernel that streams one "
-                                 "box's result to its class mates (HBM-bound); with N > 1 ranks a kernel's time is the "
-                                 "slowest rank's, FLOPs and launches are summed over the ranks" % (args.roofline_reps, args.passes)},
         }
-        line["synthesis"] = None
-        if not args.no_synthesis and world == 1:
-            try:
-                line["synthesis"] = synthesis_block(dev)
-            except Exception as e:                            # noqa: BLE001 -- never lose the headline line to the extra block
-                line["synthesis"] = {"error": repr(e)}
-        line["training"] = None
-        if not args.no_training and world == 1:
-            try:
-                line["training"] = training_block(dev)
-            except Exception as e:                            # noqa: BLE001
-                line["training"] = {"error": repr(e)}
-        line["config4"] = config4
-        line["config5"] = config5
-        line["fast_mode"] = None
-        fast_sess = None
-        if not args.no_fast_mode and world == 1 and args.passes == 3:
-            try:
-                fast_sess, line["fast_mode"] = fast_mode_block(sess, full, stride, win)
-            except Exception as e:                            # noqa: BLE001
-                line["fast_mode"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
-            sd = {k: v for k, v in sess.model.state_dict().items()}
-            line["cpu_baseline"] = cpu_baseline(sd, full, n, ranges, not args.cpu_baseline_quick, sess, fast_sess)
-            line["label_parity"] = line["cpu_baseline"].pop("label_parity")
-            try:                                              # for the N > 1 lines of the same box (rank 0 at N = 1 only)
-                os.makedirs(os.path.dirname(CPU_BASELINE_CACHE), exist_ok=True)
-                json.dump({"size": n, "cpu_baseline": line["cpu_baseline"], "label_parity": line["label_parity"]},
-                          open(CPU_BASELINE_CACHE, "w"))
-            except OSError:
-                pass
-        else:
-            line["cpu_baseline"] = None
-            if world > 1 and os.path.exists(CPU_BASELINE_CACHE):
+        if args.full:
+            line["timing"] += "; latency_ms_median = one volume at a time, synchronised after each"
+            line["latency_ms_median"] = lat_med * 1e3
+            line["dense_volume"] = None if dense_ms is None else {
+                "ms_per_step": dense_ms, "value": n ** 3 / dense_ms * 1e3, "unit": "voxels/s",
+                "conv_family": dense_family,
+                "note": "the same build and graphs on a volume of uniform noise without a zero background: nothing is "
+                        "skipped (config.tile_mask describes what the headline volume, SURVEY config 3's ellipsoid with "
+                        "exact zeros outside, lets the exact shortcuts leave out); conv_family = the instrumented conv "
+                        "pass on this volume: the data-independent fraction of the MFMA peak"}
+            line["config"].update({"tile_voxels_per_step": tile_vox, "tile_voxels_per_s": tile_vox * args.steps / dt,
+                                   "algorithmic_tflop_per_step": flops_step / 1e12,
+                                   "computed_tflop_per_step": computed_step / 1e12,
+                                   "end_to_end_tflops": computed_step * args.steps / dt / 1e12,
+                                   "tile_mask": {"skip": bool(eng.mask_skip), "tile_voxels_inside_mask_frac": inside / tile_vox,
+                                                 "last_conv_voxels_computed_frac": conv_vox / tile_vox,
+                                                 "head_voxels_computed_frac": head_vox / tile_vox,
+                                                 "uniform_box_frac_enc0_conv2": uni2 / tile_vox,
+                                                 "uniform_box_frac_dec4_conv1_skip": uni3 / tile_vox,
+                                                 "uniform_box_frac_level1_layers": uni_l1 / (tile_vox / 8.0),
+                                                 "note": "the tile loop keeps out * (tile input != 0) (scripts/demo_test.py:88-100); "
+                                                         "the last convolution (4x4x16 boxes) and the heads (runs of 64 voxels) leave "
+                                                         "out what holds no non-zero input; stitched results are bit-identical "
+                                                         "(BFM_MASK_SKIP=0 computes everything); algorithmic_tflop_per_step is the "
+                                                         "reference's dense work, computed_tflop_per_step and end_to_end_tflops what "
+                                                         "was evaluated"}})
+            line["roofline"] = {"bound": "mfma", "kernel": dominant, "kernel_members": dk.get("kernels"),
+                                "achieved": dk.get("achieved"), "peak": peak, "unit": "TFLOP/s", "frac": dk.get("frac"),
+                                "mfma_issue_frac": dk.get("mfma_issue_frac"),
+                                "mfma_issue_note": "issued fp16 MFMA FLOPs / peak: the algorithmic FLOPs times the split passes times the "
+                                                   "kernel's reduction (F(2,3) 18/27, F(4,3) 13.5/27, up-fold 8/27, direct 1); what the "
+                                                   "matrix pipe sustains on random operands fed from LDS + L2 is 0.56 of the nameplate "
+                                                   "(1 410 TFLOP/s, profiles/r02_mfma_sustained_micro.txt)",
+                                "traffic": dk.get("traffic_per_launch"), "traffic_source": traffic_note,
+                                "avg_launch_us": dk.get("avg_launch_us"),
+                                "algorithmic_bytes_per_launch": dk.get("algorithmic_bytes_per_launch"),
+                                "share_of_conv_time": dk.get("share_of_conv_time"),
+                                "per_group": groups, "per_kernel": kernels, "conv_family": family,
+                                "note": "top level = the GROUP of conv kernels with the largest share of the step's conv time (the "
+                                        "Winograd body runs under three launch names), every group under per_group, every kernel "
+                                        "name under per_kernel, the whole family under conv_family; achieved = algorithmic conv "
+                                        "FLOPs of the boxes a launch evaluates (2*27*Cin*Cout*voxels, also for Winograd / up-folded "
+                                        "layers; config.tile_mask says what the masked / uniform forms leave out) / summed launch "
+                                        "durations; durations from HIP events around %d back-to-back launches of each conv in an "
+                                        "instrumented eager replay of the step right after the timed region; the kernels issue "
+                                        "up to %dx the algorithmic FLOPs in f16 MFMA; conv_wino_uniform is a pair of kernels per "
+                                        "launch: conv_wino_rest (matrix-bound, the unflagged boxes) + a kernel that streams one "
+                                        "box's result to its class mates (HBM-bound); with N > 1 ranks a kernel's time is the "
+                                        "slowest rank's, FLOPs and launches are summed over the ranks" % (args.roofline_reps, args.passes)}
+            line["synthesis"] = None
+            if not args.no_synthesis and world == 1:
                 try:
-                    cj = json.load(open(CPU_BASELINE_CACHE))
-                    if cj.get("size") == n and cj["cpu_baseline"].get("cpu_model") == host_cpu_info()["model"]:
-                        line["cpu_baseline"] = dict(cj["cpu_baseline"], copied_from="the N = 1 run of this box (%s)"
-                                                    % os.path.relpath(CPU_BASELINE_CACHE, ROOT))
-                        line["label_parity"] = cj.get("label_parity")
-                except Exception:                             # noqa: BLE001
+                    line["synthesis"] = synthesis_block(dev)
+                except Exception as e:                            # noqa: BLE001 -- never lose the headline line to the extra block
+                    line["synthesis"] = {"error": repr(e)}
+            line["training"] = None
+            if not args.no_training and world == 1:
+                try:
+                    line["training"] = training_block(dev)
+                except Exception as e:                            # noqa: BLE001
+                    line["training"] = {"error": repr(e)}
+            line["config4"] = config4
+            line["config5"] = config5
+            line["fast_mode"] = None
+            fast_sess = None
+            if not args.no_fast_mode and world == 1 and args.passes == 3:
+                try:
+                    fast_sess, line["fast_mode"] = fast_mode_block(sess, full, stride, win)
+                except Exception as e:                            # noqa: BLE001
+                    line["fast_mode"] = {"error": repr(e)}
+            if not args.no_cpu_baseline and world == 1:
+                sd = {k: v for k, v in sess.model.state_dict().items()}
+                line["cpu_baseline"] = cpu_baseline(sd, full, n, ranges, not args.cpu_baseline_quick, sess, fast_sess)
+                line["label_parity"] = line["cpu_baseline"].pop("label_parity")
+                try:                                              # for the N > 1 lines of the same box (rank 0 at N = 1 only)
+                    os.makedirs(os.path.dirname(CPU_BASELINE_CACHE), exist_ok=True)
+                    json.dump({"size": n, "cpu_baseline": line["cpu_baseline"], "label_parity": line["label_parity"]},
+                              open(CPU_BASELINE_CACHE, "w"))
+                except OSError:
                     pass
+            else:
+                line["cpu_baseline"] = None
+                if world > 1 and os.path.exists(CPU_BASELINE_CACHE):
+                    try:
+                        cj = json.load(open(CPU_BASELINE_CACHE))
+                        if cj.get("size") == n and cj["cpu_baseline"].get("cpu_model") == host_cpu_info()["model"]:
+                            line["cpu_baseline"] = dict(cj["cpu_baseline"], copied_from="the N = 1 run of this box (%s)"
+                                                        % os.path.relpath(CPU_BASELINE_CACHE, ROOT))
+                            line["label_parity"] = cj.get("label_parity")
+                    except Exception:                             # noqa: BLE001
+                        pass
         try:                                                  # librccl's version banner sits in the C stdio buffer and
             import ctypes                                     # would otherwise land after the JSON line at exit
             ctypes.CDLL(None).fflush(None)

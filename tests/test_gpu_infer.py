@@ -1453,7 +1453,7 @@ def test_bench_line_fields_two_ranks_dry_run():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BFM_BENCH_SHARE_GPU="1", BFM_BENCH_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                         "--size", "200", "--no-dense-check", "--no-cpu-baseline", "--no-config5"], capture_output=True, text=True,
                        timeout=900, env=env, cwd=root)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -1481,7 +1481,7 @@ def test_bench_configs_4_and_5_two_ranks_dry_run():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BFM_BENCH_SHARE_GPU="1", BFM_BENCH_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full",
                         "--no-dense-check", "--no-cpu-baseline", "--roofline-reps", "0"], capture_output=True, text=True,
                        timeout=1500, env=env, cwd=root)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -1492,6 +1492,43 @@ def test_bench_configs_4_and_5_two_ranks_dry_run():
     assert c4["exchange"]["broadcast_bytes"] == 4 * 512 ** 3 and c4["exchange"]["bytes_sent_per_peer"] > 0
     assert c5["items_per_s"] > 0 and c5["scaling"] == "weak" and c5["stepped"] and np.isfinite(c5["last_loss"])
     assert c5["allreduce_ms_per_iteration"] is not None and c5["allreduce_bytes"] > 4 * 2.6e8      # 264 M fp32 gradients
+
+
+def test_bench_plain_run_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline only, runs exactly --steps timed steps, and
+    --dump-outputs writes the last timed step's 17 stitched maps (at 160^3 a seeded sample of voxels, the byte budget
+    holds no whole volume), equal to the same volume through tiled_inference here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from brainfm_amd import test_utils as TU
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--size", "160", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-800:], r.stderr[-3000:])
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "voxels/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 160 ** 3 / d["ms_per_step"] * 1e3) <= 1e-6 * d["value"]
+    assert d["dtype"] == "f16x3-split (fp32-grade)" and d["config"]["stitched_keys"] == 17
+    assert not {"roofline", "cpu_baseline", "latency_ms_median", "dense_volume", "synthesis", "config4"} & set(d)
+    files = sorted(os.listdir(out))
+    assert len(files) == 17 and sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    import bench
+    torch.manual_seed(1)
+    ga, ta = TU.default_inference_args(f_maps=64, num_levels=6)
+    s = TU.InferenceSession(ga, ta, _dev(), passes=3)
+    s.set_atlas(*bench.make_atlas())
+    acc = TU.tiled_inference(bench.make_volume(160, _dev()), s, [80] * 3, [160] * 3, batched=True)[0]
+    assert sorted(k + ".npy" for k in acc) == files
+    idx = bench.dump_index(160 ** 3, len(acc))
+    assert idx is not None and len(idx) == (48 << 20) // (4 * 17)
+    for k, v in acc.items():
+        a = np.load(out / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == idx.shape, k
+        assert _relerr(a, v.reshape(-1)[idx.to(v.device)].cpu().numpy()) <= 1e-5, k
 
 
 def test_crop3d_is_the_tile_window():

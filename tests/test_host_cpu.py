@@ -579,14 +579,12 @@ def test_volio_reads_the_reference_atlas_file():
     """SURVEY N3 pinned to the one real volume file on the reference's hot path, files/gca.mgz (utils/test_utils.py:38-43
     reads it at import: MNI, aff2 = MRIread(atlas_path); A = inv(aff2)).  Expected values: tests/golden/volio_gca.npz, an
     independent parse of the MGH format definition (make_golden_volio.py; nibabel is absent, so volio stays 'parity
-    unpinned against nibabel').  The file itself never leaves the reference tree: skipped where that is absent."""
+    unpinned against nibabel').  A copy of the file is stored as tests/golden/gca.mgz."""
     import gzip
     import hashlib
     from brainfm_amd import volio
     from brainfm_amd import test_utils as TU
-    path = os.path.join(os.environ.get("BRAINFM_REFERENCE", "/root/reference"), "files", "gca.mgz")
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
+    path = os.path.join(ROOT, "tests", "golden", "gca.mgz")
     d = load_npz("volio_gca.npz")
     v = volio.load(path)
     assert tuple(v.shape) == tuple(d["dims"][:3]) == (256, 256, 256)
