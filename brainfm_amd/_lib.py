@@ -57,6 +57,16 @@ class Dopri5Advect(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+class AgeParams(C.Structure):
+    """bfm_age_params_t: device pointers of the age head's parameters (torch layouts)."""
+    _fields_ = [(n, C.c_void_p) for n in ("c1w", "c1b", "c2w", "c2b", "l1w", "l1b", "l2w", "l2b", "l3w", "l3b")]
+
+
+class AgeGrads(C.Structure):
+    """bfm_age_grads_t: device pointers of their gradients (same shapes)."""
+    _fields_ = [(n, C.c_void_p) for n in ("c1w", "c1b", "c2w", "c2b", "l1w", "l1b", "l2w", "l2b", "l3w", "l3b")]
+
+
 GATHER_MAX_JOBS = 12          # BFM_GATHER_MAX_JOBS of include/brainfm_hip.h
 
 
@@ -257,6 +267,15 @@ SIGNATURES = {
     "bfm_tile_mask_index": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "bfm_pack_tile_compact": (_I, [_P, _L, _P, _I, _P, _P, _L, _P, _L, _P, _P]),
     "bfm_stitch_gather_compact": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P]),
+    "bfm_maxpool4": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "bfm_maxpool4_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "bfm_age_conv_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "bfm_age_conv_bwd_workspace": (_Z, [_I, _I, _I, _I, _I]),
+    "bfm_age_conv_bwd": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "bfm_age_mlp_fwd": (_I, [_P, _I, C.POINTER(AgeParams), _I, _P, _P, _P, _P]),
+    "bfm_age_mlp_bwd_workspace": (_Z, []),
+    "bfm_age_mlp_bwd": (_I, [_P, _I, C.POINTER(AgeParams), _I, _P, _P, _P, _P, C.c_double, _F, _P, C.POINTER(AgeGrads),
+                             _P, _P, _Z, _P]),
 }
 
 _lib = None

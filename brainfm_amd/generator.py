@@ -797,6 +797,8 @@ class BaseGen(torch.utils.data.Dataset):
                 self._run_gather(jobs, deform_dict, setups["flip"])
         finally:
             self._batch = None
+        if case.get("age") is not None:                       # datasets.py:85-113 (ages per subject), 678-679
+            target["age"] = float(case["age"])
         return target
 
     def __getitem__(self, idx):

@@ -266,8 +266,129 @@ def normalize_cl(eng, feat_cl, dims):
     return out
 
 
+def age_flat_features(size):
+    """in_features of final_linear1_age exactly as head.py:45 forms it: 4 * s0 // 16 * s1 // 16 * s2 // 16, left to right."""
+    s0, s1, s2 = [int(v) for v in size]
+    return 4 * s0 // 16 * s1 // 16 * s2 // 16
+
+
+def age_pooled_dims(dims):
+    """Spatial shape after the head's two MaxPool3d(4, 4) (floor mode)."""
+    return tuple(int(d) // 4 // 4 for d in dims)
+
+
+class _ConvBlock(nn.Module):
+    """head.py:152-167 (the parameters only: .main = Conv3d(k=3, s=1, p=1, bias); LeakyReLU(0.2) has none)."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.main = nn.Conv3d(cin, cout, 3, 1, 1)
+
+
+AGE_PARAM_NAMES = ("pool_layers.1.main.weight", "pool_layers.1.main.bias", "pool_layers.3.main.weight",
+                   "pool_layers.3.main.bias", "final_linear1_age.weight", "final_linear1_age.bias",
+                   "final_linear2_age.weight", "final_linear2_age.bias", "final_linear3_age.weight", "final_linear3_age.bias")
+
+
+class AgeHead:
+    """The pooled scalar head (head.py:39-48,61-66) on libbrainfm_hip.so: forward (6 launches) on a channels-last feature
+    map, and the backward of loss_age (8 launches) whose pooled gradient is added into the feature gradient.
+    params: {AGE_PARAM_NAMES entry: fp32 device tensor in torch's layout}; they are read in place at every call."""
+
+    def __init__(self, params, c_feat, n_flat, device):
+        self.lib = L.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.BfmError("the age head needs a HIP device; the product path has no CPU fallback")
+        self.params = OrderedDict((k, params[k]) for k in AGE_PARAM_NAMES)
+        for k, v in self.params.items():
+            if v.device != self.device or v.dtype != torch.float32 or not v.is_contiguous():
+                raise L.BfmError("age parameter %s must be a contiguous fp32 tensor on %s" % (k, self.device))
+        self.c_feat, self.n_flat = int(c_feat), int(n_flat)
+
+    def _prm(self):
+        return L.AgeParams(*[v.data_ptr() for v in self.params.values()])
+
+    def check_dims(self, dims):
+        P2 = age_pooled_dims(dims)
+        n = 4 * P2[0] * P2[1] * P2[2]
+        if min(int(d) for d in dims) < 16 or n != self.n_flat:
+            raise L.BfmError("the age head flattens %s features at the spatial shape %s, but final_linear1_age expects %d "
+                             "(train_args.size); the pooled scalar head runs on whole `size` inputs only, not on tiles of "
+                             "another shape" % (n, tuple(int(d) for d in dims), self.n_flat))
+        return P2
+
+    def forward(self, feat_cl, dims):
+        """feat_cl: (D,H,W,C) fp32 (the normalised last decoder feature).  Returns (age (1,) raw -- before AgeProcessor --,
+        tape for backward)."""
+        lib, st = self.lib, L.stream_ptr()
+        D, H, W = [int(d) for d in dims]
+        P2 = self.check_dims(dims)
+        P1 = (D // 4, H // 4, W // 4)
+        C_ = self.c_feat
+        feat_cl = feat_cl.contiguous()
+        if feat_cl.dtype != torch.float32 or not feat_cl.is_contiguous() or feat_cl.numel() != D * H * W * C_:
+            raise L.BfmError("age head: feature map must be a contiguous fp32 (D,H,W,%d) tensor" % C_)
+        p = self.params
+        dev = self.device
+        t = {"dims": (D, H, W), "P1": P1, "P2": P2, "feat": feat_cl}
+        t["x1"] = torch.empty(P1 + (C_,), dtype=torch.float32, device=dev)
+        t["a1"] = torch.empty(P1 + (C_,), dtype=torch.uint8, device=dev)
+        t["y1"] = torch.empty(P1 + (16,), dtype=torch.float32, device=dev)
+        t["x2"] = torch.empty(P2 + (16,), dtype=torch.float32, device=dev)
+        t["a2"] = torch.empty(P2 + (16,), dtype=torch.uint8, device=dev)
+        t["y2"] = torch.empty(P2 + (4,), dtype=torch.float32, device=dev)
+        t["h1"] = torch.empty(160, dtype=torch.float32, device=dev)
+        t["h2"] = torch.empty(10, dtype=torch.float32, device=dev)
+        t["p"] = torch.empty(1, dtype=torch.float32, device=dev)
+        L.check(lib.bfm_maxpool4(L.ptr(feat_cl), C_, D, H, W, L.ptr(t["x1"]), L.ptr(t["a1"]), st), "age maxpool4")
+        L.check(lib.bfm_age_conv_fwd(L.ptr(t["x1"]), C_, *P1, L.ptr(p["pool_layers.1.main.weight"]),
+                                     L.ptr(p["pool_layers.1.main.bias"]), 16, L.ptr(t["y1"]), st), "age conv1")
+        L.check(lib.bfm_maxpool4(L.ptr(t["y1"]), 16, *P1, L.ptr(t["x2"]), L.ptr(t["a2"]), st), "age maxpool4 (2)")
+        L.check(lib.bfm_age_conv_fwd(L.ptr(t["x2"]), 16, *P2, L.ptr(p["pool_layers.3.main.weight"]),
+                                     L.ptr(p["pool_layers.3.main.bias"]), 4, L.ptr(t["y2"]), st), "age conv2")
+        t["prm"] = prm = self._prm()
+        nv = P2[0] * P2[1] * P2[2]
+        L.check(lib.bfm_age_mlp_fwd(L.ptr(t["y2"]), nv, C.byref(prm), self.n_flat, L.ptr(t["h1"]), L.ptr(t["h2"]),
+                                    L.ptr(t["p"]), st), "age mlp")
+        return t["p"], t
+
+    def backward(self, tape, age, coef, loss_out, grads, dfeat):
+        """loss_age of one sample (| |p| - age |, fp64 -> loss_out, a device pointer or None) and its gradient scaled by
+        coef into grads ({AGE_PARAM_NAMES entry: fp32 device tensor}, written) and, through the first pool, ADDED into
+        dfeat (D,H,W,C), the gradient of the normalised feature."""
+        lib, st = self.lib, L.stream_ptr()
+        dev = self.device
+        P1, P2 = tape["P1"], tape["P2"]
+        C_ = self.c_feat
+        nv = P2[0] * P2[1] * P2[2]
+        gr = L.AgeGrads(*[grads[k].data_ptr() for k in AGE_PARAM_NAMES])
+        p = self.params
+        dy2 = torch.empty(P2 + (4,), dtype=torch.float32, device=dev)
+        wsm = torch.empty(lib.bfm_age_mlp_bwd_workspace(), dtype=torch.uint8, device=dev)
+        L.check(lib.bfm_age_mlp_bwd(L.ptr(tape["y2"]), nv, C.byref(tape["prm"]), self.n_flat, L.ptr(tape["h1"]),
+                                    L.ptr(tape["h2"]), L.ptr(tape["p"]), None, float(age), float(coef), loss_out,
+                                    C.byref(gr), L.ptr(dy2), L.ptr(wsm), wsm.numel(), st), "age mlp bwd")
+        dx2 = torch.empty(P2 + (16,), dtype=torch.float32, device=dev)
+        ws2 = torch.empty(max(1, lib.bfm_age_conv_bwd_workspace(16, *P2, 4)), dtype=torch.uint8, device=dev)
+        L.check(lib.bfm_age_conv_bwd(L.ptr(tape["x2"]), 16, *P2, L.ptr(p["pool_layers.3.main.weight"]), 4, L.ptr(tape["y2"]),
+                                     L.ptr(dy2), L.ptr(dx2), L.ptr(grads["pool_layers.3.main.weight"]),
+                                     L.ptr(grads["pool_layers.3.main.bias"]), L.ptr(ws2), ws2.numel(), st), "age conv2 bwd")
+        dy1 = torch.empty(P1 + (16,), dtype=torch.float32, device=dev)
+        L.check(lib.bfm_maxpool4_bwd(L.ptr(dx2), L.ptr(tape["a2"]), 16, *P1, L.ptr(dy1), 0, st), "age maxpool4 bwd")
+        dx1 = torch.empty(P1 + (C_,), dtype=torch.float32, device=dev)
+        ws1 = torch.empty(max(1, lib.bfm_age_conv_bwd_workspace(C_, *P1, 16)), dtype=torch.uint8, device=dev)
+        L.check(lib.bfm_age_conv_bwd(L.ptr(tape["x1"]), C_, *P1, L.ptr(p["pool_layers.1.main.weight"]), 16, L.ptr(tape["y1"]),
+                                     L.ptr(dy1), L.ptr(dx1), L.ptr(grads["pool_layers.1.main.weight"]),
+                                     L.ptr(grads["pool_layers.1.main.bias"]), L.ptr(ws1), ws1.numel(), st), "age conv1 bwd")
+        D, H, W = tape["dims"]
+        L.check(lib.bfm_maxpool4_bwd(L.ptr(dx1), L.ptr(tape["a1"]), C_, D, H, W, L.ptr(dfeat), 1, st), "age pooled scatter")
+        self._keep = (dy2, wsm, dx2, ws2, dy1, dx1, ws1, gr)
+
+
 class TaskHead(nn.Module):
-    """TaskHead with task_f_maps=[c]: one 1x1x1 conv + bias per task (head.py:20-67)."""
+    """TaskHead with task_f_maps=[c]: one 1x1x1 conv + bias per dense task, and the pooled scalar head for a task whose
+    out_channels entry is <= 0 (age; head.py:20-67)."""
 
     def __init__(self, args, f_maps_list, out_channels, is_3d=True, out_feat_level=-1, exclude_keys=[], *kwargs):
         super().__init__()
@@ -277,32 +398,88 @@ class TaskHead(nn.Module):
         self.out_channels = OrderedDict((k, v) for k, v in out_channels.items() if k not in exclude_keys)
         self.out_names = self.out_channels.keys()
         self.c_feat = f_maps_list[-1]
+        self.dense_channels = OrderedDict((k, v) for k, v in self.out_channels.items() if v > 0)
+        self.age_task = None
+        names = list(self.out_channels)
         for name, n in self.out_channels.items():
-            if n <= 0:
-                raise NotImplementedError("pooled scalar heads (age) are outside the inference hot path")
-            self.add_module("final_conv_%s" % name, nn.Conv3d(self.c_feat, n, 1))
+            if n > 0:
+                self.add_module("final_conv_%s" % name, nn.Conv3d(self.c_feat, n, 1))
+                continue
+            # the reference's forward feeds the POOLED tensor to every head after this one (head.py:61-62): only harmless
+            # while the pooled head is the last entry, which process_args guarantees
+            if name != names[-1] or self.age_task is not None:
+                raise L.BfmError("pooled scalar head '%s' must be the last entry of out_channels (got order %s)"
+                                 % (name, names))
+            if not is_3d:
+                raise NotImplementedError("the pooled scalar head is 3-D only here")
+            size = getattr(args, "size", None)
+            if size is None or len(size) != 3:
+                raise L.BfmError("the pooled scalar head '%s' needs train_args.size (3 values)" % name)
+            n_flat = age_flat_features(size)
+            P2 = age_pooled_dims(size)
+            if n_flat != 4 * P2[0] * P2[1] * P2[2]:
+                raise L.BfmError("size %s: final_linear1_%s takes 4*s0//16*s1//16*s2//16 = %d features (head.py:45), but the "
+                                 "head's pooling leaves 4 x %s = %d values at that size; no input of this size can pass "
+                                 "the head" % (tuple(size), name, n_flat, P2, 4 * P2[0] * P2[1] * P2[2]))
+            self.age_task = name
+            self.n_flat = n_flat
+            self.pool_layers = nn.ModuleList([nn.MaxPool3d(4, 4), _ConvBlock(self.c_feat, 16), nn.MaxPool3d(4, 4),
+                                              _ConvBlock(16, 4)])
+            self.add_module("final_linear1_%s" % name, nn.Linear(n_flat, 160, 1))
+            self.add_module("final_linear2_%s" % name, nn.Linear(160, 10, 1))
+            self.add_module("final_linear3_%s" % name, nn.Linear(10, -n, 1))
+            if -n != 1:
+                raise NotImplementedError("pooled head with %d outputs: only the scalar (age, -1) head is shipped" % -n)
         self._tail = None
         self._tail_key = None
+        self._age = None
+        self._age_key = None
         self.left_hemis_only = False
         self.max_surf_distance = 3.0
 
     def _version_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
+    def age_params(self):
+        """{AGE_PARAM_NAMES entry: parameter tensor} of the pooled head (reference names, task 'age')."""
+        own = dict(self.named_parameters())
+        return OrderedDict((k, own[k.replace("_age.", "_%s." % self.age_task)]) for k in AGE_PARAM_NAMES)
+
+    def age_head(self):
+        """AgeHead on this module's parameters (read in place), or None without a pooled head."""
+        if self.age_task is None:
+            return None
+        key = self._version_key()
+        if self._age is None or self._age_key != key:
+            prm = OrderedDict((k, v.detach()) for k, v in self.age_params().items())
+            dev = next(iter(prm.values())).device
+            prm = OrderedDict((k, v.to(torch.float32).contiguous()) for k, v in prm.items())
+            self._age = AgeHead(prm, self.c_feat, self.n_flat, dev)
+            self._age_key = key
+        return self._age
+
     def tail(self, eng):
         key = (id(eng), self._version_key(), self.left_hemis_only, self.max_surf_distance)
         if self._tail is None or self._tail_key != key:
-            self._tail = Tail(eng, self.out_channels, self.left_hemis_only, self.max_surf_distance)
+            self._tail = Tail(eng, self.dense_channels, self.left_hemis_only, self.max_surf_distance)
             self._tail_key = key
         return self._tail
 
     def split_raw(self, raw_cl):
-        """(D,H,W,n_out) raw logits -> {task: (1,n,D,H,W) view}."""
+        """(D,H,W,n_out) raw logits -> {task: (1,n,D,H,W) view} of the dense heads."""
         out, r0 = OrderedDict(), 0
-        for name, n in self.out_channels.items():
+        for name, n in self.dense_channels.items():
             out[name] = raw_cl[..., r0:r0 + n].permute(3, 0, 1, 2).unsqueeze(0)
             r0 += n
         return out
+
+    def run_age(self, feat_cl, dims):
+        """{age task: (1,) raw output} on the channels-last normalised feature, or {} without a pooled head."""
+        ah = self.age_head()
+        if ah is None:
+            return {}
+        p, _ = ah.forward(feat_cl.contiguous(), dims)
+        return {self.age_task: p}
 
     @torch.no_grad()
     @L.on_device(lambda self, x, *a, **k: x[self.out_feat_level])
@@ -312,12 +489,18 @@ class TaskHead(nn.Module):
         res = []
         for b in range(x.shape[0]):
             dev = x.device
-            sd = {"head." + k: v.detach() for k, v in self.state_dict().items()}
-            eng = _HeadOnlyEngine(sd, self.c_feat, dev)
-            tail = Tail(eng, self.out_channels, self.left_hemis_only, self.max_surf_distance)
             feat_cl = x[b].permute(1, 2, 3, 0).contiguous().to(torch.float32)
-            raw, _ = tail.run_raw(feat_cl, tuple(x.shape[2:]), want_feat=False)
-            res.append(self.split_raw(raw))
+            out = OrderedDict()
+            if self.dense_channels:
+                sd = {"head." + k: v.detach() for k, v in self.state_dict().items()}
+                eng = _HeadOnlyEngine(sd, self.c_feat, dev)
+                tail = Tail(eng, self.dense_channels, self.left_hemis_only, self.max_surf_distance)
+                raw, _ = tail.run_raw(feat_cl, tuple(x.shape[2:]), want_feat=False)
+                out.update(self.split_raw(raw))
+            elif self.age_task is not None and dev.type != "cuda":
+                raise L.BfmError("TaskHead needs a HIP device; the product path has no CPU fallback")
+            out.update(self.run_age(feat_cl, tuple(x.shape[2:])))
+            res.append(out)
         if len(res) == 1:
             return res[0]
         return OrderedDict((k, torch.cat([r[k] for r in res], 0)) for k in res[0])
@@ -361,7 +544,7 @@ class MultiInputIndepJoiner(nn.Module):
                 bufs = [f for f, _ in feats]
                 dims = feats[-1][1]
                 out = OrderedDict()
-                if self.head is not None:
+                if self.head is not None and self.head.dense_channels:
                     tail = self.head.tail(eng)
                     raw, fnorm = tail.run_raw(bufs[-1], dims, want_feat=True)
                     if fnorm is not None:
@@ -369,9 +552,12 @@ class MultiInputIndepJoiner(nn.Module):
                     heads = self.head.split_raw(raw)
                 elif self.backbone.is_unit_vector:
                     bufs[-1] = normalize_cl(eng, bufs[-1], dims)
-                    heads = {}
+                    heads = OrderedDict()
                 else:
-                    heads = {}
+                    heads = OrderedDict()
+                if self.head is not None and self.head.age_task is not None:
+                    # the pooled head reads the same (normalised) last feature as the dense heads (head.py:50)
+                    heads.update(self.head.run_age(bufs[-1], dims))
                 out["feat" + self.postfix] = [UNetEngine.as_ncdhw(f) for f in bufs]
                 out.update(heads)
                 per_b.append(out)
@@ -386,6 +572,15 @@ class MultiInputIndepJoiner(nn.Module):
                         m[k] = torch.cat([p[k] for p in per_b], 0)
                 outs.append(m)
         return outs, [inp[input_name] for inp in input_list]
+
+
+class AgeProcessor(nn.Module):
+    """joiner.py:57-66: abs of the raw age (a (B,) tensor: one value per case)."""
+
+    def forward(self, outputs, *kwargs):
+        for output in outputs:
+            output["age"] = output["age"].abs()
+        return outputs
 
 
 class SegProcessor(nn.Module):
@@ -448,6 +643,8 @@ def get_processors(gen_args, train_args, tasks, device, exclude_keys=[]):
         processors.append(UncertaintyProcessor(train_args.output_names))
     if getattr(train_args.losses, "implicit_pathol", False):
         raise NotImplementedError("PatholSeg (implicit_pathol) needs external checkpoints; outside the hot path")
+    if "age" in tasks:
+        processors.append(AgeProcessor())
     if "segmentation" in tasks and "segmentation" not in exclude_keys:
         processors.append(SegProcessor())
     if "distance" in tasks:

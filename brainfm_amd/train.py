@@ -12,7 +12,8 @@ Mirrors the reference's iteration -- Trainer/engine.py:96-147:
 
 with the criterion of Trainer/models/criterion.py (SetMultiCriterion: sum over the samples / all_samples) restricted to
 the supervised dense heads: T1 T2 FLAIR CT (+_grad, optional <key>_DM weights), SR(+_grad), distance, registration
-(+_grad), bias_field_log (l1 | l2, soft mask 1 - seg[:, 0]), seg_ce, seg_dice.  Any other loss name raises.
+(+_grad), bias_field_log (l1 | l2, soft mask 1 - seg[:, 0]), seg_ce, seg_dice, and loss_age of the pooled scalar head
+(| abs(p) - age |, models.AgeHead).  Any other loss name raises.
 
 Everything numeric runs in the HIP library; torch holds buffers, adds the per-sample gradients and runs the RCCL
 all-reduce.  There is no CPU path: without the extension or a HIP device construction fails.
@@ -32,7 +33,7 @@ from . import models as M
 IMAGE_KEYS = ("T1", "T2", "FLAIR", "CT")
 SUPPORTED = set(IMAGE_KEYS) | {k + "_grad" for k in IMAGE_KEYS} | {
     "SR", "SR_grad", "distance", "surface", "registration", "registration_grad", "bias_field_log", "seg_ce", "seg_dice",
-    "pathol_ce", "pathol_dice"}
+    "pathol_ce", "pathol_dice", "age"}
 
 
 class LossScaler:
@@ -252,7 +253,7 @@ class TrainStep:
 
     def __init__(self, engine, tail, loss_names, loss_weights, weights_ce, all_samples, max_surf_distance=3.0,
                  bias_field_log_type="l2", lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, clip_max_norm=0.0,
-                 scaler=None):
+                 scaler=None, age_head=None):
         bad = [n for n in loss_names if n not in SUPPORTED]
         if bad:
             raise L.BfmError("losses outside the HIP training path: %s" % bad)
@@ -279,6 +280,14 @@ class TrainStep:
         self._lane = 0
         self._ws_lane = {}
         self._ws_bytes = (self.lib.bfm_loss_workspace(max(nseg, 1)), self.lib.bfm_loss_l1_multi_workspace())
+        # the pooled scalar head (models.AgeHead, e.g. TaskHead.age_head()): the step trains its own copy of the parameters
+        self.age = None
+        if age_head is not None:
+            prm = OrderedDict((k, v.detach().to(device=self.dev, dtype=torch.float32).clone().contiguous())
+                              for k, v in age_head.params.items())
+            self.age = M.AgeHead(prm, age_head.c_feat, age_head.n_flat, self.dev)
+        if "age" in self.loss_names and self.age is None:
+            raise L.BfmError("loss 'age' needs the pooled scalar head (TrainStep(..., age_head=model.head.age_head()))")
 
     @property
     def _ws(self):
@@ -307,6 +316,9 @@ class TrainStep:
         for task, (r0, n) in self.tail.row_of.items():
             p["head.final_conv_%s.weight" % task] = self.tail.head_w[r0:r0 + n]
             p["head.final_conv_%s.bias" % task] = self.tail.head_b[r0:r0 + n]
+        if self.age is not None:                                   # registered after the dense heads (head.py:38-48)
+            for k, v in self.age.params.items():
+                p["head." + k] = v
         return p
 
     def grad_store(self):
@@ -314,6 +326,8 @@ class TrainStep:
         st = self.__dict__.get("_grad_store")
         if st is None:
             named = [("head.weight_all", (self.tail.n_out, self.tail.c_feat)), ("head.bias_all", (self.tail.n_out,))]
+            if self.age is not None:                               # the pooled head's backward ends before the backbone's
+                named += [("head." + k, tuple(v.shape)) for k, v in self.age.params.items()]
             for pair in list(reversed(self.eng.dec)) + list(reversed(self.eng.enc)):
                 for ly in reversed(pair):
                     named.append((ly.name + ".conv.weight", tuple(ly.w_raw.shape)))
@@ -333,7 +347,7 @@ class TrainStep:
 
     # ------------------------------------------------------------------ checkpoints (scripts/train.py:205-214)
     def _ref_shape(self, name, t):
-        if name.startswith("head.") and name.endswith(".weight"):
+        if name.startswith("head.final_conv_") and name.endswith(".weight"):
             return tuple(t.shape) + (1, 1, 1)                      # nn.Conv3d(C, n, 1) weight
         return tuple(t.shape)
 
@@ -622,7 +636,10 @@ class TrainStep:
             fn = feat_last
         dRaw = torch.zeros_like(raw)
         vals = torch.zeros(4 * len(self.loss_names) + 2 * tail.n_out + 8, dtype=torch.float64, device=self.dev)
-        slots, _ = self._sample_losses(raw, dims, target, sample, dRaw, vals, scale, rows=rows)
+        slots, k_used = self._sample_losses(raw, dims, target, sample, dRaw, vals, scale, rows=rows)
+        age_tape = None
+        if self.age is not None:
+            _, age_tape = self.age.forward(fn, dims)
         sink = getattr(eng, "grad_sink", None)
         dW = sink.out("head.weight_all", (n_out, cf)) if sink is not None else torch.empty((n_out, cf), dtype=torch.float32, device=self.dev)
         db = sink.out("head.bias_all", (n_out,)) if sink is not None else torch.empty(n_out, dtype=torch.float32, device=self.dev)
@@ -637,6 +654,27 @@ class TrainStep:
         if sink is not None:
             sink.done("head.weight_all")
             sink.done("head.bias_all")
+        age_grads = None
+        if age_tape is not None:
+            # criterion.py loss_age; its pooled gradient joins dFn after the dense heads' and before normalize_bwd
+            age_t = self._age_target(target)
+            on = "age" in self.loss_names and age_t is not None
+            coef = scale * self.loss_weights.get("loss_age", 0.0) / self.all_samples if on else 0.0
+            loss_ptr = None
+            if on:
+                slots["age"] = [(k_used, 1)]
+                loss_ptr = C.c_void_p(vals.data_ptr() + 8 * k_used)
+                self._touched_heads.add("age")
+            age_grads = OrderedDict()
+            for k_, v_ in self.age.params.items():
+                name = "head." + k_
+                age_grads[name] = (sink.out(name, tuple(v_.shape)) if sink is not None else
+                                   torch.empty(v_.shape, dtype=torch.float32, device=self.dev))
+            self.age.backward(age_tape, age_t if on else 0.0, coef, loss_ptr,
+                              {k_[5:]: v_ for k_, v_ in age_grads.items()}, dFn)
+            if sink is not None:
+                for name in age_grads:
+                    sink.done(name)
         if eng.unit_feat:
             dfeat = torch.empty_like(dFn)
             L.check(lib.bfm_normalize_bwd(L.ptr(feat_last), L.ptr(dFn), cf, nvox, 1e-12, L.ptr(dfeat), st), "normalize_bwd")
@@ -646,11 +684,25 @@ class TrainStep:
         for task, (r0, n) in tail.row_of.items():
             g["head.final_conv_%s.weight" % task] = dW[r0:r0 + n]
             g["head.final_conv_%s.bias" % task] = db[r0:r0 + n]
+        if age_grads is not None:
+            g.update(age_grads)
         # heads no loss of this sample reached: the reference leaves their .grad None (the all-zero rows above only keep
         # the gradient dictionary's layout fixed for the flat all-reduce); loss_and_grads collects who was reached
         self._touched_heads.update(task for task, (r0, n) in tail.row_of.items()
                                    if any(r in self._active_rows for r in range(r0, r0 + n)))
         return g, slots, vals
+
+    @staticmethod
+    def _age_target(target):
+        """target['age'] as a float (a float, a 0-d or a one-element tensor; datasets.py:678-679), or None."""
+        a = target.get("age") if target is not None else None
+        if a is None:
+            return None
+        if isinstance(a, torch.Tensor) or isinstance(a, np.ndarray):
+            if (a.numel() if isinstance(a, torch.Tensor) else a.size) != 1:
+                raise L.BfmError("target['age'] holds %d values; one training sample takes one age" % int(np.prod(a.shape)))
+            return float(a.reshape(-1)[0])
+        return float(a)
 
     @L.on_device(lambda self, *a, **k: self.dev)
     def loss_and_grads(self, xs, target, samples):
@@ -844,7 +896,7 @@ class TrainStep:
             self.allreduce_events = list(store.events) if store.events else []
         if multi:
             world = dist.get_world_size(group)
-            tasks = list(self.tail.row_of.keys())
+            tasks = list(self.tail.row_of.keys()) + (["age"] if self.age is not None else [])
             keys = list(self.loss_names)                       # fixed layout: a rank may lack a loss another one has
             # gloo reduces on the host, RCCL on the device
             rdev = self.dev if dist.get_backend(group) == "nccl" else torch.device("cpu")
@@ -868,5 +920,8 @@ class TrainStep:
             if task not in touched:
                 grads.pop("head.final_conv_%s.weight" % task, None)
                 grads.pop("head.final_conv_%s.bias" % task, None)
+        if self.age is not None and "age" not in touched:
+            for k_ in self.age.params:
+                grads.pop("head." + k_, None)
         stepped, _ = self.apply(grads, lr, weight_decay, grad_div=grad_div)
         return loss_dict, total, stepped

@@ -856,6 +856,53 @@ int bfm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, floa
 int bfm_grad_sumsq(const float* g, int64_t n, double* out, int32_t* nonfinite, void* workspace, size_t workspace_bytes,
                    bfm_stream_t stream);
 
+/* ------------------------------------------------------------------- pooled scalar (brain-age) head
+ * TaskHead's head for out_channels['age'] = -1 (Trainer/models/head.py:39-48 building, :61-66 forward):
+ * MaxPool3d(4,4) -> ConvBlock(C_feat->16) -> MaxPool3d(4,4) -> ConvBlock(16->4) -> torch.flatten(x, 1) (NCDHW order)
+ * -> final_linear1_age (N->160) + ReLU -> final_linear2_age (160->10) + ReLU -> final_linear3_age (10->1), with
+ * ConvBlock = Conv3d(k=3, s=1, p=1, bias) + LeakyReLU(0.2) (head.py:152-167).  Weights in torch's layouts (Conv3d
+ * (Cout,Cin,3,3,3), Linear (out,in)); activations channels-last; fp32, no atomics, fixed-order sums (same bits on every
+ * run).  The forward is 6 launches, the backward (loss included) 8. */
+typedef struct bfm_age_params {
+    const float *c1w, *c1b;   /* pool_layers.1.main.{weight,bias}: (16, C_feat, 3,3,3), (16) */
+    const float *c2w, *c2b;   /* pool_layers.3.main.{weight,bias}: (4, 16, 3,3,3), (4) */
+    const float *l1w, *l1b;   /* final_linear1_age: (160, N), (160) */
+    const float *l2w, *l2b;   /* final_linear2_age: (10, 160), (10) */
+    const float *l3w, *l3b;   /* final_linear3_age: (1, 10), (1) */
+} bfm_age_params_t;
+typedef struct bfm_age_grads {
+    float *c1w, *c1b, *c2w, *c2b, *l1w, *l1b, *l2w, *l2b, *l3w, *l3b;   /* same shapes as bfm_age_params_t */
+} bfm_age_grads_t;
+/* nn.MaxPool3d(4, 4) (head.py:40,42; floor mode, no padding) of in (D,H,W,C) -> out (D/4,H/4,W/4,C) plus arg (same shape,
+ * bytes): dz*16 + dy*4 + dx of the window's maximum, scanned z, y, x; first maximum on ties, NaN sticky as in nn.MaxPool3d. */
+int bfm_maxpool4(const float* in, int C, int D, int H, int W, float* out, uint8_t* arg, bfm_stream_t stream);
+/* Its backward (autograd of max_pool3d): g (D/4,H/4,W/4,C) at each window's arg.  accumulate = 0: dst (D,H,W,C) is written
+ * whole (0 off the argmax); accumulate = 1: dst[argmax] += g only (one target per window and channel: no atomics). */
+int bfm_maxpool4_bwd(const float* g, const uint8_t* arg, int C, int D, int H, int W, float* dst, int accumulate,
+                     bfm_stream_t stream);
+/* ConvBlock forward (head.py:161-167): y (D,H,W,Cout) = LeakyReLU_0.2(conv3x3x3(x, w, zero padding) + b); Cout % 4 == 0. */
+int bfm_age_conv_fwd(const float* x, int Cin, int D, int H, int W, const float* w, const float* b, int Cout, float* y,
+                     bfm_stream_t stream);
+/* ConvBlock backward: dy = d/dy (after the activation; y = the forward's output, or y = NULL when dy is already the gradient
+ * before it) -> dx (D,H,W,Cin) (NULL: not formed), dw (Cout,Cin,3,3,3), db (Cout), all written.  Two launches; the weight
+ * gradient is summed per 256 voxels into the workspace and the partials added in order. */
+size_t bfm_age_conv_bwd_workspace(int Cin, int D, int H, int W, int Cout);
+int bfm_age_conv_bwd(const float* x, int Cin, int D, int H, int W, const float* w, int Cout, const float* y, const float* dy,
+                     float* dx, float* dw, float* db, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
+/* torch.flatten(x, 1) of the (nv, 4) channels-last conv output (flat index c*nv + voxel) -> the three Linear layers
+ * (head.py:64-66): h1 (160), h2 (10) after their ReLU, out[0] = the raw age (before AgeProcessor).  n_flat == 4 * nv, the
+ * reference's 4 * s0 // 16 * s1 // 16 * s2 // 16 for a matching size; BFM_E_SHAPE otherwise. */
+int bfm_age_mlp_fwd(const float* y2, int nv, const bfm_age_params_t* prm, int n_flat, float* h1, float* h2, float* out,
+                    bfm_stream_t stream);
+/* Backward of the three Linear layers.  dp_in (device, 1 float) = d/d(raw age); or dp_in = NULL: loss_age of
+ * Trainer/criterion.py (| abs(p) - age |, evaluated in float64 -> loss[0] unless NULL) and d/dp = coef * sign(|p| - age) *
+ * sign(p) (coef = weight / all_samples * loss scale; 0 at p == 0 or |p| == age, as torch's abs backward).  Writes every
+ * final_linear gradient of grd and dy2 (nv, 4) = d/d(conv output).  workspace >= bfm_age_mlp_bwd_workspace(). */
+size_t bfm_age_mlp_bwd_workspace(void);
+int bfm_age_mlp_bwd(const float* y2, int nv, const bfm_age_params_t* prm, int n_flat, const float* h1, const float* h2,
+                    const float* p, const float* dp_in, double age, float coef, double* loss, const bfm_age_grads_t* grd,
+                    float* dy2, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
