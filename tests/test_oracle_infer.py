@@ -158,3 +158,136 @@ def test_uncertainty_head_set():
         else:
             _close(out[k].numpy(), d["out/" + k], w=w)
     _close(out["feat"][-1].numpy(), d["feat_last"], w=w)
+
+
+# ---------------------------------------------------------------- infer_deep_*.npz: the shipped 6-level net
+# tests/golden/make_golden_deep.py ran the reference on its default initialisation under torch.manual_seed(1) -- the
+# weights bench.py runs -- and stored their sha256 hashes, not the 1 GB of weights.  The helpers below are shared with
+# tests/test_gpu_infer.py, which holds the HIP path to the same fixture.
+
+def load_deep():
+    """infer_deep_a.npz (hashes, configuration, case A), _b.npz and _c.npz as one dict (one file per case keeps each
+    fixture under 1 MiB)."""
+    d = {}
+    for case in "abc":
+        d.update(load_npz("infer_deep_%s.npz" % case))
+    return d
+
+
+def sha256(t):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(t.detach().cpu().numpy()).tobytes()).hexdigest()
+
+
+def deep_case_c_input(d):
+    """Case C of the deep fixture: a seeded 64 x 80 x 96 draw with a zero slab (pooling 5 -> 2, upsampling 2 -> 5)."""
+    seed, shape = int(d["cfg"][5]), tuple(int(v) for v in d["cfg"][6:9])
+    x = torch.rand((1, 1) + shape, generator=torch.Generator().manual_seed(seed))
+    x[:, :, :, :, :9] = 0
+    return x
+
+
+_DEEP_SD = {}
+
+
+def deep_state_dict():
+    """The product's full-width model under torch.manual_seed(1), the construction bench.py uses (CPU tensors)."""
+    if not _DEEP_SD:
+        from brainfm_amd import models as M, test_utils as TU
+        torch.manual_seed(1)
+        _, _, model, _, _, _ = M.build_model(*TU.default_inference_args(64, 6), "cpu")
+        _DEEP_SD.update({k: v.detach() for k, v in model.state_dict().items()})
+    return _DEEP_SD
+
+
+def _maxerr(a, b, scale):
+    return float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max()) / max(1e-30, scale)
+
+
+def deep_compare_single(out, d, p, tie_gap):
+    """One unstitched output dict (tensors on any device) against case p ("B/" or "C/") of the deep fixture. Returns
+    ({name: worst error relative to the map's max |reference|}, [(flat voxel, gap) of every label exception]). Float
+    maps and segmentation: max-norm at the sampled voxels (segmentation at every fourth of them).  Features, per level
+    with M = max |reference|: the sampled entries, and per channel the mean, the RMS (| |a| - |b| | <= |a - b|), min and
+    max, each within err * M. Labels: the 1/8 sublattice equals the reference's except at voxels the fixture lists as
+    ties; over the whole map, the histogram of the non-tie voxels equals the reference's (tie voxels are compared one by
+    one).  An exception must have a reference gap below tie_gap."""
+    shape = tuple(int(v) for v in d[p + "shape"])
+    dev = out["segmentation"].device
+    idx = torch.from_numpy(d[p + "idx"]).to(dev)
+    errs = {}
+    for i, k in enumerate(d[p + "float_keys"]):
+        ref = d[p + "floats"][i]
+        errs[str(k)] = _maxerr(out[str(k)].detach().reshape(-1)[idx].cpu().numpy(), ref, np.abs(ref).max())
+    seg_idx = torch.from_numpy(d[p + "seg_idx"]).to(dev)
+    seg = out["segmentation"][0].reshape(out["segmentation"].shape[1], -1)[:, seg_idx].cpu().numpy()
+    errs["segmentation"] = _maxerr(seg, d[p + "seg"], np.abs(d[p + "seg"]).max())
+    for i, f in enumerate(out["feat"]):
+        pre = p + "feat%d_" % i
+        c = f.shape[1]
+        assert c == d[pre + "mean"].shape[0], (i, tuple(f.shape))
+        M = float(max(np.abs(d[pre + "min"]).max(), np.abs(d[pre + "max"]).max()))
+        f64 = f.detach()[0].reshape(c, -1).double()
+        n = f64.shape[1]
+        e = [_maxerr(f.detach().reshape(-1)[torch.from_numpy(d[pre + "idx"]).to(dev)].cpu().numpy(), d[pre + "vals"], M),
+             _maxerr(f64.mean(1).cpu().numpy(), d[pre + "mean"], M),
+             _maxerr(((f64 * f64).sum(1) / n).sqrt().cpu().numpy(), np.sqrt(d[pre + "sumsq"] / n), M),
+             _maxerr(f64.min(1).values.cpu().numpy(), d[pre + "min"], M),
+             _maxerr(f64.max(1).values.cpu().numpy(), d[pre + "max"], M)]
+        errs["feat%d" % i] = max(e)
+    lab = out["label"].detach()[0, 0].cpu()
+    assert tuple(lab.shape) == shape
+    tie_idx, tie_gaps, tie_lab = d[p + "tie_idx"], d[p + "tie_gap"], d[p + "tie_label"].astype(np.int64)
+    flat = lab.reshape(-1).numpy()
+    exc = np.nonzero(flat[tie_idx] != tie_lab)[0]
+    exceptions = [(int(tie_idx[j]), float(tie_gaps[j])) for j in exc]
+    sub = lab[::2, ::2, ::2].numpy()
+    zi, yi, xi = np.nonzero(sub != d[p + "label_sub"])
+    sub_flat = ((2 * zi) * shape[1] + 2 * yi) * shape[2] + 2 * xi
+    assert np.isin(sub_flat, tie_idx).all(), "sublattice label differences at voxels that are not ties: %s" % \
+        sub_flat[~np.isin(sub_flat, tie_idx)][:20]
+    hist_ref = d[p + "label_hist"].astype(np.int64)
+    nb = max(len(hist_ref), int(flat.max()) + 1)
+    non_tie = (np.bincount(flat, minlength=nb) - np.bincount(flat[tie_idx], minlength=nb))
+    non_tie_ref = np.bincount(np.arange(len(hist_ref)), weights=hist_ref, minlength=nb).astype(np.int64) - \
+        np.bincount(tie_lab, minlength=nb)
+    assert np.array_equal(non_tie, non_tie_ref), "label histogram off the tie voxels: %s" % \
+        np.nonzero(non_tie != non_tie_ref)[0]
+    for v, gap in exceptions:
+        print("%slabel exception at voxel %d: reference gap %.2e" % (p, v, gap))
+        assert gap < tie_gap, (v, gap)
+    return errs, exceptions
+
+
+def test_deep_fixture_weights_and_inputs_are_regenerated_here():
+    """The deep fixture holds hashes, not weights or volumes: the product's build_model under torch.manual_seed(1) draws
+    the reference's 84 state-dict tensors bit for bit, and bench.make_volume(256), bench.make_atlas() and the case-C
+    draw are the inputs the reference ran."""
+    import bench
+    d = load_deep()
+    sd = deep_state_dict()
+    assert list(sd.keys()) == [str(k) for k in d["sd_names"]] and len(sd) == 84
+    bad = [k for k, h in zip(d["sd_names"], d["sd_sha256"]) if sha256(sd[str(k)]) != str(h)]
+    assert not bad, bad
+    assert sha256(bench.make_volume(256, "cpu")) == str(d["sha_volume"])
+    atlas, aff = bench.make_atlas()
+    assert sha256(atlas) == str(d["sha_atlas"]) and np.array_equal(aff, d["atlas_aff"])
+    assert sha256(deep_case_c_input(d)) == str(d["sha_C_input"])
+
+
+def test_oracle_six_levels_odd_shape_vs_reference_deep_golden():
+    """The oracle at the shipped architecture (64 maps, 6 levels: GroupNorm over 1024 / 2048 channels, a 2048-channel
+    first feature) on case C, 64 x 80 x 96: floor pooling 5 -> 2 and nearest 2 -> 5 upsampling inside the net.  Floats and
+    features within 1e-3 (north-star tolerance) of the reference; labels equal except at reference ties (gap < 1e-5).
+    Measured: worst float error 4e-17 (the same ATen kernels), no label exception.  With ceil instead of floor pooling
+    the feature shapes already differ."""
+    d = load_deep()
+    x = deep_case_c_input(d)
+    with torch.no_grad():
+        out = O.forward_all(x, deep_state_dict(), f_maps=64, num_levels=6)
+    assert [tuple(f.shape[1:]) for f in out["feat"]] == [(2048, 2, 2, 3), (1024, 4, 5, 6), (512, 8, 10, 12),
+                                                        (256, 16, 20, 24), (128, 32, 40, 48), (64, 64, 80, 96)]
+    errs, exc = deep_compare_single(out, d, "C/", tie_gap=1e-5)
+    print("oracle vs reference, case C: worst %.2e (%s), %d label exceptions" %
+          (max(errs.values()), max(errs, key=errs.get), len(exc)))
+    assert max(errs.values()) <= 1e-3, errs
