@@ -70,6 +70,13 @@ class AgeGrads(C.Structure):
 GATHER_MAX_JOBS = 12          # BFM_GATHER_MAX_JOBS of include/brainfm_hip.h
 
 
+VERTEX_SETS_MAX = 4           # BFM_VERTEX_SETS_MAX of include/brainfm_hip.h
+
+
+class VertexSet(C.Structure):
+    _fields_ = [("V", C.c_void_p), ("n", C.c_int64)]
+
+
 class GatherJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("out", C.c_void_p), ("mean", C.c_float), ("scale", C.c_float), ("pre", C.c_int),
                 ("default_max", C.c_int), ("post_div", C.c_float), ("clamp", C.c_int), ("clamp_lo", C.c_float),
@@ -233,6 +240,9 @@ SIGNATURES = {
     "bfm_dopri5_advect_init": (_I, [C.POINTER(Dopri5Advect), C.c_double, C.c_double, _P]),
     "bfm_dopri5_advect_steps": (_I, [C.POINTER(Dopri5Advect), _I, _P]),
     "bfm_randn_philox": (_I, [_P, _L, C.c_uint64, C.c_uint64, _F, _P]),
+    "bfm_svf_integrate_workspace": (_Z, [_I, _I, _I]),
+    "bfm_svf_integrate": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "bfm_deform_vertices": (_I, [_P, _I, _I, _I, C.POINTER(VertexSet), _I, C.POINTER(_F), C.POINTER(_F), _I, _I, _P]),
     "bfm_deform_zoom_workspace": (_Z, []),
     "bfm_deform_zoom_minmax": (_I, [_P, _I, _I, _I, C.POINTER(ZoomAxis), _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F),
                                     C.POINTER(_I), _P, _P, _Z, _P]),

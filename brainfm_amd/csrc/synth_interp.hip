@@ -11,6 +11,7 @@
 // Built with -ffp-contract=off: a*b + c*d stays mul, mul, add like the reference's eager torch ops,
 // which is what makes the fp32 results bit-identical to the CPU path.
 #include "bfm_common.h"
+#include "gather3d.h"
 #include <cstdlib>
 
 namespace {
@@ -23,18 +24,7 @@ inline int grid_for(int64_t n, int tpb = 256, int cap = 8192) {
 #define GRID_STRIDE(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
-// Texel loads of the gathers (data-dependent addresses, lines re-used from the L1 by neighbouring lanes and waves) go past
-// the per-CU vector L1: agent scope = global_load_dword sc1, served by the XCD's L2.  Round 3 cornered what round 2 had
-// only worked around (HISTORY.md section 3.3, tests/diag/diag_atlas_repro.py, profiles/r03_atlas_gather_hazard.txt): with
-// ordinary loads such a gather gets wrong texels -- whole 16-lane groups -- whenever a kernel that fills its LDS by LDS-DMA
-// (global_load_lds, every conv kernel here) runs beside it on another stream; an L1 invalidate at kernel start does not
-// help, L1-bypassing loads (agent or system scope) do.  The value type is float or a 4-byte bit pattern.
-__device__ __forceinline__ float ld_tex(const float* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t ld_tex(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// ld_tex, the validity test, corners / weights and the lerp chain: gather3d.h (shared with synth_svf.hip).
 
 // C == 1.  MODE 0 ships: the two z-neighbours of a corner in ONE 8-byte load through a buffer descriptor (aux 16 = sc1), four
 // loads per sample instead of eight (20 against 25 us at 160^3).  MODE 1: the same with sc0 sc1; MODE 2: eight 4-byte
@@ -48,14 +38,9 @@ __global__ void interp_linear1(const float* __restrict__ X, int nx, int ny, int 
     const __amdgpu_buffer_rsrc_t R = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(X), 0, vol_bytes, 0x00020000);
     GRID_STRIDE(i, n) {
         const float x = II[i], y = JJ[i], z = KK[i];
-        const bool ok = (x > 0.f) && (y > 0.f) && (z > 0.f) && (x <= (float)(nx - 1)) && (y <= (float)(ny - 1)) &&
-                        (z <= (float)(nz - 1));
-        if (!ok) { out[i] = defv; continue; }
-        const float fxf = floorf(x), fyf = floorf(y), fzf = floorf(z);
-        const int fx = (int)fxf, fy = (int)fyf, fz = (int)fzf;
-        const int cx = min(fx + 1, nx - 1), cy = min(fy + 1, ny - 1), cz = min(fz + 1, nz - 1);
-        const float wcx = x - fxf, wcy = y - fyf, wcz = z - fzf;
-        const float wfx = 1.f - wcx, wfy = 1.f - wcy, wfz = 1.f - wcz;
+        if (!interp_ok(x, y, z, nx, ny, nz)) { out[i] = defv; continue; }
+        const Trilin t = trilin_setup(x, y, z, nx, ny, nz);
+        const int fx = t.fx, fy = t.fy, fz = t.fz, cx = t.cx, cy = t.cy, cz = t.cz;
         const int64_t sx = (int64_t)ny * nz, sy = nz;
         const bool zp = cz != fz;
         auto pair = [&](int a, int b, float& lo, float& hi) {
@@ -79,13 +64,7 @@ __global__ void interp_linear1(const float* __restrict__ X, int nx, int ny, int 
         };
         float t000, t001, t100, t101, t010, t011, t110, t111;
         pair(fx, fy, t000, t001); pair(cx, fy, t100, t101); pair(fx, cy, t010, t011); pair(cx, cy, t110, t111);
-        const float c00 = t000 * wfx + t100 * wcx;
-        const float c01 = t001 * wfx + t101 * wcx;
-        const float c10 = t010 * wfx + t110 * wcx;
-        const float c11 = t011 * wfx + t111 * wcx;
-        const float c0 = c00 * wfy + c10 * wcy;
-        const float c1 = c01 * wfy + c11 * wcy;
-        out[i] = c0 * wfz + c1 * wcz;
+        out[i] = trilin_lerp(t, t000, t100, t010, t110, t001, t101, t011, t111);
     }
 }
 
@@ -95,17 +74,12 @@ __global__ void interp_linear(const float* __restrict__ X, int nx, int ny, int n
     GRID_STRIDE(i, n) {
         const float x = II[i], y = JJ[i], z = KK[i];
         float* o = out + i * C;
-        const bool ok = (x > 0.f) && (y > 0.f) && (z > 0.f) && (x <= (float)(nx - 1)) && (y <= (float)(ny - 1)) &&
-                        (z <= (float)(nz - 1));
-        if (!ok) {
+        if (!interp_ok(x, y, z, nx, ny, nz)) {
             for (int c = 0; c < C; ++c) o[c] = defv;
             continue;
         }
-        const float fxf = floorf(x), fyf = floorf(y), fzf = floorf(z);
-        const int fx = (int)fxf, fy = (int)fyf, fz = (int)fzf;
-        const int cx = min(fx + 1, nx - 1), cy = min(fy + 1, ny - 1), cz = min(fz + 1, nz - 1);
-        const float wcx = x - fxf, wcy = y - fyf, wcz = z - fzf;
-        const float wfx = 1.f - wcx, wfy = 1.f - wcy, wfz = 1.f - wcz;
+        const Trilin t = trilin_setup(x, y, z, nx, ny, nz);
+        const int fx = t.fx, fy = t.fy, fz = t.fz, cx = t.cx, cy = t.cy, cz = t.cz;
         const int64_t sx = (int64_t)ny * nz * C, sy = (int64_t)nz * C;
         const float* p000 = X + fx * sx + fy * sy + (int64_t)fz * C;
         const float* p100 = X + cx * sx + fy * sy + (int64_t)fz * C;
@@ -115,15 +89,9 @@ __global__ void interp_linear(const float* __restrict__ X, int nx, int ny, int n
         const float* p101 = X + cx * sx + fy * sy + (int64_t)cz * C;
         const float* p011 = X + fx * sx + cy * sy + (int64_t)cz * C;
         const float* p111 = X + cx * sx + cy * sy + (int64_t)cz * C;
-        for (int c = 0; c < C; ++c) {
-            const float c00 = ld_tex(p000 + c) * wfx + ld_tex(p100 + c) * wcx;
-            const float c01 = ld_tex(p001 + c) * wfx + ld_tex(p101 + c) * wcx;
-            const float c10 = ld_tex(p010 + c) * wfx + ld_tex(p110 + c) * wcx;
-            const float c11 = ld_tex(p011 + c) * wfx + ld_tex(p111 + c) * wcx;
-            const float c0 = c00 * wfy + c10 * wcy;
-            const float c1 = c01 * wfy + c11 * wcy;
-            o[c] = c0 * wfz + c1 * wcz;
-        }
+        for (int c = 0; c < C; ++c)
+            o[c] = trilin_lerp(t, ld_tex(p000 + c), ld_tex(p100 + c), ld_tex(p010 + c), ld_tex(p110 + c), ld_tex(p001 + c),
+                               ld_tex(p101 + c), ld_tex(p011 + c), ld_tex(p111 + c));
     }
 }
 

@@ -177,10 +177,15 @@ class BaseGen(torch.utils.data.Dataset):
         if isinstance(self.augmentation_steps, list):
             self.augmentation_steps = {"synth": self.augmentation_steps, "real": self.augmentation_steps}
         self.input_prob = getattr(gen_args, "modality_probs", None)
+        self.cases = cases or []
+        if getattr(gen_args.task, "surface", False):
+            if int(getattr(self.synth_args, "n_steps_svf_integration", 8)) < 0:
+                raise L.BfmError("n_steps_svf_integration must be >= 0, got %d" % self.synth_args.n_steps_svf_integration)
+            for case in self.cases:
+                self._check_surface_case(case)
         self.device = torch.device(device if not isinstance(device, int) else "cuda:%d" % device)
         if self.device.type != "cuda":
             raise L.BfmError("the generator runs on a HIP device only; there is no CPU fallback in the product path")
-        self.cases = cases or []
         self.volumes = DeviceVolumes(self.device)
         self._batch = None                                # pending gather jobs while _targets collects them
         self._psum = (None, 0.0)                          # (target['pathology'] tensor, its sum) as the host knows it; the
@@ -256,7 +261,20 @@ class BaseGen(torch.utils.data.Dataset):
         F = GU.myzoom_torch(Fsmall, factor)
         if photo_mode:
             F[:, :, :, 1] = 0
+        if "surface" in self.tasks:                           # datasets.py:214-224: the SVF, integrated both ways
+            return GU.svf_integrate(F, self.n_steps_svf())
         return F, None
+
+    def n_steps_svf(self):
+        n = int(getattr(self.synth_args, "n_steps_svf_integration", 8))
+        if n < 0:
+            raise L.BfmError("n_steps_svf_integration must be >= 0, got %d" % n)
+        return n
+
+    def _check_surface_case(self, case):
+        if case.get("surface") is not None and self.synth_args.left_hemis_only:
+            # Generator/utils.py:481: "does not support left_hemis for now"
+            raise L.BfmError("a surface mesh with left_hemis_only is not supported (the reference does not support it)")
 
     def deform_grid(self, shp, A, c2, F):
         """datasets.py:264-303: one kernel for affine(+nonlinear) coordinates, clamp and the six extrema; the
@@ -324,7 +342,11 @@ class BaseGen(torch.utils.data.Dataset):
 
     def generate_deformation(self, setups, shp):
         scaling_factor_distances, A, c2 = self.random_affine_transform(shp)
-        if self.synth_args.nonlinear_transform:
+        if self.synth_args.nonlinear_transform and "surface" in self.tasks:
+            # zoom -> integrate (both directions) -> deform_grid of the integrated field (datasets.py:234-243)
+            F, Fneg = self.random_nonlinear_transform(setups["photo_mode"], setups["spac"])
+            grid = list(self.deform_grid(shp, A, c2, F))
+        elif self.synth_args.nonlinear_transform:
             Fsmall, factor = self._random_nonlinear_small(setups["photo_mode"], setups["spac"])
             F, grid = self.deform_grid_zoomed(shp, A, c2, Fsmall, factor, setups["photo_mode"])
             Fneg = None
@@ -797,6 +819,15 @@ class BaseGen(torch.utils.data.Dataset):
                 self._run_gather(jobs, deform_dict, setups["flip"])
         finally:
             self._batch = None
+        if "surface" in self.tasks:
+            # get_info never lists 'surface' among the modalities, so the reference's read_and_deform_target returns
+            # {'surface': 0.} (datasets.py:622-627).  A case that supplies a mesh gets it deformed as well (an extension:
+            # the reference never reaches read_and_deform_surface from __getitem__).
+            target["surface"] = 0.
+            if case.get("surface") is not None:
+                self._check_surface_case(case)
+                target.update(GU.read_and_deform_surface(None, "surface", case["surface"], setups, deform_dict,
+                                                         self.device, self.hemis_mask, self.size))
         if case.get("age") is not None:                       # datasets.py:85-113 (ages per subject), 678-679
             target["age"] = float(case["age"])
         return target

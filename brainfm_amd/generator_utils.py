@@ -9,6 +9,8 @@ torch tensors on the HIP device, the arithmetic runs in libbrainfm_hip.so:
   add_gamma_transform / add_bias_field / resample_resolution / add_noise   :568-638
   make_affine_matrix / binarize / resolution_sampler                 :34-57,:65-72,:102-116
   augment_pathology                                                  :542-560
+  svf_integrate (random_nonlinear_transform's 'surface' branch)      Generator/datasets.py:214-224
+  read_and_deform_surface                                            Generator/utils.py:479-531
 
 Random draws keep the reference's call order on ``np.random`` so a seeded host stream lines up;
 ``torch.randn`` is drawn on the device (RNG-stream parity across devices is not a goal).
@@ -475,3 +477,85 @@ def augment_pathology(Pprob, pde_func, t, shape_gen_args, device):
         return Pprob
     pde_func.V_dict = generate_velocity_3d(Pprob.shape, shape_gen_args.perlin_res, shape_gen_args.V_multiplier, device)
     return odeint_adjoint(pde_func, Pprob[None], t[:nt], shape_gen_args.dt, method=shape_gen_args.integ_method)[-1, 0]
+
+
+# ----------------------------------------------------------------------------- surface task
+def svf_integrate(F, n_steps):
+    """Generator/datasets.py:214-224: the nonlinear field F (sx,sy,sz,3) integrated as a stationary velocity field by n
+    steps of scaling and squaring, in both directions.  Returns (Fsvf, Fsvf_neg), bit for bit the reference's."""
+    _require_cuda(F, "svf_integrate")
+    n_steps = int(n_steps)
+    if n_steps < 0:
+        raise L.BfmError("n_steps_svf_integration must be >= 0, got %d" % n_steps)
+    lib = L.load()
+    Fc = F.to(torch.float32).contiguous()
+    if Fc.dim() != 4 or Fc.shape[3] != 3:
+        raise L.BfmError("svf_integrate needs a (sx, sy, sz, 3) field, got %s" % (tuple(Fc.shape),))
+    sx, sy, sz = (int(v) for v in Fc.shape[:3])
+    Fo, Fn = torch.empty_like(Fc), torch.empty_like(Fc)
+    ws = torch.empty(lib.bfm_svf_integrate_workspace(sx, sy, sz) if n_steps > 1 else 0, dtype=torch.uint8, device=Fc.device)
+    L.check(lib.bfm_svf_integrate(L.ptr(Fc), sx, sy, sz, n_steps, L.ptr(Fo), L.ptr(Fn), L.ptr(ws) if ws.numel() else None,
+                                  ws.numel(), L.stream_ptr()), "svf_integrate")
+    return Fo, Fn
+
+
+SURFACE_KEYS = ("Vlw", "Flw", "Vrw", "Frw", "Vlp", "Flp", "Vrp", "Frp")
+
+
+def load_surface_mesh(file_name):
+    """The eight arrays of a case's surface: an in-memory dict, or loadmat(file_name.split('.nii')[0] + '.mat')."""
+    if isinstance(file_name, dict):
+        mat = file_name
+    else:
+        try:
+            from scipy.io import loadmat
+        except ImportError as e:
+            raise L.BfmError("reading a surface mesh (.mat) needs scipy, which is not installed") from e
+        mat = loadmat(str(file_name).split(".nii")[0] + ".mat")
+    missing = [k for k in SURFACE_KEYS if k not in mat]
+    if missing:
+        raise L.BfmError("surface mesh lacks %s" % ", ".join(missing))
+    return mat
+
+
+def read_and_deform_surface(exist_keys, task_name, file_name, setups, deform_dict, device, mask, size):
+    """Generator/utils.py:479-531 (without its debug prints): every vertex set V goes through V -= c2,
+    V = V @ inverse(A).T, V += fast_3D_interp_torch(Fneg, V + c2), V += c2 in one launch for the four sets; with
+    setups['flip'] x is mirrored (size[0] - 1 - x) and left / right are swapped, vertices and faces.  inverse(A) is taken
+    in float64 and rounded to fp32, the matrix product is evaluated per vertex: vertices agree with the reference to
+    about 1e-5 voxels, not bitwise.  file_name: a path (its .mat sibling is read) or a dict of the eight arrays."""
+    Fneg, A, c2 = deform_dict["Fneg"], deform_dict["A"], deform_dict["c2"]
+    if Fneg is None:
+        raise L.BfmError("read_and_deform_surface needs the inverse field Fneg (the surface task with "
+                         "nonlinear_transform on)")
+    _require_cuda(Fneg, "read_and_deform_surface")
+    lib = L.load()
+    dev = Fneg.device
+    mat = load_surface_mesh(file_name)
+    out = {}
+    for k in SURFACE_KEYS:
+        if k[0] == "V":
+            v = torch.as_tensor(np.asarray(mat[k]), dtype=torch.float32).to(dev).contiguous()
+            if v.dim() != 2 or v.shape[1] != 3:
+                raise L.BfmError("surface %s must be (n, 3), got %s" % (k, tuple(v.shape)))
+            out[k] = v
+        else:
+            out[k] = torch.as_tensor(np.asarray(mat[k]), dtype=torch.int32).to(dev)
+    Fc = Fneg.to(torch.float32).contiguous()
+    sx, sy, sz = (int(v) for v in Fc.shape[:3])
+    A = A.detach().cpu().numpy() if isinstance(A, torch.Tensor) else np.asarray(A)
+    c2 = c2.detach().cpu().numpy() if isinstance(c2, torch.Tensor) else np.asarray(c2)
+    Ainv = np.linalg.inv(A.astype(np.float64)).astype(np.float32).reshape(-1)
+    names = ("Vlw", "Vrw", "Vlp", "Vrp")
+    sets = (L.VertexSet * L.VERTEX_SETS_MAX)(*[L.VertexSet(out[k].data_ptr() if out[k].numel() else None,
+                                                           out[k].shape[0]) for k in names])
+    L.check(lib.bfm_deform_vertices(L.ptr(Fc), sx, sy, sz, sets, len(names),
+                                    (C.c_float * 9)(*[float(v) for v in Ainv]),
+                                    (C.c_float * 3)(*[float(v) for v in np.asarray(c2, np.float32).reshape(-1)]),
+                                    int(bool(setups["flip"])), int(size[0]), L.stream_ptr()), "deform_vertices")
+    if setups["flip"]:
+        out["Vlw"], out["Vrw"] = out["Vrw"], out["Vlw"]
+        out["Vlp"], out["Vrp"] = out["Vrp"], out["Vlp"]
+        out["Flw"], out["Frw"] = out["Frw"], out["Flw"]
+        out["Flp"], out["Frp"] = out["Frp"], out["Flp"]
+    return out

@@ -638,6 +638,29 @@ int bfm_deform_zoom_write(const float* Fsmall, int fnx, int fny, int fnz, const 
                           const float* lo_host /*[3]*/, float* xx, float* yy, float* zz, float* F_out /*or NULL*/,
                           bfm_stream_t stream);
 
+/* The surface task.  BaseGen.random_nonlinear_transform with 'surface' in the tasks -- Generator/datasets.py:214-224:
+ *     s = 1 / 2**n; Fsvf = F * s; n times: Fsvf += fast_3D_interp_torch(Fsvf, xx + Fsvf[...,0], yy + Fsvf[...,1],
+ *     zz + Fsvf[...,2], 'linear'); the same from Fsvf_neg = -F * s.
+ * F, F_out, Fneg_out: [sx][sy][sz][3] fp32 (device, distinct).  One launch per step covers both directions; the first step
+ * reads F and applies +-s itself; each step reads one buffer and writes another (the interpolation is complete before the
+ * add), one scratch buffer per direction in the workspace (>= bfm_svf_integrate_workspace; none needed for n <= 1), and
+ * the start buffer is chosen by the parity of n so that the last step writes F_out / Fneg_out.  n_steps = 0: F * 1 and
+ * -F * 1.  Each voxel's arithmetic is fast_3D_interp_torch's in its order: bit-identical to the reference's CPU path. */
+size_t bfm_svf_integrate_workspace(int sx, int sy, int sz);
+int bfm_svf_integrate(const float* F, int sx, int sy, int sz, int n_steps, float* F_out, float* Fneg_out, void* workspace,
+                      size_t workspace_bytes, bfm_stream_t stream);
+/* read_and_deform_surface -- Generator/utils.py:479-531, the vertex arithmetic of up to BFM_VERTEX_SETS_MAX sets in one
+ * launch, in place on V [n][3] fp32 (device):  V -= c2; V = V @ Ainv.T; V += fast_3D_interp_torch(Fneg, V[:,0] + c2[0],
+ * V[:,1] + c2[1], V[:,2] + c2[2]) (0 where not ok); V += c2; flip: V[:,0] = size0 - 1 - V[:,0].  Fneg [sx][sy][sz][3]
+ * (device); Ainv_host = inverse(A), row-major [9], c2_host [3].  Faces are not touched (the host swaps left / right). */
+#define BFM_VERTEX_SETS_MAX 4
+typedef struct {
+    float* V;
+    int64_t n;
+} bfm_vertex_set_t;
+int bfm_deform_vertices(const float* Fneg, int sx, int sy, int sz, const bfm_vertex_set_t* sets, int n_sets,
+                        const float* Ainv_host, const float* c2_host, int flip, int size0, bfm_stream_t stream);
+
 /* read_and_deform and its callers (Generator/utils.py:296-322; _image :331-345, _distance :376-400,
  * _registration :462-473) for up to BFM_GATHER_MAX_JOBS volumes that share one coordinate field, straight from the
  * resident full volumes [nx][ny][nz]: box6 = {x1,y1,z1,x2,y2,z2} is the crop the reference takes (upper ends clipped
