@@ -12,8 +12,9 @@ Mirrors the reference's iteration -- Trainer/engine.py:96-147:
 
 with the criterion of Trainer/models/criterion.py (SetMultiCriterion: sum over the samples / all_samples) restricted to
 the supervised dense heads: T1 T2 FLAIR CT (+_grad, optional <key>_DM weights), SR(+_grad), distance, registration
-(+_grad), bias_field_log (l1 | l2, soft mask 1 - seg[:, 0]), seg_ce, seg_dice, and loss_age of the pooled scalar head
-(| abs(p) - age |, models.AgeHead).  Any other loss name raises.
+(+_grad, and the regularisers registration_smooth / registration_hessian of the raw head output), bias_field_log (l1 | l2,
+soft mask 1 - seg[:, 0]), seg_ce, seg_dice, and loss_age of the pooled scalar head (| abs(p) - age |, models.AgeHead).
+Any other loss name raises.  criterion_losses builds the loss names and weights from train_args as get_criterion does.
 
 Everything numeric runs in the HIP library; torch holds buffers, adds the per-sample gradients and runs the RCCL
 all-reduce.  There is no CPU path: without the extension or a HIP device construction fails.
@@ -32,8 +33,55 @@ from . import models as M
 
 IMAGE_KEYS = ("T1", "T2", "FLAIR", "CT")
 SUPPORTED = set(IMAGE_KEYS) | {k + "_grad" for k in IMAGE_KEYS} | {
-    "SR", "SR_grad", "distance", "surface", "registration", "registration_grad", "bias_field_log", "seg_ce", "seg_dice",
-    "pathol_ce", "pathol_dice", "age"}
+    "SR", "SR_grad", "distance", "surface", "registration", "registration_grad", "registration_smooth",
+    "registration_hessian", "bias_field_log", "seg_ce", "seg_dice", "pathol_ce", "pathol_dice", "age"}
+REG_REGULARISERS = ("registration_smooth", "registration_hessian")
+
+
+def criterion_losses(train_args, tasks, exclude_keys=()):
+    """(loss_names, weight_dict) as Trainer/models/__init__.py get_criterion builds them from the task names and
+    train_args.losses / train_args.weights, in the reference's order.  A switch missing from train_args.losses is off."""
+    lo, w = train_args.losses, train_args.weights
+    on = lambda k: bool(getattr(lo, k, False))                         # noqa: E731
+    names, wd = [], OrderedDict()
+    if "contrastive" in tasks:
+        return ["contrastive"], OrderedDict(loss_contrastive=w.contrastive)
+
+    def add(name, weight):
+        names.append(name)
+        wd["loss_" + name] = weight
+    for task in tasks:
+        if any(k in task for k in IMAGE_KEYS):
+            add(task, w.image)
+            if on("image_grad"):
+                add(task + "_grad", w.image_grad)
+        if "segmentation" in task:
+            add("seg_ce", w.seg_ce)
+            add("seg_dice", w.seg_dice)
+        if "bias_field" in task:
+            add("bias_field_log", w.bias_field_log)
+        if "super_resolution" in task:
+            add("SR", w.image)
+            if on("image_grad"):
+                add("SR_grad", w.image_grad)
+        if "distance" in task:
+            add("distance", w.distance)
+        if "registration" in task:
+            add("registration", w.registration)
+            for k in ("registration_grad",) + REG_REGULARISERS:
+                if on(k):
+                    add(k, getattr(w, k))
+        if "surface" in task:
+            add("surface", w.surface)
+        if "age" in task:
+            add("age", w.age)
+        if "pathology" in task and "pathology" not in exclude_keys:
+            add("pathol_ce", w.pathol_ce)
+            add("pathol_dice", w.pathol_dice)
+    if on("implicit_pathol"):
+        add("implicit_pathol_ce", w.implicit_pathol_ce)
+        add("implicit_pathol_dice", w.implicit_pathol_dice)
+    return names, wd
 
 
 class LossScaler:
@@ -288,6 +336,8 @@ class TrainStep:
             self.age = M.AgeHead(prm, age_head.c_feat, age_head.n_flat, self.dev)
         if "age" in self.loss_names and self.age is None:
             raise L.BfmError("loss 'age' needs the pooled scalar head (TrainStep(..., age_head=model.head.age_head()))")
+        if any(n in REG_REGULARISERS for n in self.loss_names) and "registration" not in tail.row_of:
+            raise L.BfmError("losses %s need the registration head" % [n for n in self.loss_names if n in REG_REGULARISERS])
 
     @property
     def _ws(self):
@@ -495,6 +545,17 @@ class TrainStep:
                         clampv = self.max_dist if head == "distance" else 0.0
                         slot(name)
                         dense.append((k - 1, co, tgt[j], None, None, clampv, 0, coef / nch))
+            elif name in REG_REGULARISERS:
+                # criterion.py:187-191: SmoothnessLoss('l2') / HessianLoss('l2') of the raw registration output (no processor,
+                # no target); value and coef * d/d(raw) in one launch pair, added into the registration rows of dRaw
+                r0, nch = self.tail.row_of["registration"]
+                active.update(range(r0, r0 + nch))
+                off, cs, vs = (r0 * raw.stride(0), raw.stride(0), 1) if rows else (r0, 1, n_out)
+                wsr = torch.empty(lib.bfm_loss_reg_workspace(nch, D, H, W), dtype=torch.uint8, device=self.dev)
+                keep.append(wsr)
+                fn = lib.bfm_loss_reg_smooth if name == "registration_smooth" else lib.bfm_loss_reg_hessian
+                L.check(fn(L.ptr(raw), off, cs, vs, nch, D, H, W, coef, L.ptr(dRaw), slot(name), L.ptr(wsr), wsr.numel(), st),
+                        "loss_" + name)
             elif name in ("pathol_ce", "pathol_dice"):
                 # criterion.py:193-212 on sigmoid(raw) (PatholProcessor): both names of a sample in ONE bfm_loss_pathol call,
                 # issued when the first of them comes up

@@ -824,6 +824,22 @@ size_t bfm_loss_pathol_workspace(void);
 int bfm_loss_pathol(const float* raw, int64_t col_offset, int64_t voxel_stride, const float* target, int64_t nvox,
                     float coef_ce, float coef_dice, float* dRaw, double* loss_ce, double* loss_dice, void* workspace,
                     size_t workspace_bytes, bfm_stream_t stream);
+/* Regularisers of the registration head (Trainer/models/losses.py:72-130 SmoothnessLoss('l2') / HessianLoss('l2'), as
+ * Trainer/models/criterion.py:187-191 applies them to the raw outputs['registration']).  Field u of nch channels over
+ * D x H x W; element (c, v) at raw[col_offset + c * chan_stride + v * voxel_stride] (channels-last: column, 1, n_out; rows:
+ * column * row_stride, row_stride, 1).  D_a = forward difference along x (W), y (H) or z (D), zero on the axis' last index.
+ *   smooth:  loss_out[0] = mean_{c,v} sum_a (D_a u)^2;  dRaw += coef * (2 / N) sum_a D_a^T D_a u  (N = nch D H W)
+ *   hessian: loss_out[0] = SUM_{c,v} det(H)^2, H_ab = D_a D_b u, det as losses.py:136;
+ *            dRaw += coef * sum_ab (D_a D_b)^T [2 det ddet/dH_ab]
+ * dRaw (same addressing) may be NULL: the value only.  Fixed-order fp64 reductions, no atomics (the same bits on every run).
+ * workspace >= bfm_loss_reg_workspace(nch, D, H, W), 8-byte aligned. */
+size_t bfm_loss_reg_workspace(int nch, int D, int H, int W);
+int bfm_loss_reg_smooth(const float* raw, int64_t col_offset, int64_t chan_stride, int64_t voxel_stride, int nch, int D, int H,
+                        int W, float coef, float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes,
+                        bfm_stream_t stream);
+int bfm_loss_reg_hessian(const float* raw, int64_t col_offset, int64_t chan_stride, int64_t voxel_stride, int nch, int D, int H,
+                         int W, float coef, float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes,
+                         bfm_stream_t stream);
 /* dW [n_out][C], db [n_out], dFn [nvox][C] from dRaw [nvox][n_out] and the normalised features Fn [nvox][C] */
 size_t bfm_head_bwd_workspace(int n_out, int C, int64_t nvox);
 int bfm_head_bwd(const float* dRaw, const float* Fn, const float* head_w, int n_out, int C, int64_t nvox, float* dW,
