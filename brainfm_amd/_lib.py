@@ -187,6 +187,8 @@ SIGNATURES = {
     "bfm_loss_reg_workspace": (_Z, [_I, _I, _I, _I]),
     "bfm_loss_reg_smooth": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),
     "bfm_loss_reg_hessian": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _F, _P, _P, _P, _Z, _P]),
+    "bfm_loss_contrastive_workspace": (_Z, []),
+    "bfm_loss_contrastive": (_I, [_P, _P, _I, _L, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "bfm_head_bwd_workspace": (_Z, [_I, _I, _L]),
     "bfm_head_bwd": (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _P, _P, _Z, _P]),
     "bfm_tail_raw_rows": (_I, [_P, _L, C.POINTER(TailDesc), _P, _P, _L, _P]),

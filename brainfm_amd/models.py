@@ -251,7 +251,7 @@ class UNet3D(nn.Module):
 
 
 def normalize_cl(eng, feat_cl, dims):
-    """F.normalize(dim=1) alone (tail kernel with no heads)."""
+    """F.normalize(dim=1) alone (tail kernel with no heads).  eng = None: no engine at hand, the library alone."""
     D, H, W = dims
     c = feat_cl.shape[-1]
     if c > 64 or c % 8:
@@ -261,8 +261,9 @@ def normalize_cl(eng, feat_cl, dims):
     desc = L.TailDesc(0, c, z.data_ptr(), z.data_ptr(), zi.data_ptr(), zi.data_ptr(), 0, 0, zi.data_ptr(), 0, 0, 0.0,
                       1, -1, -1, 0)
     out = torch.empty_like(feat_cl)
-    L.check(eng.lib.bfm_tail_heads(L.ptr(feat_cl), None, D * H * W, C.byref(desc), L.ptr(out), None, None, None, None,
-                                   L.stream_ptr()), "normalize")
+    lib = eng.lib if eng is not None else L.load()
+    L.check(lib.bfm_tail_heads(L.ptr(feat_cl), None, D * H * W, C.byref(desc), L.ptr(out), None, None, None, None,
+                               L.stream_ptr()), "normalize")
     return out
 
 
@@ -636,6 +637,93 @@ class UncertaintyProcessor(nn.Module):
         return outputs
 
 
+class ContrastiveProcessor(nn.Module):
+    """joiner.py:136-147: F.normalize(dim=1) of the last feature map of every sample (a second normalisation when the
+    backbone's unit_feat is on)."""
+
+    def __init__(self):
+        super().__init__()
+
+    @L.on_device(lambda self, outputs, *a, **k: outputs[0]["feat"][-1] if outputs else None)
+    def forward(self, outputs, *kwargs):
+        for output in outputs:
+            f = output["feat"][-1]
+            if f.device.type != "cuda":
+                raise L.BfmError("ContrastiveProcessor needs a HIP device; the product path has no CPU fallback")
+            per_b = []
+            for b in range(f.shape[0]):
+                cl = f[b].permute(1, 2, 3, 0).contiguous().to(torch.float32)
+                per_b.append(UNetEngine.as_ncdhw(normalize_cl(None, cl, tuple(f.shape[2:]))))
+            output["feat"][-1] = per_b[0] if len(per_b) == 1 else torch.cat(per_b, 0)
+        return outputs
+
+
+def loss_feat_contrastive(outputs, temperatures):
+    """criterion.py:96-109 in one bfm_loss_contrastive launch, forward only: outputs[0]['feat'][-1] and
+    outputs[1]['feat'][-1], (b, C, s, r, c), used as the processors left them; temperatures = (alpha, beta, gamma).
+    Returns {'loss_contrastive': 0-d float64 tensor on the device}."""
+    f1, f2 = outputs[0]["feat"][-1], outputs[1]["feat"][-1]
+    if f1.device.type != "cuda":
+        raise L.BfmError("loss_feat_contrastive needs a HIP device; the product path has no CPU fallback")
+    if tuple(f1.shape) != tuple(f2.shape):
+        raise L.BfmError("the two feature maps differ in shape: %s and %s" % (tuple(f1.shape), tuple(f2.shape)))
+    lib = L.load()
+    alpha, beta, gamma = (float(t) for t in temperatures)
+    c = f1.shape[1]
+    with torch.cuda.device(f1.device):
+        p = f1.permute(0, 2, 3, 4, 1).contiguous().to(torch.float32)
+        q = f2.permute(0, 2, 3, 4, 1).contiguous().to(torch.float32)
+        nvox = p.numel() // c
+        val = torch.zeros(1, dtype=torch.float64, device=f1.device)
+        ws = torch.empty(lib.bfm_loss_contrastive_workspace(), dtype=torch.uint8, device=f1.device)
+        L.check(lib.bfm_loss_contrastive(L.ptr(p), L.ptr(q), c, nvox, 0, 1e-12, alpha, beta, gamma, 1.0, None, None,
+                                         None, None, L.ptr(val), L.ptr(ws), ws.numel(), L.stream_ptr()),
+                "loss_contrastive")
+    return {"loss_contrastive": val[0]}
+
+
+class SetCriterion(nn.Module):
+    """criterion.py:15-325 limited to the one loss the head-less model has: criterion(outputs, targets, samples) ->
+    {'loss_contrastive': value}.  weight_dict / loss_names as get_criterion builds them (Trainer/models/__init__.py:169-178);
+    the temperatures are train_args.contrastive_temperatures.{alpha, beta, gamma} (criterion.py:45-48).  Forward only: the
+    gradients belong to train.ContrastiveStep."""
+
+    def __init__(self, gen_args, train_args, weight_dict, loss_names, device):
+        super().__init__()
+        if list(loss_names) != ["contrastive"]:
+            raise L.BfmError("this SetCriterion evaluates loss 'contrastive' alone (got %s); the dense losses run in "
+                             "train.TrainStep" % list(loss_names))
+        self.gen_args, self.train_args = gen_args, train_args
+        self.weight_dict = weight_dict
+        self.loss_names = list(loss_names)
+        t = train_args.contrastive_temperatures
+        self.temp_alpha, self.temp_beta, self.temp_gamma = t.alpha, t.beta, t.gamma
+
+    def loss_feat_contrastive(self, outputs, *kwargs):
+        return loss_feat_contrastive(outputs, (self.temp_alpha, self.temp_beta, self.temp_gamma))
+
+    def get_loss(self, loss_name, outputs, targets, *kwargs):
+        assert loss_name == "contrastive", "do you really want to compute %s loss?" % loss_name
+        return self.loss_feat_contrastive(outputs, targets, *kwargs)
+
+    def forward(self, outputs, targets, *kwargs):
+        losses = {}
+        for loss_name in self.loss_names:
+            losses.update(self.get_loss(loss_name, outputs, targets, *kwargs))
+        return losses
+
+
+def get_criterion(gen_args, train_args, tasks, device, exclude_keys=[]):
+    """Trainer/models/__init__.py:162-267 for the task the forward surface evaluates itself: 'contrastive' -> SetCriterion
+    when train_args carries what it reads (weights.contrastive, contrastive_temperatures); otherwise None, as for every
+    other task: the dense losses belong to train.TrainStep (train.criterion_losses gives their names and weights)."""
+    if "contrastive" in tasks and hasattr(train_args, "contrastive_temperatures") and \
+            hasattr(getattr(train_args, "weights", None), "contrastive"):
+        return SetCriterion(gen_args, train_args, OrderedDict(loss_contrastive=train_args.weights.contrastive),
+                            ["contrastive"], device)
+    return None
+
+
 def get_processors(gen_args, train_args, tasks, device, exclude_keys=[]):
     """joiner.py:238-256."""
     processors = []
@@ -643,6 +731,8 @@ def get_processors(gen_args, train_args, tasks, device, exclude_keys=[]):
         processors.append(UncertaintyProcessor(train_args.output_names))
     if getattr(train_args.losses, "implicit_pathol", False):
         raise NotImplementedError("PatholSeg (implicit_pathol) needs external checkpoints; outside the hot path")
+    if "contrastive" in tasks:
+        processors.append(ContrastiveProcessor())
     if "age" in tasks:
         processors.append(AgeProcessor())
     if "segmentation" in tasks and "segmentation" not in exclude_keys:
@@ -734,7 +824,8 @@ def get_joiner(task, backbone, head, device, postfix=""):
 
 def build_model(gen_args, train_args, device="cpu"):
     """Trainer/models/__init__.py:404-420.  criterion is None: losses belong to the training
-    step (SURVEY 'next' row N2), not to this path."""
+    step (SURVEY 'next' row N2), not to this path -- except for the head-less 'contrastive' task, whose one loss the
+    forward surface evaluates (get_criterion)."""
     gen_args, train_args = process_args(gen_args, train_args, task=gen_args.task)
     backbone = build_backbone(train_args, train_args.backbone)
     head = get_head(train_args, train_args.task_f_maps, train_args.out_channels, True, -1)
@@ -742,7 +833,7 @@ def build_model(gen_args, train_args, device="cpu"):
     head.max_surf_distance = float(gen_args.max_surf_distance)
     model = get_joiner(gen_args.tasks, backbone, head, device)
     processors = get_processors(gen_args, train_args, gen_args.tasks, device)
-    criterion = None
+    criterion = get_criterion(gen_args, train_args, gen_args.tasks, device)
     model.to(device)
     return gen_args, train_args, model, processors, criterion, get_postprocessor
 

@@ -15,6 +15,8 @@ the supervised dense heads: T1 T2 FLAIR CT (+_grad, optional <key>_DM weights), 
 (+_grad, and the regularisers registration_smooth / registration_hessian of the raw head output), bias_field_log (l1 | l2,
 soft mask 1 - seg[:, 0]), seg_ce, seg_dice, and loss_age of the pooled scalar head (| abs(p) - age |, models.AgeHead).
 Any other loss name raises.  criterion_losses builds the loss names and weights from train_args as get_criterion does.
+The head-less pre-training mode (task 'contrastive': SetCriterion with loss_feat_contrastive alone, criterion.py:96-109)
+is ContrastiveStep, which shares the parameter table, optimiser, scaler and checkpoint code with TrainStep.
 
 Everything numeric runs in the HIP library; torch holds buffers, adds the per-sample gradients and runs the RCCL
 all-reduce.  There is no CPU path: without the extension or a HIP device construction fails.
@@ -302,34 +304,21 @@ class TrainStep:
     def __init__(self, engine, tail, loss_names, loss_weights, weights_ce, all_samples, max_surf_distance=3.0,
                  bias_field_log_type="l2", lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, clip_max_norm=0.0,
                  scaler=None, age_head=None):
+        if "contrastive" in loss_names:
+            # the reference never mixes it with other losses (get_criterion returns early, Trainer/models/__init__.py:169-178)
+            raise L.BfmError("loss 'contrastive' is the head-less pre-training mode: use ContrastiveStep, not TrainStep")
         bad = [n for n in loss_names if n not in SUPPORTED]
         if bad:
             raise L.BfmError("losses outside the HIP training path: %s" % bad)
-        self.eng, self.tail = engine, tail
-        self.lib = engine.lib
-        self.dev = engine.device
-        self.loss_names = list(loss_names)
-        self.loss_weights = dict(loss_weights)
+        self.tail = tail
+        self._init_optim(engine, loss_names, loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler)
         self.all_samples = float(all_samples)
         self.max_dist = float(max_surf_distance)
         self.bias_l2 = 1 if bias_field_log_type == "l2" else 0
         self.wce = torch.as_tensor(weights_ce).to(device=self.dev, dtype=torch.float32).contiguous()
-        self.lr, self.wd, self.betas, self.eps, self.clip = float(lr), float(weight_decay), betas, float(eps), float(clip_max_norm)
-        self.scaler = scaler if scaler is not None else LossScaler(enabled=False)
-        self.t = 0                                          # iterations stepped so far
-        self.steps = {}                                     # per-parameter AdamW step counts (a head without an active
-                                                            # loss is not stepped: its .grad is None in the reference)
-        self._touched_heads = set()
-        self._active_rows = set()
-        self.state = {}                                   # name -> (m, v)
         nseg = tail.desc.n_seg
-        self.sample_lanes = max(1, int(os.environ.get("BFM_TRAIN_LANES", "2")))
-        self._lane_streams = []
-        self._lane = 0
-        self._ws_lane = {}
         self._ws_bytes = (self.lib.bfm_loss_workspace(max(nseg, 1)), self.lib.bfm_loss_l1_multi_workspace())
         # the pooled scalar head (models.AgeHead, e.g. TaskHead.age_head()): the step trains its own copy of the parameters
-        self.age = None
         if age_head is not None:
             prm = OrderedDict((k, v.detach().to(device=self.dev, dtype=torch.float32).clone().contiguous())
                               for k, v in age_head.params.items())
@@ -338,6 +327,27 @@ class TrainStep:
             raise L.BfmError("loss 'age' needs the pooled scalar head (TrainStep(..., age_head=model.head.age_head()))")
         if any(n in REG_REGULARISERS for n in self.loss_names) and "registration" not in tail.row_of:
             raise L.BfmError("losses %s need the registration head" % [n for n in self.loss_names if n in REG_REGULARISERS])
+
+    def _init_optim(self, engine, loss_names, loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler):
+        """What every kind of step holds: the engine, the loss table, the optimiser's and the scaler's state, the lanes."""
+        self.eng = engine
+        self.lib = engine.lib
+        self.dev = engine.device
+        self.loss_names = list(loss_names)
+        self.loss_weights = dict(loss_weights)
+        self.lr, self.wd, self.betas, self.eps, self.clip = float(lr), float(weight_decay), betas, float(eps), float(clip_max_norm)
+        self.scaler = scaler if scaler is not None else LossScaler(enabled=False)
+        self.t = 0                                          # iterations stepped so far
+        self.steps = {}                                     # per-parameter AdamW step counts (a head without an active
+                                                            # loss is not stepped: its .grad is None in the reference)
+        self._touched_heads = set()
+        self._active_rows = set()
+        self.state = {}                                   # name -> (m, v)
+        self.age = None
+        self.sample_lanes = max(1, int(os.environ.get("BFM_TRAIN_LANES", "2")))
+        self._lane_streams = []
+        self._lane = 0
+        self._ws_lane = {}
 
     @property
     def _ws(self):
@@ -986,3 +996,138 @@ class TrainStep:
                 grads.pop("head." + k_, None)
         stepped, _ = self.apply(grads, lr, weight_decay, grad_div=grad_div)
         return loss_dict, total, stepped
+
+
+class _NoHead:
+    """What TrainStep's shared code reads of a tail when the model has no head (process_args leaves out_channels empty
+    for task 'contrastive', Trainer/models/__init__.py:57)."""
+    row_of = {}
+    n_out = 0
+
+
+class ContrastiveStep(TrainStep):
+    """One iteration of the reference's feature pre-training (gen_args.task.contrastive): the backbone alone, trained with
+    loss_feat_contrastive (criterion.py:96-109) on the last feature maps of the FIRST TWO augmented samples after
+    ContrastiveProcessor (joiner.py:136-147).  The criterion is SetCriterion, not SetMultiCriterion: no loop over the
+    samples and no division by all_samples.  Parameters, apply / step, checkpoints and the scaler are TrainStep's; the
+    parameter table holds the backbone alone.
+
+    Samples after the second are not run.  The reference pushes every sample through the model (engine.py:114) and then
+    reads outputs[0] and outputs[1] only, so the others cost a forward pass and change neither the loss nor a gradient.
+
+    temperatures: (alpha, beta, gamma) = train_args.contrastive_temperatures.{alpha, beta, gamma} (criterion.py:45-48); no
+    shipped yaml sets them, so they are plain arguments here.
+
+    More than one rank is refused (BfmError): the gradient all-reduce of this step is not built."""
+
+    def __init__(self, engine, loss_weights, temperatures, lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8,
+                 clip_max_norm=0.0, scaler=None):
+        self.tail = _NoHead()
+        self._init_optim(engine, ["contrastive"], loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler)
+        self.alpha, self.beta, self.gamma = (float(t) for t in temperatures)
+        if not (self.alpha > 0 and self.beta > 0 and self.gamma > 0):
+            raise L.BfmError("contrastive temperatures must be positive, got %s" % (tuple(temperatures),))
+        cf = engine.fm[0]
+        if not 2 <= cf <= 64:
+            raise L.BfmError("the contrastive loss kernel takes 2..64 feature channels, the backbone has %d" % cf)
+        self.c_feat = cf
+        self.n_norm = (1 if engine.unit_feat else 0) + 1   # the backbone's unit_feat (unet3d/model.py:205-207) + the processor
+        self._ws_bytes = (max(self.lib.bfm_loss_contrastive_workspace(), self.lib.bfm_loss_workspace(1)),)   # + apply()'s sums
+
+    def grad_store(self):
+        raise L.BfmError("ContrastiveStep runs on one rank: it has no bucketed gradient all-reduce")
+
+    def _weights_changed(self):
+        self.eng.repack_all(refresh=BW.refresh_dgrad)
+
+    def _forward(self, x):
+        dims = tuple(x.shape[-3:])
+        feats, tape = BW.backbone_forward_train(self.eng, self.eng.to_cl(x), dims)
+        return feats, tape, dims
+
+    def _backward(self, feats, tape, dims, dfeat):
+        return BW.backbone_backward(self.eng, tape, [None] * (len(feats) - 1) + [dfeat.view(dims + (self.c_feat,))])
+
+    @L.on_device(lambda self, *a, **k: self.dev)
+    def loss_and_grads(self, xs, target=None, samples=None):
+        """xs: the augmented samples' inputs, (1,C,D,H,W) each, at least two; target / samples are not read (the loss has no
+        target).  Returns ({'loss_contrastive': v}, weight * v, grads) with grads = d(scale * weight * v)/d(parameter)
+        under the backbone's parameter names: sample 0's gradient + sample 1's, added on the caller's stream.
+        With sample_lanes > 1 (from the second iteration on, as TrainStep) the two forwards run on two streams, the loss
+        kernel on the caller's stream after both, and the two backward passes on the two streams again; every kernel sees
+        the same inputs as with one lane, so the result is the same bits."""
+        self.__dict__.pop("_store_next", None)
+        if len(xs) < 2:
+            raise L.BfmError("the contrastive loss compares two augmented samples; got %d" % len(xs))
+        if any(x.shape[0] != 1 for x in xs[:2]) or tuple(xs[0].shape) != tuple(xs[1].shape):
+            raise L.BfmError("ContrastiveStep takes two (1,C,D,H,W) inputs of one shape, got %s and %s"
+                             % (tuple(xs[0].shape), tuple(xs[1].shape)))
+        eng, lib = self.eng, self.lib
+        w = float(self.loss_weights.get("loss_contrastive", 0.0))
+        coef = self.scaler.scale * w
+        lanes = min(2, self.sample_lanes) if self.t >= 1 else 1
+        main = torch.cuda.current_stream(self.dev)
+        while len(self._lane_streams) < lanes:
+            self._lane_streams.append(torch.cuda.Stream(device=self.dev))
+
+        def on_lanes(fn):
+            """fn(i) for i = 0, 1: in turn on the caller's stream, or one per lane stream between two joins."""
+            if lanes <= 1:
+                return [fn(0), fn(1)]
+            start = torch.cuda.Event()
+            start.record(main)
+            seen = eng.pack_count
+            out, evs = [], []
+            for i in range(2):
+                st = self._lane_streams[i]
+                st.wait_event(start)
+                if eng.pack_count != seen:                 # a packed form was created lazily while issuing sample 0
+                    for e in evs:
+                        st.wait_event(e)
+                    seen = eng.pack_count
+                eng.lane, self._lane = i, i
+                try:
+                    with torch.cuda.stream(st):
+                        out.append(fn(i))
+                        ev = torch.cuda.Event()
+                        ev.record(st)
+                finally:
+                    eng.lane, self._lane = 0, 0
+                evs.append(ev)
+            for ev in evs:
+                main.wait_event(ev)
+            return out
+
+        def keep(t_):                                      # allocated on a lane, used on the caller's stream (or back)
+            if lanes > 1:
+                for st in [main] + self._lane_streams[:2]:
+                    t_.record_stream(st)
+            return t_
+
+        fwd = on_lanes(lambda i: self._forward(xs[i]))
+        dims = fwd[0][2]
+        nvox = dims[0] * dims[1] * dims[2]
+        f0, f1 = keep(fwd[0][0][-1][0]), keep(fwd[1][0][-1][0])
+        d0, d1 = keep(torch.empty_like(f0)), keep(torch.empty_like(f1))
+        val = torch.zeros(1, dtype=torch.float64, device=self.dev)
+        ws = self._lane_ws()[0]
+        L.check(lib.bfm_loss_contrastive(L.ptr(f0), L.ptr(f1), self.c_feat, nvox, self.n_norm, 1e-12, self.alpha, self.beta,
+                                         self.gamma, coef, L.ptr(d0), L.ptr(d1), None, None, L.ptr(val), L.ptr(ws),
+                                         ws.numel(), L.stream_ptr()), "loss_contrastive")
+        dfs = (d0, d1)
+        gs = on_lanes(lambda i: self._backward(fwd[i][0], fwd[i][1], dims, dfs[i]))
+        if lanes > 1:
+            for g in gs:
+                for t_ in g.values():
+                    t_.record_stream(main)
+        grads = OrderedDict((k_, gs[0][k_] + gs[1][k_]) for k_ in gs[0])
+        v = float(val.item())
+        return OrderedDict(loss_contrastive=v), w * v, grads
+
+    def step(self, xs, target=None, samples=None, lr=None, weight_decay=None, group=None):
+        """One full iteration (Trainer/engine.py:96-147) on one rank.  Returns (loss_dict, total, stepped)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            raise L.BfmError("ContrastiveStep runs on one rank: the gradient all-reduce of the contrastive step is not "
+                             "built (world size %d)" % dist.get_world_size(group))
+        return super().step(xs, target, samples, lr=lr, weight_decay=weight_decay, group=group)

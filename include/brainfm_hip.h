@@ -840,6 +840,23 @@ int bfm_loss_reg_smooth(const float* raw, int64_t col_offset, int64_t chan_strid
 int bfm_loss_reg_hessian(const float* raw, int64_t col_offset, int64_t chan_stride, int64_t voxel_stride, int nch, int D, int H,
                          int W, float coef, float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes,
                          bfm_stream_t stream);
+/* Trainer/models/criterion.py:96-109 loss_feat_contrastive on the feature maps Trainer/models/joiner.py:136-147
+ * ContrastiveProcessor leaves (the head-less pre-training mode, Trainer/models/__init__.py:57,169-178): featP / featQ are
+ * the RAW last decoder outputs of samples 0 and 1, channels-last [nvox][C] fp32, 2 <= C <= 64; p, q = F.normalize(., dim=1)
+ * applied n_norm times (0, 1 or 2: the backbone's unit_feat plus the processor give 2) with eps (1e-12).  Per voxel, with
+ * S = sum_j p_j:  num = sum_c exp(p_c q_c / alpha),  den = sum_i [exp(p_i^2 / beta) + exp((p_i S - p_i^2) / gamma)],
+ * loss_out[0] (device fp64) = mean_v log(den) - log(num).  Each voxel's largest exponent is subtracted before
+ * exponentiating, so the result stays finite where the reference's fp32 overflows and equals it where it does not.
+ * dP / dQ [nvox][C] (both or neither; written, not added) = coef * d loss / d featP, d featQ, through the n_norm
+ * normalisations; a row whose norm is <= eps is treated as bfm_normalize_bwd treats it: its gradient is the incoming one
+ * divided by eps (torch's autograd gives the same 1 / eps there).  coef = loss scale * weight; the loss value does not depend
+ * on it.  p_out / q_out [nvox][C] (either may be NULL) receive p and q.  C == 64 with 16-byte aligned maps takes the wide
+ * path (8 lanes per voxel, 16-byte accesses); other widths run one wave per voxel.  Fixed-order fp64 reduction, no atomics
+ * (the same bits on every run).  workspace >= bfm_loss_contrastive_workspace(), 8-byte aligned. */
+size_t bfm_loss_contrastive_workspace(void);
+int bfm_loss_contrastive(const float* featP, const float* featQ, int C, int64_t nvox, int n_norm, float eps, float alpha,
+                         float beta, float gamma, float coef, float* dP, float* dQ, float* p_out, float* q_out,
+                         double* loss_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
 /* dW [n_out][C], db [n_out], dFn [nvox][C] from dRaw [nvox][n_out] and the normalised features Fn [nvox][C] */
 size_t bfm_head_bwd_workspace(int n_out, int C, int64_t nvox);
 int bfm_head_bwd(const float* dRaw, const float* Fn, const float* head_w, int n_out, int C, int64_t nvox, float* dW,
