@@ -12,7 +12,7 @@ tensors handed back to callers are NCDHW *views* of those buffers
 """
 import ctypes as C
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -39,6 +39,25 @@ def nearest_index_map(n_in, n_out):
 
 
 _TUNE_CHOICES = {}          # (device, passes, shape key) -> conv variant that won UNetEngine._autotune in this process
+
+# The conv variants (cfg[6]): 0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino F(2,3), 4 conv_wino4 F(4,3).  Per variant
+# the packed-weight layout and its packer; for the two Winograd families also the entry points that exist once per family
+# with one C signature (_lib.SIGNATURES).  Names here; UNetEngine._variant binds them to the library once per engine.
+_Variant = namedtuple("_Variant", "layout pack_bytes pack rows box dense masked_workspace masked uniform_scratch uniform",
+                      defaults=(None,) * 7)
+_MFMA = _Variant("mfma", "bfm_pack_conv_weights_mfma_bytes", "bfm_pack_conv_weights_mfma")
+_CONV_VARIANTS = (
+    _MFMA,
+    _MFMA,
+    _Variant("mfma16", "bfm_pack_conv_weights_mfma16_bytes", "bfm_pack_conv_weights_mfma16"),
+    _Variant("wino", "bfm_pack_conv_weights_wino_bytes", "bfm_pack_conv_weights_wino", "bfm_conv3x3x3_wino_rows",
+             "bfm_conv3x3x3_wino_box", "bfm_conv3x3x3_wino_ex", "bfm_conv3x3x3_wino_masked_workspace",
+             "bfm_conv3x3x3_wino_masked", "bfm_conv3x3x3_wino_uniform_scratch", "bfm_conv3x3x3_wino_uniform"),
+    _Variant("wino4", "bfm_pack_conv_weights_wino4_bytes", "bfm_pack_conv_weights_wino4", "bfm_conv3x3x3_wino4_rows",
+             "bfm_conv3x3x3_wino4_box", "bfm_conv3x3x3_wino4", "bfm_conv3x3x3_wino4_masked_workspace",
+             "bfm_conv3x3x3_wino4_masked", "bfm_conv3x3x3_wino4_uniform_scratch", "bfm_conv3x3x3_wino4_uniform"),
+)
+_VARIANT_OF = {v.layout: ver for ver, v in enumerate(_CONV_VARIANTS)}      # packed-weight layout -> a variant that reads it
 
 # The persisted tune table: the variants agree to ~1e-6, not bit for bit, so a choice made by timing would let two
 # processes flip different argmax ties of the same volume.  brainfm_amd/conv_tune_gfx950.json (next to the .so, tracked)
@@ -135,6 +154,11 @@ class UNetEngine:
     weights_epoch = 0           # bumped when the weights change in place: captured graphs bake in the packing exponents
     pack_count = 0              # packed weight forms created so far (train.py: lazily created ones order the sample lanes)
     _ws_lanes = None
+    _variants = None            # _CONV_VARIANTS bound to self.lib (_variant)
+    _f23_ids = None             # caches made on first use: _needs_f23, _same_boxes, uniform_flags (one pass), _region_ok
+    _same_box_cache = None
+    _uf_cache = None
+    _deep_ok = None
     tape = None                 # training (backward.py): list that single_conv / maxpool append their records to
     grad_sink = None            # training (train.GradStore through train._Sink): where the backward kernels put gradients
     prof_reps = 1
@@ -227,30 +251,28 @@ class UNetEngine:
     def _mfma_ok(self, ly, ca, cb):
         return (not self.force_direct) and ca % 16 == 0 and cb % 16 == 0 and ly.cout % 64 == 0
 
+    def _variant(self, ver):
+        """_CONV_VARIANTS[ver] with the entry points as functions of self.lib (looked up once per engine).  A number
+        outside the table (a BFM_CONV_VER nobody defined) is conv_mfma, as the library's own launcher takes it."""
+        if self._variants is None:
+            self._variants = tuple(_Variant(v.layout, *[fn and getattr(self.lib, fn) for fn in v[1:]])
+                                   for v in _CONV_VARIANTS)
+        return self._variants[ver if 0 <= ver < len(self._variants) else 0]
+
     def _make_pack(self, ly, layout, wmax=None):
         """Create ly.packs[layout] from ly.w_raw (reusing the buffer of `prev` when repacking in place); wmax: max |w|
         when the caller already has it on the host (saves a device round trip per layer)."""
         st = L.stream_ptr()
         prev = ly.packs.get(layout)
         self.pack_count += 1
-        if layout in ("wino", "wino4"):
-            fn_b = self.lib.bfm_pack_conv_weights_wino_bytes if layout == "wino" else self.lib.bfm_pack_conv_weights_wino4_bytes
-            fn_p = self.lib.bfm_pack_conv_weights_wino if layout == "wino" else self.lib.bfm_pack_conv_weights_wino4
-            nbytes = fn_b(ly.cin, ly.cout, self.passes)
+        if layout in _VARIANT_OF:
+            v = self._variant(_VARIANT_OF[layout])
+            ps = (self.passes,) if v.dense is not None else ()     # the Winograd packers take the passes too
+            nbytes = v.pack_bytes(ly.cin, ly.cout, *ps)
             buf = prev[0] if prev is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             wexp = C.c_int(0)
             wmax = float(ly.w_raw.abs().max().item()) if wmax is None else wmax
-            L.check(fn_p(L.ptr(ly.w_raw), ly.cin, ly.cout, wmax, self.passes, L.ptr(buf), C.byref(wexp), st),
-                    "pack_%s %s" % (layout, ly.name))
-            ly.packs[layout] = (buf, wexp.value)
-        elif layout in ("mfma", "mfma16"):
-            v2 = layout == "mfma16"
-            fn_b = self.lib.bfm_pack_conv_weights_mfma16_bytes if v2 else self.lib.bfm_pack_conv_weights_mfma_bytes
-            fn_p = self.lib.bfm_pack_conv_weights_mfma16 if v2 else self.lib.bfm_pack_conv_weights_mfma
-            buf = prev[0] if prev is not None else torch.empty(fn_b(ly.cin, ly.cout), dtype=torch.uint8, device=self.device)
-            wexp = C.c_int(0)
-            wmax = float(ly.w_raw.abs().max().item()) if wmax is None else wmax
-            L.check(fn_p(L.ptr(ly.w_raw), ly.cin, ly.cout, wmax, L.ptr(buf), C.byref(wexp), st),
+            L.check(v.pack(L.ptr(ly.w_raw), ly.cin, ly.cout, wmax, *ps, L.ptr(buf), C.byref(wexp), st),
                     "pack_%s %s" % (layout, ly.name))
             ly.packs[layout] = (buf, wexp.value)
         elif layout == "direct":
@@ -265,7 +287,7 @@ class UNetEngine:
         """Pack (once per layout) and select the weights for this launch: 'direct' [27][Cin][Cout] fp32,
         'mfma' 32x32x16 fragments (plan variants 0/1), 'mfma16' 16x16x32 tap-pair fragments (variant 2),
         'wino' F(2,3)-along-x transformed fragments (variant 3, single-source layers only), 'wino4' F(4,3) (variant 4)."""
-        layout = "direct" if not mfma else ("wino4" if ver == 4 else "wino" if ver == 3 else ("mfma16" if ver == 2 else "mfma"))
+        layout = self._variant(ver).layout if mfma else "direct"
         if layout not in ly.packs:
             self._make_pack(ly, layout)
         ly.touch(layout)
@@ -390,7 +412,6 @@ class UNetEngine:
         """Pick the fastest conv variant (0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino, 4 conv_wino4) for this
         (Cin, Cout, dims, two-source) by timing them once on the real operands (HIP events on the launch stream).  All variants compute the same result; the chip is
         power-limited on this kernel, so which one wins is shape dependent (profiles/).  BFM_CONV_VER pins one."""
-        import os
         cfg = self._plan_cache[key]
         if key in self._tuned or os.environ.get("BFM_CONV_VER") or os.environ.get("BFM_CONV_TUNE", "1") == "0":
             return cfg
@@ -522,24 +543,22 @@ class UNetEngine:
     def _conv_launch(self, ly, A, ca, B, cb, dims, upp, scale, shift, bound, groups, cfg, out, ws, rows=None, slope=None,
                      mask_img=None, uni_flags=None, pool=None):
         """One launch of the planned variant of GN-apply + conv + LeakyReLU (cfg[6]: 0/1/2 conv_mfma family,
-        3 Winograd; cfg[7] bit 0: accumulate onto `out`).  mask_img (variant 3 only): the tile's input image; boxes of
-        output voxels where it is all zero are left uncomputed (bfm_conv3x3x3_wino_masked).  uni_flags (variant 3, one
-        source): per-box flags of bfm_uniform_boxes -> bfm_conv3x3x3_wino_uniform."""
+        3 / 4 Winograd F(2,3) / F(4,3); cfg[7] bit 0: accumulate onto `out`).  mask_img (variants 3 and 4 only): the tile's
+        input image; boxes of output voxels where it is all zero are left uncomputed (the family's _masked entry point).
+        uni_flags (variants 3 and 4, one source): per-box flags of bfm_uniform_boxes -> the family's _uniform entry point."""
         D, H, W = dims
         st = L.stream_ptr()
         slope = self.slope if slope is None else float(slope)
         self._pack(ly, True, cfg[6])
+        v = self._variant(cfg[6])
         if mask_img is not None:
-            if cfg[6] not in (3, 4) or cb or rows is not None:
+            if v.masked is None or cb or rows is not None:
                 raise L.BfmError("a masked launch is a one-source Winograd kernel without moment rows")
-            nws = (self.lib.bfm_conv3x3x3_wino_masked_workspace if cfg[6] == 3
-                   else self.lib.bfm_conv3x3x3_wino4_masked_workspace)(D, H, W, self.passes)
+            nws = v.masked_workspace(D, H, W, self.passes)
             mws = torch.empty(nws, dtype=torch.uint8, device=self.device)       # box activity, count, list of boxes
-            fn = self.lib.bfm_conv3x3x3_wino_masked if cfg[6] == 3 else self.lib.bfm_conv3x3x3_wino4_masked
-            L.check(fn(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound),
-                                                       groups, L.ptr(ly.wpacked), ly.wexp, ly.cout, slope, self.passes,
-                                                       cfg[7] & 1, L.ptr(out), L.ptr(mask_img), L.ptr(mws), nws, st),
-                    "conv_wino(masked) " + ly.name)
+            L.check(v.masked(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked),
+                             ly.wexp, ly.cout, slope, self.passes, cfg[7] & 1, L.ptr(out), L.ptr(mask_img), L.ptr(mws), nws,
+                             st), "conv_wino(masked) " + ly.name)
             return
         if pool is not None:
             # (pooled tensor, its moment rows): the F(2,3) kernel writes MaxPool3d(2) of its output too (single_conv(pool=True))
@@ -562,34 +581,20 @@ class UNetEngine:
             return
         if uni_flags is not None and cfg[6] == 4 and not self._same_boxes(dims):
             uni_flags = None                                # the flags are per box of conv_wino's grid: dense launch, same bits
-        if uni_flags is not None and cfg[6] in (3, 4) and not cb:
-            f4 = cfg[6] == 4
-            scratch = torch.empty((self.lib.bfm_conv3x3x3_wino4_uniform_scratch if f4
-                                   else self.lib.bfm_conv3x3x3_wino_uniform_scratch)(ly.cout), dtype=torch.uint8,
-                                  device=self.device)
-            fn = self.lib.bfm_conv3x3x3_wino4_uniform if f4 else self.lib.bfm_conv3x3x3_wino_uniform
-            L.check(fn(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound),
-                                                        groups, L.ptr(ly.wpacked), ly.wexp, ly.cout, slope, self.passes,
-                                                        cfg[7] & 1, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
-                                                        L.ptr(uni_flags), L.ptr(scratch), st),
+        if uni_flags is not None and v.uniform is not None and not cb:
+            scratch = torch.empty(v.uniform_scratch(ly.cout), dtype=torch.uint8, device=self.device)
+            L.check(v.uniform(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked),
+                              ly.wexp, ly.cout, slope, self.passes, cfg[7] & 1, L.ptr(out),
+                              L.ptr(rows[0]) if rows is not None else None, L.ptr(uni_flags), L.ptr(scratch), st),
                     "conv_wino(uniform) " + ly.name)
             return
-        if cfg[6] == 4:
+        if v.dense is not None:
             if cb:
-                raise L.BfmError("the Winograd variants take one source")
-            L.check(self.lib.bfm_conv3x3x3_wino4(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups,
-                                                 L.ptr(ly.wpacked), ly.wexp, ly.cout, slope, self.passes, (cfg[7] & 1),
-                                                 L.ptr(out), L.ptr(rows[0]) if rows is not None else None, st),
-                    "conv_wino4 " + ly.name)
-            return
-        if cfg[6] == 3:
-            if cb:
-                raise L.BfmError("the Winograd variant takes one source")
-            L.check(self.lib.bfm_conv3x3x3_wino_ex(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound),
-                                                   groups, L.ptr(ly.wpacked), ly.wexp, ly.cout, slope, self.passes,
-                                                   (cfg[7] & 1), L.ptr(out),
-                                                   L.ptr(rows[0]) if rows is not None else None, st),
-                    "conv_wino " + ly.name)
+                raise L.BfmError("the Winograd variant takes one source" if cfg[6] == 3 else
+                                 "the Winograd variants take one source")
+            L.check(v.dense(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked),
+                            ly.wexp, ly.cout, slope, self.passes, cfg[7] & 1, L.ptr(out),
+                            L.ptr(rows[0]) if rows is not None else None, st), "conv_%s %s" % (v.layout, ly.name))
             return
         L.check(self.lib.bfm_conv3x3x3_mfma_ex(L.ptr(A), ca, L.ptr(B) if cb else None, cb, D, H, W, upp if cb else None,
                                                L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked),
@@ -606,23 +611,19 @@ class UNetEngine:
         uniform-box layer: a box is a whole number of quads, its sums depend on its mathematical halo only, so they may run
         F(4,3) with the same flags (bfm_conv3x3x3_wino4_uniform, round 5).  A layer must compute the same bits with the
         shortcut on and off, so the rule goes by position in the network, never by the state of a switch."""
-        ids = self.__dict__.get("_f23_ids")
-        if ids is None:
-            ids = set()
-            for i, j in ((0, 1), (1, 0), (1, 1)):
-                if i < len(self.enc):
-                    ids.add(id(self.enc[i][j]))
-            self.__dict__["_f23_ids"] = ids
-        return id(ly) in ids
+        if self._f23_ids is None:
+            self._f23_ids = {id(self.enc[i][j]) for i, j in ((0, 1), (1, 0), (1, 1)) if i < len(self.enc)}
+        return id(ly) in self._f23_ids
 
     def _same_boxes(self, dims):
         """conv_wino4's box for this volume is conv_wino's (the grid bfm_uniform_boxes flags)."""
-        cache = self.__dict__.setdefault("_same_box_cache", {})
-        key = tuple(dims)
+        if self._same_box_cache is None:
+            self._same_box_cache = {}
+        cache, key = self._same_box_cache, tuple(dims)
         if key not in cache:
             b3, b4 = (C.c_int * 3)(), (C.c_int * 3)()
-            ok = (self.lib.bfm_conv3x3x3_wino_box(dims[0], dims[1], dims[2], self.passes, b3) == 0 and
-                  self.lib.bfm_conv3x3x3_wino4_box(dims[0], dims[1], dims[2], self.passes, b4) == 0)
+            ok = (self._variant(3).box(dims[0], dims[1], dims[2], self.passes, b3) == 0 and
+                  self._variant(4).box(dims[0], dims[1], dims[2], self.passes, b4) == 0)
             cache[key] = ok and list(b3) == list(b4)
         return cache[key]
 
@@ -635,20 +636,45 @@ class UNetEngine:
             cfg[6] = 3
         return cfg
 
-    def _rows_for(self, cin, cout, dims, cfg):
+    def _rows_for(self, cin, cout, dims, cfg, S=1):
         """(buffer, nrows) for the producer's output-moment rows, or None when this plan cannot emit them."""
+        v = self._variant(cfg[6])
+        if v.rows is not None:
+            return self._rows_buf(cout, S, v.rows, dims[0], dims[1], dims[2], self.passes)
+        return self._rows_buf(cout, S, self.lib.bfm_conv3x3x3_mfma_rows, cin, cout, dims[0], dims[1], dims[2], cfg)
+
+    def _rows_buf(self, cout, S, rows_fn, *args):
+        """(buffer, n) for the moment rows a producer writes beside its output -- n = rows_fn(*args) rows of cout channels
+        per sample, S samples -- or None (BFM_FUSE_STATS=0: rows_fn is not asked; or no rows for this shape)."""
         if not self.fuse_stats:
             return None
-        if cfg[6] == 4:
-            n = self.lib.bfm_conv3x3x3_wino4_rows(dims[0], dims[1], dims[2], self.passes)
-        elif cfg[6] == 3:
-            n = self.lib.bfm_conv3x3x3_wino_rows(dims[0], dims[1], dims[2], self.passes)
-        else:
-            n = self.lib.bfm_conv3x3x3_mfma_rows(cin, cout, dims[0], dims[1], dims[2], cfg)
+        n = rows_fn(*args)
         if n <= 0:
             return None
-        buf = torch.empty(self.lib.bfm_moment_rows_bytes(n, cout), dtype=torch.uint8, device=self.device)
-        return (buf, n)
+        return (torch.empty(self.lib.bfm_moment_rows_bytes(S * n, cout), dtype=torch.uint8, device=self.device), n)
+
+    @staticmethod
+    def _tag(ly):
+        """The layer's name in the records of the instrumented pass."""
+        return ly.name.replace("backbone.", "").replace(".basic_module.SingleConv", ".")
+
+    def _bracket(self, launch, record):
+        """Issue one conv launch.  In the instrumented pass (bench.py: self.prof is a list) the launch is issued prof_reps
+        times back to back inside one HIP event pair, so the bracket holds kernel time, not host submission gaps (the
+        result is idempotent except for the accumulating halves of the up-folded layers, "sk" and "x%dsk": their output is
+        that of a plain pass with prof_reps == 1 only); record() -> (flops, bytes, tag, cin, cout, dims, cfg) is asked for after the closing event only
+        (counting the voxels of a masked or uniform launch synchronises)."""
+        if self.prof is None:
+            launch()
+            return
+        reps = max(1, int(self.prof_reps))
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        for _ in range(reps):
+            launch()
+        ev[1].record()
+        flops, nbytes, tag, cin, cout, dims, cfg = record()
+        self.prof.append((ev[0], ev[1], flops, nbytes, reps, (tag, cin, cout, tuple(dims), tuple(cfg))))
 
     # ------------------------------------------------------------------ one SingleConv
     def single_conv(self, ly, A, dims, B=None, lo_dims=None, mask_img=None, uni_flags=None, pool=False):
@@ -683,8 +709,6 @@ class UNetEngine:
             cfg = self._f23_cfg(ly, self._autotune(ly, (ly.cin, ly.cout, tuple(dims), B is not None, False), _launch))
         self._pack(ly, mfma, cfg[6] if cfg is not None else 0)
         if mfma:
-            ev = None
-            reps = 1
             if mask_img is not None and not (cfg[6] in (3, 4) and B is None and self.tape is None):
                 mask_img = None
             if uni_flags is not None and not (cfg[6] in (3, 4) and B is None and mask_img is None):
@@ -696,45 +720,28 @@ class UNetEngine:
             if (pool and cfg[6] == 3 and B is None and mask_img is None and self.tape is None and self.fuse_pool
                     and min(dims) >= 2 and self.lib.bfm_conv3x3x3_wino_pool_ok(D, H, W, self.passes)):
                 pooled = torch.empty((D // 2, H // 2, W // 2, ly.cout), dtype=torch.float32, device=self.device)
-                prow = None
-                if self.fuse_stats:
-                    n = self.lib.bfm_conv3x3x3_wino_rows(D, H, W, self.passes)
-                    prow = (torch.empty(self.lib.bfm_moment_rows_bytes(n, ly.cout), dtype=torch.uint8, device=self.device), n)
-                pl = (pooled, prow)
-            if self.prof is not None:
-                # instrumented pass (bench.py): the launch is issued prof_reps times back to back inside one HIP
-                # event pair (the result is idempotent), so the bracket holds kernel time, not host submission gaps
-                reps = max(1, int(self.prof_reps))
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-            for _ in range(reps):
-                self._conv_launch(ly, A, ca, B, cb, dims, upp, scale, shift, bound, ly.groups, cfg, out, ws, rows,
-                                  mask_img=mask_img, uni_flags=uni_flags, pool=pl)
-            if rows is not None:
-                out._bfm_rows = rows
-            if pl is not None:
-                if pl[1] is not None:
-                    pl[0]._bfm_rows = pl[1]
-                out._bfm_pooled = (pl[0], (D // 2, H // 2, W // 2))
-            if ev is not None:
-                ev[1].record()
+                pl = (pooled, self._rows_buf(ly.cout, 1, self.lib.bfm_conv3x3x3_wino_rows, D, H, W, self.passes))
+
+            def _record():
                 nv = D * H * W
                 if mask_img is not None:                    # only the boxes the kernel computes count as work
                     nv = self.masked_voxels(mask_img, dims, cfg[6])
                 if uni_flags is not None:                   # a uniform box runs a quarter of its products
                     nv = self.uniform_voxels(uni_flags, dims)
                 lo = 0 if B is None else lo_dims[0] * lo_dims[1] * lo_dims[2]
-                self.prof.append((ev[0], ev[1], 2.0 * 27 * ly.cin * ly.cout * nv,
-                                  4.0 * (nv * ca + lo * cb + nv * ly.cout + 27 * ly.cin * ly.cout), reps,
-                                  (ly.name.replace("backbone.", "").replace(".basic_module.SingleConv", ".")
-                                   + ("[masked]" if mask_img is not None else "[uniform]" if uni_flags is not None else ""),
-                                   ly.cin, ly.cout, tuple(dims), tuple(cfg))))
+                return (2.0 * 27 * ly.cin * ly.cout * nv, 4.0 * (nv * ca + lo * cb + nv * ly.cout + 27 * ly.cin * ly.cout),
+                        self._tag(ly) + ("[masked]" if mask_img is not None else "[uniform]" if uni_flags is not None else ""),
+                        ly.cin, ly.cout, dims, cfg)
+            self._bracket(lambda: self._conv_launch(ly, A, ca, B, cb, dims, upp, scale, shift, bound, ly.groups, cfg, out, ws,
+                                                    rows, mask_img=mask_img, uni_flags=uni_flags, pool=pl), _record)
+            if rows is not None:
+                out._bfm_rows = rows
+            if pl is not None:
+                if pl[1] is not None:
+                    pl[0]._bfm_rows = pl[1]
+                out._bfm_pooled = (pl[0], (D // 2, H // 2, W // 2))
         elif ca == 1 and cb == 0 and ly.cout in (32, 64) and not self.force_direct:
-            rows = None
-            if self.fuse_stats:
-                n = self.lib.bfm_conv3x3x3_stem_rows(D, H, W)
-                rows = (torch.empty(self.lib.bfm_moment_rows_bytes(n, ly.cout), dtype=torch.uint8,
-                                    device=self.device), n)
+            rows = self._rows_buf(ly.cout, 1, self.lib.bfm_conv3x3x3_stem_rows, D, H, W)
             L.check(self.lib.bfm_conv3x3x3_stem_ex(L.ptr(A), D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound),
                                                    L.ptr(ly.wpacked), ly.cout, self.slope, L.ptr(out),
                                                    L.ptr(rows[0]) if rows is not None else None, st),
@@ -762,8 +769,7 @@ class UNetEngine:
             if os.environ.get("BFM_CONV_VER"):
                 ver = int(os.environ["BFM_CONV_VER"])
         box = (C.c_int * 3)()
-        L.check((self.lib.bfm_conv3x3x3_wino4_box if ver == 4 else self.lib.bfm_conv3x3x3_wino_box)(D, H, W, self.passes, box),
-                "wino_box")
+        L.check(self._variant(4 if ver == 4 else 3).box(D, H, W, self.passes, box), "wino_box")
         td, th, tw = box[0], box[1], box[2]
         m = (mask_img.reshape(D, H, W) != 0)
         m = torch.nn.functional.pad(m, (0, -W % tw, 0, -H % th, 0, -D % td))
@@ -783,7 +789,9 @@ class UNetEngine:
         # (a box constant within 3 voxels is constant within 2) and flags 1 % fewer boxes than each layer's own radius
         radius = max([radius] + [r for k, r in self.UNIFORM_RADIUS.items() if k[1] == level])
         ckey = (x_cl.data_ptr(), tuple(dims), int(level), int(radius), torch.cuda.current_stream(self.device).cuda_stream)
-        cache = self.__dict__.setdefault("_uf_cache", {})
+        if self._uf_cache is None:
+            self._uf_cache = {}
+        cache = self._uf_cache
         if ckey in cache:
             return cache[ckey]
         D, H, W = dims
@@ -854,36 +862,24 @@ class UNetEngine:
         sc_b, sh_b = scale[ca:], shift[ca:]
         nv = D * H * W
         lo = lo_dims[0] * lo_dims[1] * lo_dims[2]
-        tag = ly.name.replace("backbone.", "").replace(".basic_module.SingleConv", ".")
-        reps = max(1, int(self.prof_reps)) if self.prof is not None else 1
-        ev = None
-        if self.prof is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        for _ in range(reps):
+
+        def _launch_up():
             L.check(self.lib.bfm_conv3x3x3_upfold_ex(L.ptr(B), cb, lo_dims[0], lo_dims[1], lo_dims[2], L.ptr(sc_b),
                                                      L.ptr(sh_b), L.ptr(bound), ly.groups, L.ptr(wup), wexp_up, ly.cout,
                                                      self.passes, L.ptr(out), L.ptr(ws) if wsu else None, ws.numel(), st),
                     "conv_upfold " + ly.name)
-        if ev is not None:
-            ev[1].record()
-            self.prof.append((ev[0], ev[1], 2.0 * 27 * cb * ly.cout * nv, 4.0 * (lo * cb + nv * ly.cout), reps,
-                              (tag + "up", cb, ly.cout, tuple(dims), (0,) * 8)))
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
+        self._bracket(_launch_up, lambda: (2.0 * 27 * cb * ly.cout * nv, 4.0 * (lo * cb + nv * ly.cout),
+                                           self._tag(ly) + "up", cb, ly.cout, dims, (0,) * 8))
         rows = self._rows_for(ca, ly.cout, dims, cfg)
         if uni_flags is not None and (cfg[6] not in (3, 4) or (cfg[6] == 4 and not self._same_boxes(dims))):
             uni_flags = None
-        for _ in range(reps):
-            self._conv_launch(sk, A, ca, None, 0, dims, None, scale, shift, bound, ly.groups, cfg, out, ws, rows,
-                              uni_flags=uni_flags)
+        self._bracket(lambda: self._conv_launch(sk, A, ca, None, 0, dims, None, scale, shift, bound, ly.groups, cfg, out, ws,
+                                                rows, uni_flags=uni_flags),
+                      lambda: (2.0 * 27 * ca * ly.cout * (nv if uni_flags is None else self.uniform_voxels(uni_flags, dims)),
+                               4.0 * (nv * ca + 2 * nv * ly.cout),
+                               self._tag(ly) + ("sk[uniform]" if uni_flags is not None else "sk"), ca, ly.cout, dims, cfg))
         if rows is not None:
             out._bfm_rows = rows
-        if ev is not None:
-            ev[1].record()
-            nve = nv if uni_flags is None else self.uniform_voxels(uni_flags, dims)
-            self.prof.append((ev[0], ev[1], 2.0 * 27 * ca * ly.cout * nve, 4.0 * (nv * ca + 2 * nv * ly.cout), reps,
-                              (tag + ("sk[uniform]" if uni_flags is not None else "sk"), ca, ly.cout, tuple(dims), tuple(cfg))))
         self._record(ly, A, B, dims, lo_dims, scale, shift, bound, out)
         return out
 
@@ -895,11 +891,7 @@ class UNetEngine:
             return fused                                     # written by the producing conv's epilogue (single_conv(pool=True))
         if out is None:
             out = torch.empty((D // 2, H // 2, W // 2, c), dtype=torch.float32, device=self.device)
-        rows = None
-        if self.fuse_stats:
-            n = self.lib.bfm_maxpool2_rows(c, D, H, W)
-            if n > 0:
-                rows = (torch.empty(self.lib.bfm_moment_rows_bytes(n, c), dtype=torch.uint8, device=self.device), n)
+        rows = self._rows_buf(c, 1, self.lib.bfm_maxpool2_rows, c, D, H, W)
         L.check(self.lib.bfm_maxpool2_ex(L.ptr(X), c, D, H, W, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
                                          L.stream_ptr()), "maxpool2")
         if rows is not None:
@@ -916,18 +908,13 @@ class UNetEngine:
             for s_ in range(S):
                 self.maxpool(X[s_], dims, out=out[s_])
             return out
-        rows = None
-        if self.fuse_stats:
-            n = self.lib.bfm_maxpool2_batch_rows(c, D, H, W)
-            if n > 0:
-                rows = (torch.empty(self.lib.bfm_moment_rows_bytes(S * n, c), dtype=torch.uint8, device=self.device), n)
+        rows = self._rows_buf(c, S, self.lib.bfm_maxpool2_batch_rows, c, D, H, W)
         L.check(self.lib.bfm_maxpool2_batch(L.ptr(X), c, S, D, H, W, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
                                             L.stream_ptr()), "maxpool2_batch")
         if rows is not None:
             out._bfm_rows = rows
         return out
 
-    # ------------------------------------------------------------------ backbone
     # ------------------------------------------------------------------ the deep levels, batched over samples
     # Levels >= deep_from (20^3 voxels and fewer on a 160^3 tile) are bound by their weights: 253 M of the 264 M
     # parameters = 1 GB of packed fragments that every tile re-reads for a few thousand voxels.  Tiles of one shape
@@ -959,7 +946,9 @@ class UNetEngine:
     deep_vox = int(os.environ.get("BFM_DEEP_VOX", "16000"))
 
     def _region_ok(self, df):
-        cache = self.__dict__.setdefault("_deep_ok", {})
+        if self._deep_ok is None:
+            self._deep_ok = {}
+        cache = self._deep_ok
         if df not in cache:                                  # every layer of the region must be a matrix-core layer
             ndeep = len(self.enc) - 1 - df
             layers = [ly for pair in self.enc[df:] + self.dec[:ndeep] for ly in pair]
@@ -1026,62 +1015,59 @@ class UNetEngine:
             return self._batch_conv_upfold(ly, A, dims, B, lo_dims, scale, shift, bound)
         key = (ly.cin, ly.cout, tuple(dims), B is not None, False, 1)       # trailing 1: a layer of the batched levels
         vers = self.DEEP_VERS if B is not None else self.DEEP_VERS_1SRC
-        if key not in self._plan_cache:
-            cfg = (C.c_int * 8)()
-            L.check(self.lib.bfm_conv3x3x3_mfma_plan(ly.cin, ly.cout, D, H, W, cfg), "mfma_plan")
-            if cfg[6] not in vers:
-                cfg[6] = 0
-            self._plan_cache[key] = cfg
-        cfg = self._plan_cache[key]
+        cfg = self._batch_plan(key, vers)
         out = torch.empty((S, D, H, W, ly.cout), dtype=torch.float32, device=self.device)
-        st = L.stream_ptr()
-
-        def _launch(c, rows=None, A_=A, B_=B, S_=S, out_=out, sc=scale, sh=shift, bd=bound):
-            self._pack(ly, True, c[6])
-            if c[6] == 4:
-                L.check(self.lib.bfm_conv3x3x3_wino4_batch(L.ptr(A_), ca, S_, D, H, W, L.ptr(sc), L.ptr(sh), L.ptr(bd), ly.groups,
-                                                           L.ptr(ly.wpacked), ly.wexp, ly.cout, self.slope, self.passes, 0,
-                                                           L.ptr(out_), L.ptr(rows[0]) if rows is not None else None, 0, st),
-                        "conv_wino4_batch " + ly.name)
-                return
-            wsb = self.lib.bfm_conv3x3x3_mfma_batch_workspace(ly.cin, ly.cout, S_, D, H, W, c[5])
-            ws = self._workspace(wsb)
-            L.check(self.lib.bfm_conv3x3x3_mfma_batch(L.ptr(A_), ca, L.ptr(B_) if cb else None, cb, S_, D, H, W,
-                                                      upp if cb else None, L.ptr(sc), L.ptr(sh), L.ptr(bd), ly.groups,
-                                                      L.ptr(ly.wpacked), ly.wexp, ly.cout, self.slope, self.passes, c,
-                                                      L.ptr(out_), L.ptr(ws), ws.numel(),
-                                                      L.ptr(rows[0]) if rows is not None else None, 0, st),
-                    "conv_mfma_batch " + ly.name)
         if key not in self._tuned:
             # timed on ONE sample (the choice must not depend on the batch size: a tile's bits may not either)
-            cfg = self._autotune(ly, key, lambda c: _launch(c, None, A[0:1], B[0:1] if B is not None else None, 1, out[0:1],
-                                                            scale[0:1], shift[0:1], bound[0:1]), vers=vers)
+            cfg = self._autotune(ly, key, lambda c: self._batch_launch(ly, c, A[0:1], B[0:1] if B is not None else None, upp, dims,
+                                                                       scale[0:1], shift[0:1], bound[0:1], out[0:1]),
+                                 vers=vers)
         self._pack(ly, True, cfg[6])
-        rows = None
-        if self.fuse_stats:
-            n = (self.lib.bfm_conv3x3x3_wino4_rows(D, H, W, self.passes) if cfg[6] == 4 else
-                 self.lib.bfm_conv3x3x3_mfma_rows(ly.cin, ly.cout, D, H, W, cfg))
-            if n > 0:
-                rows = (torch.empty(self.lib.bfm_moment_rows_bytes(S * n, ly.cout), dtype=torch.uint8, device=self.device), n)
-        ev = None
-        reps = 1
-        if self.prof is not None:
-            reps = max(1, int(self.prof_reps))
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        for _ in range(reps):
-            _launch(cfg, rows)
-        if ev is not None:
-            ev[1].record()
-            nv = D * H * W
-            lo = 0 if B is None else lo_dims[0] * lo_dims[1] * lo_dims[2]
-            self.prof.append((ev[0], ev[1], 2.0 * 27 * ly.cin * ly.cout * nv * S,
-                              4.0 * (S * (nv * ca + lo * cb + nv * ly.cout) + 27 * ly.cin * ly.cout), reps,
-                              (ly.name.replace("backbone.", "").replace(".basic_module.SingleConv", ".") + ("x%d" % S),
-                               ly.cin, ly.cout, tuple(dims), tuple(cfg))))
+        rows = self._rows_for(ly.cin, ly.cout, dims, cfg, S)
+        nv = D * H * W
+        lo = 0 if B is None else lo_dims[0] * lo_dims[1] * lo_dims[2]
+        self._bracket(lambda: self._batch_launch(ly, cfg, A, B, upp, dims, scale, shift, bound, out, rows),
+                      lambda: (2.0 * 27 * ly.cin * ly.cout * nv * S,
+                               4.0 * (S * (nv * ca + lo * cb + nv * ly.cout) + 27 * ly.cin * ly.cout),
+                               self._tag(ly) + ("x%d" % S), ly.cin, ly.cout, dims, cfg))
         if rows is not None:
             out._bfm_rows = rows
         return out
+
+    def _batch_plan(self, key, vers):
+        """The cached plan of a layer of the batched levels (key as in batch_conv: cin, cout, dims, two sources,
+        accumulate, 1), its variant clamped to `vers` = those that take a batch."""
+        if key not in self._plan_cache:
+            cfg = (C.c_int * 8)()
+            L.check(self.lib.bfm_conv3x3x3_mfma_plan(key[0], key[1], key[2][0], key[2][1], key[2][2], cfg), "mfma_plan")
+            if cfg[6] not in vers:
+                cfg[6] = 0
+            if key[4]:
+                cfg[7] = 1
+            self._plan_cache[key] = cfg
+        return self._plan_cache[key]
+
+    def _batch_launch(self, ly, cfg, A, B, upp, dims, scale, shift, bound, out, rows=None, aff=0):
+        """One launch of `ly` on the batch A (S,D,H,W,CA) [+ B]: conv_wino4d on the batch (cfg[6] == 4, one source) or
+        bfm_conv3x3x3_mfma_batch.  cfg[7] bit 0: accumulate onto `out`; aff: pitch of the rows of scale / shift when they
+        are column windows of wider tables (0: ly.cin)."""
+        S, (D, H, W), ca = A.shape[0], dims, A.shape[-1]
+        cb = 0 if B is None else B.shape[-1]
+        st = L.stream_ptr()
+        self._pack(ly, True, cfg[6])
+        if cfg[6] == 4:
+            L.check(self.lib.bfm_conv3x3x3_wino4_batch(L.ptr(A), ca, S, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound),
+                                                       ly.groups, L.ptr(ly.wpacked), ly.wexp, ly.cout, self.slope, self.passes,
+                                                       cfg[7] & 1, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
+                                                       aff, st), "conv_wino4_batch " + ly.name)
+            return
+        ws = self._workspace(self.lib.bfm_conv3x3x3_mfma_batch_workspace(ly.cin, ly.cout, S, D, H, W, cfg[5]))
+        L.check(self.lib.bfm_conv3x3x3_mfma_batch(L.ptr(A), ca, L.ptr(B) if cb else None, cb, S, D, H, W,
+                                                  upp if cb else None, L.ptr(scale), L.ptr(shift), L.ptr(bound), ly.groups,
+                                                  L.ptr(ly.wpacked), ly.wexp, ly.cout, self.slope, self.passes, cfg,
+                                                  L.ptr(out), L.ptr(ws), ws.numel(),
+                                                  L.ptr(rows[0]) if rows is not None else None, aff, st),
+                "conv_mfma_batch " + ly.name)
 
     def _batch_conv_upfold(self, ly, A, dims, B, lo_dims, scale, shift, bound):
         """A decoder's first conv on a batch, with the exact 2x upsample folded into the weights (as _single_conv_upfold
@@ -1103,66 +1089,28 @@ class UNetEngine:
         aff = ca + cb
         out = torch.empty((S, D, H, W, ly.cout), dtype=torch.float32, device=self.device)
         key = (ca, ly.cout, tuple(dims), False, True, 1)
-        if key not in self._plan_cache:
-            cfg = (C.c_int * 8)()
-            L.check(self.lib.bfm_conv3x3x3_mfma_plan(ca, ly.cout, D, H, W, cfg), "mfma_plan")
-            if cfg[6] not in self.DEEP_VERS_1SRC:
-                cfg[6] = 0
-            cfg[7] = 1
-            self._plan_cache[key] = cfg
-        cfg = self._plan_cache[key]
-
-        def _launch_skip(c, rows=None, A_=A, S_=S, out_=out, sc=sc_a, sh=sh_a, bd=bound):
-            self._pack(sk, True, c[6])
-            if c[6] == 4:                                      # conv_wino4d on the batch, accumulating onto the up-folded half
-                L.check(self.lib.bfm_conv3x3x3_wino4_batch(L.ptr(A_), ca, S_, D, H, W, L.ptr(sc), L.ptr(sh), L.ptr(bd), ly.groups,
-                                                           L.ptr(sk.wpacked), sk.wexp, ly.cout, self.slope, self.passes, 1,
-                                                           L.ptr(out_), L.ptr(rows[0]) if rows is not None else None, aff, st),
-                        "conv_wino4_batch " + sk.name)
-                return
-            ws = self._workspace(self.lib.bfm_conv3x3x3_mfma_batch_workspace(ca, ly.cout, S_, D, H, W, c[5]))
-            L.check(self.lib.bfm_conv3x3x3_mfma_batch(L.ptr(A_), ca, None, 0, S_, D, H, W, None, L.ptr(sc), L.ptr(sh),
-                                                      L.ptr(bd), ly.groups, L.ptr(sk.wpacked), sk.wexp, ly.cout,
-                                                      self.slope, self.passes, c, L.ptr(out_), L.ptr(ws), ws.numel(),
-                                                      L.ptr(rows[0]) if rows is not None else None, aff, st),
-                    "conv_mfma_batch " + sk.name)
+        cfg = self._batch_plan(key, self.DEEP_VERS_1SRC)
         if key not in self._tuned:                              # on one sample; trials accumulate onto garbage
-            cfg = self._autotune(sk, key, lambda c: _launch_skip(c, None, A[0:1], 1, out[0:1], sc_a[0:1], sh_a[0:1],
-                                                                 bound[0:1]), vers=self.DEEP_VERS_1SRC)
+            cfg = self._autotune(sk, key, lambda c: self._batch_launch(sk, c, A[0:1], None, None, dims, sc_a[0:1], sh_a[0:1],
+                                                                       bound[0:1], out[0:1], None, aff),
+                                 vers=self.DEEP_VERS_1SRC)
         self._pack(sk, True, cfg[6])
         nv = D * H * W
         lo = lo_dims[0] * lo_dims[1] * lo_dims[2]
-        tag = ly.name.replace("backbone.", "").replace(".basic_module.SingleConv", ".")
-        reps = max(1, int(self.prof_reps)) if self.prof is not None else 1
-        ev = None
-        if self.prof is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
         wsu = self.lib.bfm_conv3x3x3_upfold_batch_workspace(cb, S, lo_dims[0], lo_dims[1], lo_dims[2], ly.cout)
-        for _ in range(reps):
+
+        def _launch_up():
             ws = self._workspace(wsu)
             L.check(self.lib.bfm_conv3x3x3_upfold_batch(L.ptr(B), cb, S, lo_dims[0], lo_dims[1], lo_dims[2], L.ptr(sc_b),
                                                         L.ptr(sh_b), L.ptr(bound), ly.groups, L.ptr(wup), wexp_up,
                                                         ly.cout, self.passes, L.ptr(out), L.ptr(ws) if wsu else None,
                                                         ws.numel() if wsu else 0, aff, st), "conv_upfold_batch " + ly.name)
-        if ev is not None:
-            ev[1].record()
-            self.prof.append((ev[0], ev[1], 2.0 * 27 * cb * ly.cout * nv * S, 4.0 * (S * (lo * cb + nv * ly.cout)), reps,
-                              (tag + "x%dup" % S, cb, ly.cout, tuple(dims), (0,) * 8)))
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        rows = None
-        if self.fuse_stats:
-            n = (self.lib.bfm_conv3x3x3_wino4_rows(D, H, W, self.passes) if cfg[6] == 4 else
-                 self.lib.bfm_conv3x3x3_mfma_rows(ca, ly.cout, D, H, W, cfg))
-            if n > 0:
-                rows = (torch.empty(self.lib.bfm_moment_rows_bytes(S * n, ly.cout), dtype=torch.uint8, device=self.device), n)
-        for _ in range(reps):
-            _launch_skip(cfg, rows)
-        if ev is not None:
-            ev[1].record()
-            self.prof.append((ev[0], ev[1], 2.0 * 27 * ca * ly.cout * nv * S, 4.0 * S * (nv * ca + 2 * nv * ly.cout), reps,
-                              (tag + "x%dsk" % S, ca, ly.cout, tuple(dims), tuple(cfg))))
+        self._bracket(_launch_up, lambda: (2.0 * 27 * cb * ly.cout * nv * S, 4.0 * (S * (lo * cb + nv * ly.cout)),
+                                           self._tag(ly) + "x%dup" % S, cb, ly.cout, dims, (0,) * 8))
+        rows = self._rows_for(ca, ly.cout, dims, cfg, S)
+        self._bracket(lambda: self._batch_launch(sk, cfg, A, None, None, dims, sc_a, sh_a, bound, out, rows, aff),
+                      lambda: (2.0 * 27 * ca * ly.cout * nv * S, 4.0 * S * (nv * ca + 2 * nv * ly.cout),
+                               self._tag(ly) + "x%dsk" % S, ca, ly.cout, dims, cfg))
         if rows is not None:
             out._bfm_rows = rows
         return out
@@ -1221,31 +1169,17 @@ class UNetEngine:
         full output, so nothing that is kept changes); that map holds unwritten memory there."""
         if self.has_deep_region():
             return self.backbone_batch([x_cl], dims, mask_last=mask_last)[0]
-        self.__dict__["_uf_cache"] = {}                      # flags live for one pass (keyed by the image's address)
+        self._uf_cache = {}                                  # flags live for one pass (keyed by the image's address)
         mask_img = x_cl if (mask_last and self.mask_skip and x_cl.shape[-1] == 1) else None
-        UR = self.UNIFORM_RADIUS
-        skips = []
-        x, d = x_cl, tuple(dims)
-        for i, (l1, l2) in enumerate(self.enc):
-            if i > 0:
-                if min(d) < 2:
-                    raise L.BfmError("volume %s too small for %d pooling levels" % (dims, len(self.enc) - 1))
-                x, d = self.maxpool(x, d)
-            uf1 = self.uniform_flags(x_cl, dims, UR[("enc", i, 0)], i) if ("enc", i, 0) in UR else None
-            x = self.single_conv(l1, x, d, uni_flags=uf1)
-            uf2 = self.uniform_flags(x_cl, dims, UR[("enc", i, 1)], i) if ("enc", i, 1) in UR else None
-            x = self.single_conv(l2, x, d, uni_flags=uf2, pool=i + 1 < len(self.enc))
-            skips.insert(0, (x, d))
-        skips = skips[1:]
-        feats = [(x, d)]
-        for k, ((l1, l2), (skip, sd_)) in enumerate(zip(self.dec, skips)):
-            lvl = len(self.dec) - 1 - k                       # the level this decoder ends at
-            uf = self.uniform_flags(x_cl, dims, UR[("dec", lvl)], lvl) if ("dec", lvl) in UR else None
-            y = self.single_conv(l1, skip, sd_, B=x, lo_dims=d, uni_flags=uf)
-            x = self.single_conv(l2, y, sd_, mask_img=mask_img if k == len(self.dec) - 1 else None)
-            d = sd_
-            feats.append((x, d))
-        return feats
+        skips = self.encoder_top(x_cl, dims, len(self.enc))  # no batched region: every level, then every decoder
+        x, d = skips.pop()
+        return [(x, d)] + self.decoder_top(skips, x, d, mask_img=mask_img, df=len(self.enc) - 1, image=x_cl)
+
+    def _layer_flags(self, key, image, dims):
+        """uniform_flags of the input image for the layer UNIFORM_RADIUS lists under `key` (key[1]: its level), else None."""
+        if key not in self.UNIFORM_RADIUS:
+            return None
+        return self.uniform_flags(image, dims, self.UNIFORM_RADIUS[key], key[1])
 
     def encoder_top(self, x_cl, dims, df=None):
         """Encoder levels < df (default deep_from) of one sample: ([(skip, dims)] shallowest first, top = last of them)."""
@@ -1257,11 +1191,9 @@ class UNetEngine:
                 if min(d) < 2:
                     raise L.BfmError("volume %s too small for %d pooling levels" % (dims, len(self.enc) - 1))
                 x, d = self.maxpool(x, d)
-            UR = self.UNIFORM_RADIUS
-            uf1 = self.uniform_flags(x_cl, dims, UR[("enc", i, 0)], i) if ("enc", i, 0) in UR else None
-            x = self.single_conv(l1, x, d, uni_flags=uf1)
-            uf2 = self.uniform_flags(x_cl, dims, UR[("enc", i, 1)], i) if ("enc", i, 1) in UR else None
-            x = self.single_conv(l2, x, d, uni_flags=uf2, pool=i + 1 < nlev)     # (the region pools the last level itself)
+            x = self.single_conv(l1, x, d, uni_flags=self._layer_flags(("enc", i, 0), x_cl, dims))
+            x = self.single_conv(l2, x, d, uni_flags=self._layer_flags(("enc", i, 1), x_cl, dims),
+                                 pool=i + 1 < nlev)              # (the region pools the last level itself)
             skips.append((x, d))
         return skips
 
@@ -1273,10 +1205,7 @@ class UNetEngine:
         nd = len(self.dec) - ndeep
         for k, ((l1, l2), (skip, sd_)) in enumerate(zip(self.dec[ndeep:], reversed(skips))):
             lvl = nd - 1 - k                                  # the level this decoder ends at
-            uf = None
-            if image is not None and ("dec", lvl) in self.UNIFORM_RADIUS:
-                idims = tuple(image.shape[:3])
-                uf = self.uniform_flags(image, idims, self.UNIFORM_RADIUS[("dec", lvl)], lvl)
+            uf = self._layer_flags(("dec", lvl), image, tuple(image.shape[:3])) if image is not None else None
             y = self.single_conv(l1, skip, sd_, B=x, lo_dims=d, uni_flags=uf)
             x = self.single_conv(l2, y, sd_, mask_img=mask_img if k == nd - 1 else None)
             d = sd_
@@ -1287,7 +1216,7 @@ class UNetEngine:
         """The backbone of S same-shape samples: encoder levels above the region per sample, the region batched, the
         remaining decoders per sample.  Returns one feature list per sample (deepest first, like backbone_cl).
         mask_last: as in backbone_cl."""
-        self.__dict__["_uf_cache"] = {}                      # flags live for one pass (keyed by the image's address)
+        self._uf_cache = {}                                  # flags live for one pass (keyed by the image's address)
         df = self.region_start(dims)
         tops = [self.encoder_top(x, dims, df) for x in xs]
         out, d, deep_feats = self.deep_region([t[-1] for t in tops], df)

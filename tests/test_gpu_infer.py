@@ -2333,3 +2333,106 @@ def test_deep_odd_shape_64x80x96_vs_reference_deep_golden():
     eng = _deep_single_case("C/", x)
     assert eng.region_start(tuple(x.shape[2:])) == 2
     assert "upfold" in eng.dec[1][0].packs and "upfold" not in eng.dec[0][0].packs
+
+
+def test_instrumented_pass_records_every_conv_launch_and_changes_no_bit():
+    """The instrumented pass (eng.prof = [], what bench.py's roofline block and layer table are built from) against the
+    plain one, on the smallest shape that reaches every bracket with the default switches: a 64-wide 4-level net on two
+    40^3 tiles, one with its first 20 slices zero.  The batched region starts at level 2 (10^3 = 1 000 voxels <= deep_vox);
+    level 3 has 5^3 = 125 >= deep_upfold_min voxels, so decoder 0 takes the batched up-fold; decoders 1 and 2 (low sides
+    10^3 and 20^3 >= upfold_min) the per-tile up-fold.  Once through backbone_batch, once per sample through backbone_cl
+    with deep_batch off (an engine each, so that `"upfold" in ly.packs` says what that flow up-folded):
+    (1) with prof_reps = 1 every feature map is bit-identical with and without the brackets (the last map where the
+        input is non-zero: the masked boxes hold unwritten memory);
+    (2) every record is (Event, Event, float, float, int, (str, int, int, 3-tuple, 8-tuple of int));
+    (3) there is one record per matrix-core SingleConv launch, two for an up-folded layer;
+    (4) with mask_skip and uniform_skip off the recorded FLOPs sum to 2 * 27 * cin * cout * voxels per layer and sample --
+        integers below 2^53, so the float sum is exact;
+    (5) every tag is the layer's short name plus one of the suffixes bench.py's kernel_of / issue_factor read, and the
+        suffixes this shape must produce ("", "up", an "sk" form; batched also "x2", "x2up", "x2sk") all occur."""
+    from brainfm_amd.engine import UNetEngine
+    sd = O.random_state_dict(1, 64, 4, seed=41)
+    dims = (40, 40, 40)
+    g = torch.Generator().manual_seed(14)
+    xs = [torch.rand(dims + (1,), generator=g).to(_dev()) for _ in range(2)]
+    xs[1][:20] = 0
+    S = len(xs)
+
+    def matrix_core(ly):
+        return ly.cin % 16 == 0 and ly.cout % 64 == 0
+
+    def n_records(layers):
+        return sum(2 if "upfold" in ly.packs else 1 for ly in layers if matrix_core(ly))
+
+    def check_records(prof):
+        for p in prof:
+            assert len(p) == 6 and isinstance(p[0], torch.cuda.Event) and isinstance(p[1], torch.cuda.Event), p
+            assert type(p[2]) is float and type(p[3]) is float and type(p[4]) is int and p[4] == 1, p
+            tag, cin, cout, dd, cfg = p[5]
+            assert type(tag) is str and type(cin) is int and type(cout) is int, p[5]
+            assert type(dd) is tuple and len(dd) == 3 and all(type(v) is int for v in dd), p[5]
+            assert type(cfg) is tuple and len(cfg) == 8 and all(type(v) is int for v in cfg), p[5]
+
+    def check_tags(prof, need):
+        """The tags are `<en|de>coders.<i>.<j>` plus the suffix bench.py's kernel_of / issue_factor read."""
+        import re
+        seen = set()
+        for p in prof:
+            m = re.fullmatch(r"(?:encoders|decoders)\.\d+\.[12](.*)", p[5][0])
+            assert m, p[5]
+            seen.add(m.group(1))
+        assert seen <= {"", "[masked]", "[uniform]", "up", "sk", "sk[uniform]", "x%d" % S, "x%dup" % S, "x%dsk" % S}, seen
+        assert need <= seen and seen & {"sk", "sk[uniform]"}, (seen, need)
+
+    def same_bits(plain, prof):
+        assert len(plain) == len(prof) == S
+        for s_ in range(S):
+            assert len(plain[s_]) == len(prof[s_]) == 4
+            for i, ((a, da), (b, db)) in enumerate(zip(plain[s_], prof[s_])):
+                assert da == db
+                if i == len(plain[s_]) - 1:
+                    m = xs[s_][..., 0] != 0
+                    a, b = a[m], b[m]
+                assert torch.equal(a, b), (s_, i, da)
+
+    for batched in (True, False):
+        eng = UNetEngine(sd, in_channels=1, f_maps=64, num_levels=4, device=_dev())
+        eng.deep_batch = batched
+        assert eng.has_deep_region() == batched and eng.region_start(dims) == 2
+
+        def run():
+            if batched:
+                return eng.backbone_batch(xs, dims, mask_last=True)
+            return [eng.backbone_cl(x, dims, mask_last=True) for x in xs]
+
+        plain = run()
+        eng.prof, eng.prof_reps = [], 1
+        try:
+            inst = run()
+            prof = eng.prof
+            eng.mask_skip = eng.uniform_skip = False
+            eng.prof = []
+            run()
+            full = eng.prof
+        finally:
+            eng.prof = None
+        same_bits(plain, inst)
+        check_records(prof)
+        check_records(full)
+        check_tags(prof, {"", "up", "x%d" % S, "x%dup" % S, "x%dsk" % S} if batched else {"", "up"})
+        check_tags(full, {"", "up", "sk", "x%d" % S, "x%dup" % S, "x%dsk" % S} if batched else {"", "up", "sk"})
+        level = [(ly, i) for i, pair in enumerate(eng.enc) for ly in pair]
+        level += [(ly, len(eng.dec) - 1 - k) for k, pair in enumerate(eng.dec) for ly in pair]
+        if batched:
+            top = [ly for ly, lv in level if lv < 2]                  # per sample: encoders 0, 1 and decoders 1, 2
+            region = [ly for ly, lv in level if lv >= 2]              # once for the batch
+            want = S * n_records(top) + n_records(region)
+            assert "upfold" in eng.dec[0][0].packs
+        else:
+            want = S * n_records([ly for ly, _ in level])
+            assert "upfold" not in eng.dec[0][0].packs
+        assert "upfold" in eng.dec[1][0].packs and "upfold" in eng.dec[2][0].packs
+        assert len(prof) == len(full) == want, (batched, len(prof), len(full), want)
+        flops = sum(2 * 27 * ly.cin * ly.cout * (dims[0] >> lv) * (dims[1] >> lv) * (dims[2] >> lv) * S
+                    for ly, lv in level if matrix_core(ly))
+        assert flops < 2 ** 53 and sum(p[2] for p in full) == float(flops), (batched, sum(p[2] for p in full), flops)
