@@ -95,7 +95,6 @@ SIGNATURES = {
     "bfm_version": (C.c_char_p, []),
     "bfm_gn_stats_workspace": (_Z, [_I, _I, _I, _I, _I, _UP]),
     "bfm_gn_stats": (_I, [_P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P]),
-    "bfm_pack_conv_weights_direct_bytes": (_Z, [_I, _I]),
     "bfm_pack_conv_weights_direct": (_I, [_P, _I, _I, _P, _P]),
     "bfm_pack_conv_weights_mfma_bytes": (_Z, [_I, _I]),
     "bfm_pack_conv_weights_mfma": (_I, [_P, _I, _I, _F, _P, C.POINTER(_I), _P]),
@@ -142,7 +141,6 @@ SIGNATURES = {
     "bfm_mean_lastdim": (_I, [_P, _L, _I, _P, _P]),
     "bfm_pack_conv_weights_wino_bytes": (_Z, [_I, _I, _I]),
     "bfm_pack_conv_weights_wino": (_I, [_P, _I, _I, _F, _I, _P, C.POINTER(_I), _P]),
-    "bfm_conv3x3x3_wino": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P]),
     "bfm_bspline3_prefilter_axis": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P, _F, _F, _F, _P]),
     "bfm_bspline3_resample_axis": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "bfm_conv3x3x3_wino_rows": (_I, [_I, _I, _I, _I]),
@@ -201,7 +199,6 @@ SIGNATURES = {
     "bfm_grad_sumsq": (_I, [_P, _L, _P, _P, _P, _Z, _P]),
     "bfm_grad_sumsq_multi": (_I, [_P, _I, _P, _I, _L, _P, _P, _P, _Z, _P]),
     "bfm_adamw_step_multi": (_I, [_P, _I, _P, _I, _L, _F, _F, _F, _F, _F, _P]),
-    "bfm_conv3x3x3_stem": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P]),
     "bfm_conv3x3x3_mfma_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
     "bfm_conv3x3x3_mfma_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "bfm_conv3x3x3_mfma": (_I, [_P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _P, _I, _P, _I, _I, _F, _I,
@@ -214,7 +211,6 @@ SIGNATURES = {
     "bfm_absmax_f32": (_I, [_P, _L, _L, _L, _P, _P]),
     "bfm_softmax_cl": (_I, [_P, _L, _I, _P, _L, _L, _P]),
     "bfm_argmax_lut_cl": (_I, [_P, _L, _I, _P, _P, _L, _P]),
-    "bfm_pathology_encode": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _L, _P, _P]),
     "bfm_fake_cortical": (_I, [_P, _L, _I, _P, _L, _P]),
     "bfm_interp3d_linear": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _F, _P, _P]),
     "bfm_interp3d_nearest": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
@@ -269,12 +265,9 @@ SIGNATURES = {
     "bfm_pathology_encode_dev": (_I, [_P, _P, _P, _I, _P, C.POINTER(_F), _I, _P, _L, _P, _P, _P, _Z, _P]),
     "bfm_interp3d_linear_axes": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P]),
     "bfm_sample_finalize": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P]),
-    "bfm_ew_dev": (_I, [_I, _P, _L, _P, _F, _P, _P]),
     "bfm_stitch_accumulate": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bfm_stitch_accumulate_multi": (_I, [_P, _L, _P, _I, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "bfm_mask_tile": (_I, [_P, _P, _P, _L, _P, _P]),
     "bfm_tile_count_add": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "bfm_divide_by_count": (_I, [_P, _P, _L, _P]),
     "bfm_pack_tile_multi": (_I, [_P, _L, _P, _I, _P, _P, _L, _P, _P]),
     "bfm_divide_by_count_multi": (_I, [_P, _P, _L, _I, _P]),
     "bfm_stitch_gather_multi": (_I, [_P, _I, _I, _P, _I, _I, _I, _P]),

@@ -8,7 +8,7 @@
 //
 // One thread = one output voxel x 8 output channels; blockIdx.y = channel
 // group, so the weight addresses are wave-uniform (scalar loads).
-#include "bfm_common.h"
+#include "conv_shared.h"
 
 namespace {
 
@@ -275,10 +275,6 @@ __global__ void __launch_bounds__(256, 3) conv_stem_mfma(const float* __restrict
 
 }  // namespace
 
-extern "C" size_t bfm_pack_conv_weights_direct_bytes(int Cin, int Cout) {
-    return (size_t)27 * Cin * Cout * sizeof(float);
-}
-
 extern "C" int bfm_pack_conv_weights_direct(const float* w, int Cin, int Cout, float* wpacked, bfm_stream_t stream) {
     if (!w || !wpacked || Cin <= 0 || Cout <= 0) return BFM_E_ARG;
     int64_t n = (int64_t)27 * Cin * Cout;
@@ -323,28 +319,13 @@ extern "C" int bfm_conv3x3x3_stem_ex(const float* A, int D, int H, int W, const 
     if ((int64_t)D * H * W >= ((int64_t)1 << 31)) return BFM_E_SHAPE;          // the kernel indexes the input with 32 bits
     const int64_t nblk = (int64_t)D * H * ((W + 31) / 32);
     const int64_t nb = stem_grid(D, H, W);
-    double *rsum = nullptr, *rsq = nullptr;
-    float *rmn = nullptr, *rmx = nullptr;
-    if (moment_rows) {
-        if (reinterpret_cast<uintptr_t>(moment_rows) & 7) return BFM_E_ARG;
-        char* rb = static_cast<char*>(moment_rows);
-        const size_t n = (size_t)nb * 4 * Cout;
-        rsum = reinterpret_cast<double*>(rb);
-        rsq = reinterpret_cast<double*>(rb + n * 8);
-        rmn = reinterpret_cast<float*>(rb + n * 16);
-        rmx = reinterpret_cast<float*>(rb + n * 20);
-    }
+    MomentRows r;
+    if (moment_rows && !r.carve(moment_rows, (size_t)nb * 4 * Cout)) return BFM_E_ARG;
     if (Cout == 32)
         hipLaunchKernelGGL(conv_stem_mfma<1>, dim3((unsigned)nb), dim3(256), 0, bfm_s(stream), A, D, H, W, scale, shift,
-                           bound, wpacked_direct, slope, out, nblk, rsum, rsq, rmn, rmx);
+                           bound, wpacked_direct, slope, out, nblk, r.rsum, r.rsq, r.rmn, r.rmx);
     else
         hipLaunchKernelGGL(conv_stem_mfma<2>, dim3((unsigned)nb), dim3(256), 0, bfm_s(stream), A, D, H, W, scale, shift,
-                           bound, wpacked_direct, slope, out, nblk, rsum, rsq, rmn, rmx);
+                           bound, wpacked_direct, slope, out, nblk, r.rsum, r.rsq, r.rmn, r.rmx);
     return bfm_launch_status();
-}
-
-extern "C" int bfm_conv3x3x3_stem(const float* A, int D, int H, int W, const float* scale, const float* shift,
-                                  const float* bound, const float* wpacked_direct, int Cout, float slope, float* out,
-                                  bfm_stream_t stream) {
-    return bfm_conv3x3x3_stem_ex(A, D, H, W, scale, shift, bound, wpacked_direct, Cout, slope, out, nullptr, stream);
 }

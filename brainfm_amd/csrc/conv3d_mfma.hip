@@ -23,7 +23,7 @@
 // relative product error (passes=3).  passes=1 keeps only hi*hi.
 //
 // Wave tile 64x64 (2x2 MFMA blocks), workgroup = WM x WN waves.
-#include "bfm_common.h"
+#include "conv_shared.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -112,18 +112,6 @@ __device__ __forceinline__ void store_moment_row(const ConvParams& p, unsigned c
         const size_t o = (size_t)mt * p.Cout + (nt * WN + w2) * 64 + c;
         p.rsum[o] = S; p.rsq[o] = Q; p.rmn[o] = MN; p.rmx[o] = MX;
     }
-}
-
-// lane (= MFMA row) -> position inside the 32-row block such that every
-// ds_read_b128 lane group {0-3,12-15,20-27} / {4-11,16-19,28-31} reads 16
-// consecutive box positions (one w-run when TW == 16): conflict-free.
-__device__ __forceinline__ int row_perm(int l) {
-    if (l < 4) return l;
-    if (l < 12) return l + 12;
-    if (l < 16) return l - 8;
-    if (l < 20) return l + 8;
-    if (l < 28) return l - 12;
-    return l;
 }
 
 __device__ __forceinline__ void box_coords(const ConvParams& p, int q, int& d, int& h, int& w) {
@@ -1403,32 +1391,24 @@ HostPlan choose_plan(int Cin, int Cout, int D, int H, int W) {
 }
 
 void launch16(const ConvParams& p, int passes, bool wm4, dim3 grid, size_t smem, hipStream_t st) {
-    if (wm4) {
-        if (passes == 3) hipLaunchKernelGGL((conv_mfma16<4, 1, 3, 2, 2>), grid, dim3(256), smem, st, p);
-        else hipLaunchKernelGGL((conv_mfma16<4, 1, 1, 2, 2>), grid, dim3(256), smem, st, p);
-    } else {
-        if (passes == 3) hipLaunchKernelGGL((conv_mfma16<2, 2, 3, 1, 3>), grid, dim3(256), smem, st, p);
-        else hipLaunchKernelGGL((conv_mfma16<2, 2, 1, 1, 3>), grid, dim3(256), smem, st, p);
-    }
+    if (wm4) bfm_launch_by_passes(passes, conv_mfma16<4, 1, 3, 2, 2>, conv_mfma16<4, 1, 1, 2, 2>, grid, dim3(256), smem, st, p);
+    else bfm_launch_by_passes(passes, conv_mfma16<2, 2, 3, 1, 3>, conv_mfma16<2, 2, 1, 1, 3>, grid, dim3(256), smem, st, p);
 }
 
 template <int WM, int WN>
-void launch_ws(const ConvParams& p, int passes, dim3 grid, size_t smem, hipStream_t st) {
-    if (passes == 3) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_ws<WM, WN, 3>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT_WS);
-        hipLaunchKernelGGL((conv_mfma_ws<WM, WN, 3>), grid, dim3(512), smem, st, p);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_ws<WM, WN, 1>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT_WS);
-        hipLaunchKernelGGL((conv_mfma_ws<WM, WN, 1>), grid, dim3(512), smem, st, p);
-    }
+int launch_ws(const ConvParams& p, int passes, dim3 grid, size_t smem, hipStream_t st) {
+    static bool attr = false;
+    if (const int rc = bfm_raise_lds_limit(attr, {bfm_kernel(&conv_mfma_ws<WM, WN, 3>), bfm_kernel(&conv_mfma_ws<WM, WN, 1>)},
+                                           LDS_LIMIT_WS))
+        return rc;
+    bfm_launch_by_passes(passes, conv_mfma_ws<WM, WN, 3>, conv_mfma_ws<WM, WN, 1>, grid, dim3(512), smem, st, p);
+    return BFM_OK;
 }
 
 template <int WM, int WN>
 void launch(const ConvParams& p, int passes, dim3 grid, size_t smem, hipStream_t st) {
-    if (passes == 3) hipLaunchKernelGGL((conv_mfma<WM, WN, 3, nslot_for(WN)>), grid, dim3(64 * WM * WN), smem, st, p);
-    else hipLaunchKernelGGL((conv_mfma<WM, WN, 1, nslot_for(WN)>), grid, dim3(64 * WM * WN), smem, st, p);
+    bfm_launch_by_passes(passes, conv_mfma<WM, WN, 3, nslot_for(WN)>, conv_mfma<WM, WN, 1, nslot_for(WN)>, grid,
+                         dim3(64 * WM * WN), smem, st, p);
 }
 
 }  // namespace
@@ -1453,12 +1433,7 @@ extern "C" int bfm_pack_conv_weights_mfma(const float* w, int Cin, int Cout, flo
     const int64_t nblk = (int64_t)(Cout / 64) * (Cin / KC) * 2;
     const size_t smem = (size_t)32 * PK_ROW * sizeof(float);
     static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pack_mfma_tiled), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return BFM_E_LAUNCH;
-        attr = true;
-    }
+    if (const int rc = bfm_raise_lds_limit(attr, {bfm_kernel(&pack_mfma_tiled)}, (int)smem)) return rc;
     if (nblk <= 0x7fffffff) {
         hipLaunchKernelGGL(pack_mfma_tiled, dim3((unsigned)nblk), dim3(256), smem, bfm_s(stream), w, Cin, Cout, wexp,
                            reinterpret_cast<uint4*>(wpacked));
@@ -1492,12 +1467,7 @@ extern "C" int bfm_pack_conv_weights_mfma16(const float* w, int Cin, int Cout, f
     if (nblk <= 0x7fffffff) {
         const size_t smem = (size_t)32 * PK16_ROW * sizeof(float);
         static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pack_mfma16_tiled),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-                return BFM_E_LAUNCH;
-            attr = true;
-        }
+        if (const int rc = bfm_raise_lds_limit(attr, {bfm_kernel(&pack_mfma16_tiled)}, (int)smem)) return rc;
         hipLaunchKernelGGL(pack_mfma16_tiled, dim3((unsigned)nblk), dim3(256), smem, bfm_s(stream), w, Cin, Cout, wexp,
                            reinterpret_cast<uint4*>(wpacked));
         return bfm_launch_status();
@@ -1668,13 +1638,9 @@ static int conv_mfma_launch(const float* A, int CA, const float* B, int CB, int 
         if (reinterpret_cast<uintptr_t>(moment_rows) & 7) return BFM_E_ARG;      // written by splitk_reduce_rows below
     } else if (moment_rows) {
         if (hp.ver == 1) return BFM_E_SHAPE;                   // see bfm_conv3x3x3_mfma_rows
-        if (reinterpret_cast<uintptr_t>(moment_rows) & 7) return BFM_E_ARG;
-        char* rb = static_cast<char*>(moment_rows);
-        const size_t n = (size_t)p.nMt * Cout;
-        p.rsum = reinterpret_cast<double*>(rb);
-        p.rsq = reinterpret_cast<double*>(rb + n * 8);
-        p.rmn = reinterpret_cast<float*>(rb + n * 16);
-        p.rmx = reinterpret_cast<float*>(rb + n * 20);
+        MomentRows rows;
+        if (!rows.carve(moment_rows, (size_t)p.nMt * Cout)) return BFM_E_ARG;
+        rows.into(p);
     }
 #ifdef BFM_MFMA_ABLATE
     if (const char* e = getenv("BFM_MFMA_ABL")) p.abl = atoi(e);
@@ -1693,8 +1659,8 @@ static int conv_mfma_launch(const float* A, int CA, const float* B, int CB, int 
     if (hp.ver == 2) {
         launch16(p, passes, hp.WM == 4, grid, smem, st);
     } else if (hp.ver == 1) {
-        if (hp.WM == 4) launch_ws<4, 1>(p, passes, grid, smem, st);
-        else launch_ws<2, 2>(p, passes, grid, smem, st);
+        if (const int rc = hp.WM == 4 ? launch_ws<4, 1>(p, passes, grid, smem, st) : launch_ws<2, 2>(p, passes, grid, smem, st))
+            return rc;
     } else {
         if (hp.WM == 4) launch<4, 1>(p, passes, grid, smem, st);
         else launch<2, 2>(p, passes, grid, smem, st);
@@ -1706,12 +1672,11 @@ static int conv_mfma_launch(const float* A, int CA, const float* B, int CB, int 
         const int vpb = splitk_rows_vpb(nvox, Cout);
         const int nrows = (int)bfm_cdiv64(nvox, vpb);
         const int CG = Cout / 4, CGB = splitk_cgb(CG);
-        char* rb = static_cast<char*>(moment_rows);
-        const size_t n = (size_t)S * nrows * Cout;
+        MomentRows rows;
+        (void)rows.carve(moment_rows, (size_t)S * nrows * Cout);         // its alignment was checked above
         hipLaunchKernelGGL(splitk_reduce_rows, dim3(nrows, CG / CGB, S), dim3(256), 0, st,
                            static_cast<const float*>(workspace), p.splitk, p.split_stride / 4, (int)nvox, Cout, vpb, nrows,
-                           slope, p.accum, out, reinterpret_cast<double*>(rb), reinterpret_cast<double*>(rb + n * 8),
-                           reinterpret_cast<float*>(rb + n * 16), reinterpret_cast<float*>(rb + n * 20));
+                           slope, p.accum, out, rows.rsum, rows.rsq, rows.rmn, rows.rmx);
         rc = bfm_launch_status();
     } else if (p.splitk > 1) {
         int64_t n4 = (int64_t)S * nvox * Cout / 4;

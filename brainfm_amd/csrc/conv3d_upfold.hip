@@ -16,7 +16,7 @@
 // conv3d_mfma.hip (hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_f16, fp32 accumulate).
 // The result (no activation) is written to the interleaved full-res positions of `out`; the skip half of the
 // convolution then runs through bfm_conv3x3x3_mfma with the accumulate flag (cfg[7] bit 0) and applies LeakyReLU.
-#include "bfm_common.h"
+#include "conv_shared.h"
 #include <type_traits>
 
 namespace {
@@ -51,15 +51,6 @@ struct UpParams {
     int64_t sB, sO;
     int dbg_sleep;                   // diagnostics builds: odd CUs' first workgroups start this many kilocycles late
 };
-
-__device__ __forceinline__ int row_perm(int l) {        // same lane -> row order as conv_mfma (conflict-free b128)
-    if (l < 4) return l;
-    if (l < 12) return l + 12;
-    if (l < 16) return l - 8;
-    if (l < 20) return l + 8;
-    if (l < 28) return l - 12;
-    return l;
-}
 
 __device__ __forceinline__ void box_coords(const UpParams& p, int q, int& bd, int& bh, int& bw) {
     bd = q / p.BHW;
@@ -483,12 +474,7 @@ extern "C" int bfm_pack_conv_weights_upfold(const float* w_oidhw, int CA, int CB
     const int64_t nblk = (int64_t)(Cout / 64) * (CB / KC);
     const size_t smem = (size_t)64 * PKU_ROW * sizeof(float);
     static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pack_upfold_tiled), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return BFM_E_LAUNCH;
-        attr = true;
-    }
+    if (const int rc = bfm_raise_lds_limit(attr, {bfm_kernel(&pack_upfold_tiled)}, (int)smem)) return rc;
     if (nblk <= 0x7fffffff) {
         hipLaunchKernelGGL(pack_upfold_tiled, dim3((unsigned)nblk), dim3(256), smem, bfm_s(stream), w_oidhw, CA + CB, CA, CB,
                            Cout, wexp, npl, static_cast<uint4*>(wpacked));
@@ -633,10 +619,8 @@ static int upfold_launch(const float* B, int CB, int S, int d, int h, int w, con
         const int64_t gx = 16 * bfm_cdiv64(nblk, 8);
         if (gx > 0x7fffffff) return BFM_E_SHAPE;
         dim3 gridh((unsigned)gx, (unsigned)nsplit, (unsigned)S);
-        if (passes == 3) hipLaunchKernelGGL(conv_upfold_h<3>, gridh, dim3(NTHR / 2), smem, bfm_s(stream), p);
-        else hipLaunchKernelGGL(conv_upfold_h<1>, gridh, dim3(NTHR / 2), smem, bfm_s(stream), p);
-    } else if (passes == 3) hipLaunchKernelGGL(conv_upfold<3>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-    else hipLaunchKernelGGL(conv_upfold<1>, grid, dim3(NTHR), smem, bfm_s(stream), p);
+        bfm_launch_by_passes(passes, conv_upfold_h<3>, conv_upfold_h<1>, gridh, dim3(NTHR / 2), smem, bfm_s(stream), p);
+    } else bfm_launch_by_passes(passes, conv_upfold<3>, conv_upfold<1>, grid, dim3(NTHR), smem, bfm_s(stream), p);
     if (nsplit > 1) {
         const int64_t n4 = nout / 4;
         const int nb = (int)std::min<int64_t>(4096, bfm_cdiv64(n4, 256));

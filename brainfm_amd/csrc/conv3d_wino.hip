@@ -17,7 +17,6 @@
 // stream L2 -> VGPR two taps ahead.  Epilogue: the four m_p meet in LDS, one thread per (pair, cout) forms y0/y1,
 // dequantises, optionally adds what `out` holds (accumulate mode, the skip half of an up-folded decoder conv),
 // applies LeakyReLU and stores 128-byte row segments.  Single-source inputs only (CB == 0), no split-K.
-#include "bfm_common.h"
 #include "wino_shared.h"
 #include <cstdlib>
 #include <type_traits>
@@ -61,24 +60,6 @@ struct WinoParams {
     float *prmn, *prmx;
 };
 
-__device__ __forceinline__ int row_perm(int l) {        // as conv_mfma: each 16-lane b128 group reads 16 consecutive positions
-    if (l < 4) return l;
-    if (l < 12) return l + 12;
-    if (l < 16) return l - 8;
-    if (l < 20) return l + 8;
-    if (l < 28) return l - 12;
-    return l;
-}
-
-__device__ __forceinline__ int row_unperm(int q) {      // inverse of row_perm
-    if (q < 4) return q;
-    if (q < 8) return q + 8;
-    if (q < 16) return q + 12;
-    if (q < 24) return q - 12;
-    if (q < 28) return q - 8;
-    return q;
-}
-
 __device__ __forceinline__ void pair_coords(const WinoParams& p, int q, int& d, int& h, int& j) {
     d = q >> p.thp_shift;
     const int rem = q & ((1 << p.thp_shift) - 1);
@@ -90,6 +71,7 @@ __device__ __forceinline__ void pair_coords(const WinoParams& p, int q, int& d, 
 // exact in fp32 and at most 2^-10 |x|), lo = fp16(x - hi) by one v_fma_mixlo/hi_f16 per value (fp32 = fp16 * -1 + fp32,
 // rounded to nearest; round 5: in place of convert-back, subtract and re-pack -- 6 instead of 12 instructions per four
 // values); the neglected lo*lo product stays below 2^-20 relative.
+// (not in conv_shared.h: conv3d_wino4.hip's split_store4 truncates lo as well, with a convert, subtract and re-pack)
 typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
 template <bool LO>
 __device__ __forceinline__ void split_store4(const float (&t)[4], unsigned char* dp, int plane_stride) {
@@ -807,11 +789,10 @@ bool bfm_wino_choose_box(int D, int H, int W, int npl, int& TD, int& TH, int& TW
 
 int bfm_wino_mask_list(const float* mask_img, int D, int H, int W, int TD, int TH, int TW, int nTy, int nTx, int nMt, void* ws,
                        bfm_stream_t stream) {
-    unsigned char* act = static_cast<unsigned char*>(ws);
-    int* cnt = reinterpret_cast<int*>(act + (((size_t)nMt + 3) & ~(size_t)3));
+    const MaskListBuf b{ws, (size_t)nMt};
     hipLaunchKernelGGL(wino_box_active_kernel, dim3((unsigned)bfm_cdiv(nMt, 4)), dim3(256), 0, bfm_s(stream), mask_img, D, H, W,
-                       TD, TH, TW, nTy, nTx, nMt, act);
-    hipLaunchKernelGGL(wino_mask_list_kernel, dim3(1), dim3(1024), 0, bfm_s(stream), act, nMt, cnt + 1, cnt);
+                       TD, TH, TW, nTy, nTx, nMt, b.act());
+    hipLaunchKernelGGL(wino_mask_list_kernel, dim3(1), dim3(1024), 0, bfm_s(stream), b.act(), nMt, b.list(), b.count());
     return bfm_launch_status();
 }
 
@@ -837,12 +818,7 @@ extern "C" int bfm_pack_conv_weights_wino(const float* w_oidhw, int Cin, int Cou
     const int64_t nblk = (int64_t)(Cout / 64) * (Cin / KC) * 2;
     const size_t smem = (size_t)32 * PKW_ROW * sizeof(float);
     static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pack_wino_tiled), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return BFM_E_LAUNCH;
-        attr = true;
-    }
+    if (const int rc = bfm_raise_lds_limit(attr, {bfm_kernel(&pack_wino_tiled)}, (int)smem)) return rc;
     if (nblk <= 0x7fffffff) {
         hipLaunchKernelGGL(pack_wino_tiled, dim3((unsigned)nblk), dim3(256), smem, bfm_s(stream), w_oidhw, Cin, Cout, wexp, npl,
                            static_cast<uint4*>(wpacked));
@@ -859,7 +835,7 @@ extern "C" int bfm_pack_conv_weights_wino(const float* w_oidhw, int Cin, int Cou
 extern "C" int bfm_conv3x3x3_wino_rows(int D, int H, int W, int passes) {
     int TD, TH, TW;
     if (D <= 0 || H <= 0 || W <= 0 || !choose_box(D, H, W, passes == 3 ? 2 : 1, TD, TH, TW)) return 0;
-    return bfm_cdiv(D, TD) * bfm_cdiv(H, TH) * bfm_cdiv(W, TW);
+    return (int)bfm_box_count(D, H, W, TD, TH, TW);
 }
 
 extern "C" int bfm_conv3x3x3_wino_box(int D, int H, int W, int passes, int* box) {
@@ -868,24 +844,6 @@ extern "C" int bfm_conv3x3x3_wino_box(int D, int H, int W, int passes, int* box)
     box[0] = TD; box[1] = TH; box[2] = TW;
     return BFM_OK;
 }
-
-extern "C" int bfm_conv3x3x3_wino_ex(const float* A, int CA, int D, int H, int W, const float* scale,
-                                     const float* shift, const float* bound, int G, const void* wpacked, int wexp,
-                                     int Cout, float slope, int passes, int flags, float* out, void* moment_rows,
-                                     bfm_stream_t stream);
-
-extern "C" int bfm_conv3x3x3_wino(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
-                                  const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope,
-                                  int passes, int flags, float* out, bfm_stream_t stream) {
-    return bfm_conv3x3x3_wino_ex(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out,
-                                 nullptr, stream);
-}
-
-static int wino_launch(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
-                       const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes, int flags,
-                       float* out, void* moment_rows, const float* mask_img, bfm_stream_t stream,
-                       const unsigned char* uni_flags = nullptr, float* uni_acc = nullptr, void* mask_ws = nullptr,
-                       float* pool_out = nullptr, void* pool_rows = nullptr);
 
 static bool pool_ok_box(int TD, int TH, int TW, int D, int H, int W) {
     return TD == 8 && TH == 8 && TW == 4 && D % 8 == 0 && H % 8 == 0 && W % 4 == 0;
@@ -899,36 +857,10 @@ extern "C" int bfm_conv3x3x3_wino_pool_ok(int D, int H, int W, int passes) {
     return pool_ok_box(TD, TH, TW, D, H, W) ? 1 : 0;
 }
 
-// bfm_conv3x3x3_wino_ex that also writes nn.MaxPool3d(2) of its output (buildingblocks.py:185-186: what the next encoder
-// level reads) into pooled (D/2,H/2,W/2,Cout) and that tensor's moment rows [bfm_conv3x3x3_wino_rows()][Cout] into
-// pooled_rows (or NULL): out and moment_rows as bfm_conv3x3x3_wino_ex writes them, pooled the bits of bfm_maxpool2(out)
-extern "C" int bfm_conv3x3x3_wino_pool(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
-                                       const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope,
-                                       int passes, int flags, float* out, void* moment_rows, float* pooled,
-                                       void* pooled_rows, bfm_stream_t stream) {
-    if (!pooled) return BFM_E_ARG;
-    return wino_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows,
-                       nullptr, stream, nullptr, nullptr, nullptr, pooled, pooled_rows);
-}
-
-// the same for the uniform-box pair (bfm_conv3x3x3_wino_uniform)
-extern "C" int bfm_conv3x3x3_wino_uniform_pool(const float* A, int CA, int D, int H, int W, const float* scale,
-                                               const float* shift, const float* bound, int G, const void* wpacked,
-                                               int wexp, int Cout, float slope, int passes, int flags, float* out,
-                                               void* moment_rows, const unsigned char* uniform_flags, void* scratch,
-                                               float* pooled, void* pooled_rows, bfm_stream_t stream) {
-    if (!uniform_flags || !scratch || !pooled || (flags & ~1)) return BFM_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(uniform_flags) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return BFM_E_ARG;
-    return wino_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows,
-                       nullptr, stream, uniform_flags, static_cast<float*>(scratch), nullptr, pooled, pooled_rows);
-}
-
 extern "C" size_t bfm_uniform_boxes_bytes(int D, int H, int W, int passes) {
     int TD, TH, TW;
     if (D <= 0 || H <= 0 || W <= 0 || !choose_box(D, H, W, passes == 3 ? 2 : 1, TD, TH, TW)) return 0;
-    const size_t n = (size_t)bfm_cdiv(D, TD) * bfm_cdiv(H, TH) * bfm_cdiv(W, TW);
-    // flags, the first box of each of the 27 classes, the two counts, the two work lists (uniform_lists_kernel)
-    return ((n + 3) & ~(size_t)3) + 27 * 4 + 2 * 4 + 2 * n * 4;
+    return UniformFlagBuf::bytes((size_t)bfm_box_count(D, H, W, TD, TH, TW));
 }
 
 extern "C" int bfm_uniform_boxes_level(const float* image, int D, int H, int W, int level, int radius, int passes,
@@ -939,14 +871,13 @@ extern "C" int bfm_uniform_boxes_level(const float* image, int D, int H, int W, 
     int TD, TH, TW;
     if (d <= 0 || h <= 0 || w <= 0 || !choose_box(d, h, w, passes == 3 ? 2 : 1, TD, TH, TW)) return BFM_E_SHAPE;
     const int nTz = bfm_cdiv(d, TD), nTy = bfm_cdiv(h, TH), nTx = bfm_cdiv(w, TW);
-    const size_t n = (size_t)nTz * nTy * nTx;
-    int* first = reinterpret_cast<int*>(flags + ((n + 3) & ~(size_t)3));
+    const UniformFlagBuf fb{flags, (size_t)nTz * nTy * nTx};
     // a class is well defined when a box side outreaches the radius at its level (else a middle box could see a face)
     if ((TD << level) < radius || (TH << level) < radius || (TW << level) < radius) return BFM_E_SHAPE;
-    hipLaunchKernelGGL(uniform_boxes_kernel, dim3((unsigned)n), dim3(256), 0, bfm_s(stream), image, D, H, W, TD, TH, TW, nTz,
+    hipLaunchKernelGGL(uniform_boxes_kernel, dim3((unsigned)fb.n), dim3(256), 0, bfm_s(stream), image, D, H, W, TD, TH, TW, nTz,
                        nTy, nTx, level, radius, flags);
-    hipLaunchKernelGGL(uniform_lists_kernel, dim3(1), dim3(1024), 0, bfm_s(stream), flags, (int)n, first, first + 27,
-                       first + 29, first + 29 + (int)n);
+    hipLaunchKernelGGL(uniform_lists_kernel, dim3(1), dim3(1024), 0, bfm_s(stream), flags, (int)fb.n, fb.first(), fb.counts(),
+                       fb.rest_list(), fb.uniform_list());
     return bfm_launch_status();
 }
 
@@ -959,29 +890,130 @@ extern "C" size_t bfm_conv3x3x3_wino_uniform_scratch(int Cout) {
     return Cout > 0 && Cout % 64 == 0 ? (size_t)27 * (Cout / 64) * 2 * 16 * NTHR * 2 * sizeof(float) : 0;
 }
 
-extern "C" int bfm_conv3x3x3_wino_uniform(const float* A, int CA, int D, int H, int W, const float* scale,
-                                          const float* shift, const float* bound, int G, const void* wpacked, int wexp,
-                                          int Cout, float slope, int passes, int flags, float* out, void* moment_rows,
-                                          const unsigned char* uniform_flags, void* scratch, bfm_stream_t stream) {
-    if (!uniform_flags || !scratch || (flags & ~1)) return BFM_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(uniform_flags) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return BFM_E_ARG;
-    return wino_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows,
-                       nullptr, stream, uniform_flags, static_cast<float*>(scratch));
+extern "C" size_t bfm_conv3x3x3_wino_masked_workspace(int D, int H, int W, int passes) {
+    int TD, TH, TW;
+    if (D <= 0 || H <= 0 || W <= 0 || !choose_box(D, H, W, passes == 3 ? 2 : 1, TD, TH, TW)) return 0;
+    return MaskListBuf::bytes((size_t)bfm_box_count(D, H, W, TD, TH, TW));
+}
+
+static int wino_launch(const WinoLaunch& a) {
+    if (const int rc = bfm_wino_check(a, KC)) return rc;
+    const int D = a.D, H = a.H, W = a.W, Cout = a.Cout, passes = a.passes;
+    const int npl = passes == 3 ? 2 : 1;
+    WinoParams p{};
+    p.A = a.A; p.CA = a.CA; p.D = D; p.H = H; p.W = W;
+    p.scale = a.scale; p.shift = a.shift; p.bound = a.bound; p.G = a.G;
+    p.wp = static_cast<const uint4*>(a.wpacked);
+    p.wexp = a.wexp; p.Cout = Cout; p.slope = a.slope; p.out = a.out; p.accum = a.flags & 1;
+    p.mask_img = a.mask.img;
+    p.uni_flags = a.uniform.flags;
+    p.uni_acc = a.uniform.scratch;
+    if (!choose_box(D, H, W, npl, p.TD, p.TH, p.TW)) return BFM_E_SHAPE;
+    p.HT = p.TH + 2; p.PW = p.TW / 2;
+    p.pw_shift = ilog2i(p.PW); p.thp_shift = ilog2i(p.TH * p.PW);
+    const int nTz = bfm_cdiv(D, p.TD);
+    p.nTy = bfm_cdiv(H, p.TH); p.nTx = bfm_cdiv(W, p.TW);
+    p.nMt = nTz * p.nTy * p.nTx;
+    const UniformFlagBuf fb{a.uniform.flags, (size_t)p.nMt};
+    p.uni_first = fb.flags ? fb.first() : nullptr;
+    p.NT = Cout / 64;
+    p.KCN = a.CA / KC;
+    p.npos_lds = (p.TD + 2) * p.HT * p.PW;
+    p.plane_stride = ((p.npos_lds * 16 + 255) / 256) * 256 + 16;
+    size_t smem = (size_t)8 * npl * p.plane_stride;
+    const size_t epi = (size_t)4 * 128 * MLD * sizeof(float) + 6144;    // output-transform scratch + moment-row fold
+    if (smem < epi) smem = epi;
+    MomentRows rows, prows;
+    if (a.moment_rows && !rows.carve(a.moment_rows, (size_t)p.nMt * Cout)) return BFM_E_ARG;
+    rows.into(p);
+    if (a.pool.out) {                                          // the POOL kernels: box 8 x 8 x 4, every box inside the tensor
+        if (a.mask.img || !pool_ok_box(p.TD, p.TH, p.TW, D, H, W)) return BFM_E_SHAPE;
+        if (reinterpret_cast<uintptr_t>(a.pool.out) & 15) return BFM_E_ARG;
+        p.pool_out = a.pool.out;
+        if (a.pool.rows && !prows.carve(a.pool.rows, (size_t)p.nMt * Cout)) return BFM_E_ARG;
+        p.prsum = prows.rsum; p.prsq = prows.rsq; p.prmn = prows.rmn; p.prmx = prows.rmx;
+    } else if (a.pool.rows) return BFM_E_ARG;
+    if ((int64_t)p.nMt * p.NT > 0x7fffffff) return BFM_E_SHAPE;
+    if (smem > 80 * 1024) return BFM_E_SHAPE;
+    static bool attr_done = false;
+    if (const int rc = bfm_raise_lds_limit(
+            attr_done,
+            {bfm_kernel(&conv_wino_pool<3>), bfm_kernel(&conv_wino_pool<1>), bfm_kernel(&conv_wino_rest_pool<3>),
+             bfm_kernel(&conv_wino_rest_pool<1>), bfm_kernel(&conv_wino<3>), bfm_kernel(&conv_wino<1>),
+             bfm_kernel(&conv_wino_masked<3>), bfm_kernel(&conv_wino_masked<1>), bfm_kernel(&conv_wino_uniform<3>),
+             bfm_kernel(&conv_wino_uniform<1>), bfm_kernel(&conv_wino_rest<3>), bfm_kernel(&conv_wino_rest<1>)},
+            80 * 1024))
+        return rc;
+    const dim3 grid((unsigned)(p.nMt * p.NT)), block(NTHR);
+    hipStream_t st = bfm_s(a.stream);
+    // the sparse forms take their boxes from a list built on the device; workgroups beyond the list end at once
+    if (a.mask.img) {
+        if (!a.mask.ws) return BFM_E_ARG;
+        const MaskListBuf mb{a.mask.ws, (size_t)p.nMt};
+        if (const int rc = bfm_wino_mask_list(a.mask.img, D, H, W, p.TD, p.TH, p.TW, p.nTy, p.nTx, p.nMt, a.mask.ws, a.stream))
+            return rc;
+        p.list = mb.list(); p.list_n = mb.count();
+        bfm_launch_by_passes(passes, conv_wino_masked<3>, conv_wino_masked<1>, grid, block, smem, st, p);
+        return bfm_launch_status();
+    }
+    if (fb.flags) {                                            // disjoint boxes: the two launches may overlap
+        p.list = fb.rest_list(); p.list_n = fb.counts();
+        if (a.pool.out) bfm_launch_by_passes(passes, conv_wino_rest_pool<3>, conv_wino_rest_pool<1>, grid, block, smem, st, p);
+        else bfm_launch_by_passes(passes, conv_wino_rest<3>, conv_wino_rest<1>, grid, block, smem, st, p);
+        p.list = fb.uniform_list(); p.list_n = fb.counts() + 1;
+        // conv_wino_uniform's LDS: its row fold; with the pooling, the windows' exchange and the pooled rows' fold behind it
+        if (a.pool.out) bfm_launch_by_passes(passes, conv_wino_uniform_pool<3>, conv_wino_uniform_pool<1>, grid, block, 20480, st, p);
+        else bfm_launch_by_passes(passes, conv_wino_uniform<3>, conv_wino_uniform<1>, grid, block, 6144, st, p);
+        return bfm_launch_status();
+    }
+    if (a.pool.out) bfm_launch_by_passes(passes, conv_wino_pool<3>, conv_wino_pool<1>, grid, block, smem, st, p);
+    else bfm_launch_by_passes(passes, conv_wino<3>, conv_wino<1>, grid, block, smem, st, p);
+    return bfm_launch_status();
 }
 
 extern "C" int bfm_conv3x3x3_wino_ex(const float* A, int CA, int D, int H, int W, const float* scale,
                                      const float* shift, const float* bound, int G, const void* wpacked, int wexp,
                                      int Cout, float slope, int passes, int flags, float* out, void* moment_rows,
                                      bfm_stream_t stream) {
-    return wino_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows,
-                       nullptr, stream);
+    return wino_launch({A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream});
 }
 
-extern "C" size_t bfm_conv3x3x3_wino_masked_workspace(int D, int H, int W, int passes) {
-    int TD, TH, TW;
-    if (D <= 0 || H <= 0 || W <= 0 || !choose_box(D, H, W, passes == 3 ? 2 : 1, TD, TH, TW)) return 0;
-    const size_t n = (size_t)bfm_cdiv(D, TD) * bfm_cdiv(H, TH) * bfm_cdiv(W, TW);
-    return ((n + 3) & ~(size_t)3) + 4 + n * 4;                 // box activity bytes, the count, the list
+// bfm_conv3x3x3_wino_ex that also writes nn.MaxPool3d(2) of its output (buildingblocks.py:185-186: what the next encoder
+// level reads) into pooled (D/2,H/2,W/2,Cout) and that tensor's moment rows [bfm_conv3x3x3_wino_rows()][Cout] into
+// pooled_rows (or NULL): out and moment_rows as bfm_conv3x3x3_wino_ex writes them, pooled the bits of bfm_maxpool2(out)
+extern "C" int bfm_conv3x3x3_wino_pool(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
+                                       const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope,
+                                       int passes, int flags, float* out, void* moment_rows, float* pooled,
+                                       void* pooled_rows, bfm_stream_t stream) {
+    if (!pooled) return BFM_E_ARG;
+    WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
+    a.pool = {pooled, pooled_rows};
+    return wino_launch(a);
+}
+
+extern "C" int bfm_conv3x3x3_wino_uniform(const float* A, int CA, int D, int H, int W, const float* scale,
+                                          const float* shift, const float* bound, int G, const void* wpacked, int wexp,
+                                          int Cout, float slope, int passes, int flags, float* out, void* moment_rows,
+                                          const unsigned char* uniform_flags, void* scratch, bfm_stream_t stream) {
+    if (!uniform_flags || !scratch || (flags & ~1)) return BFM_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(uniform_flags) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return BFM_E_ARG;
+    WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
+    a.uniform = {uniform_flags, static_cast<float*>(scratch)};
+    return wino_launch(a);
+}
+
+// the same with the pooling fused (bfm_conv3x3x3_wino_pool)
+extern "C" int bfm_conv3x3x3_wino_uniform_pool(const float* A, int CA, int D, int H, int W, const float* scale,
+                                               const float* shift, const float* bound, int G, const void* wpacked,
+                                               int wexp, int Cout, float slope, int passes, int flags, float* out,
+                                               void* moment_rows, const unsigned char* uniform_flags, void* scratch,
+                                               float* pooled, void* pooled_rows, bfm_stream_t stream) {
+    if (!uniform_flags || !scratch || !pooled || (flags & ~1)) return BFM_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(uniform_flags) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return BFM_E_ARG;
+    WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
+    a.uniform = {uniform_flags, static_cast<float*>(scratch)};
+    a.pool = {pooled, pooled_rows};
+    return wino_launch(a);
 }
 
 extern "C" int bfm_conv3x3x3_wino_masked(const float* A, int CA, int D, int H, int W, const float* scale,
@@ -993,137 +1025,7 @@ extern "C" int bfm_conv3x3x3_wino_masked(const float* A, int CA, int D, int H, i
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3) ||
         workspace_bytes < bfm_conv3x3x3_wino_masked_workspace(D, H, W, passes))
         return BFM_E_ARG;
-    return wino_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, nullptr,
-                       mask_image, stream, nullptr, nullptr, workspace);
-}
-
-static int wino_launch(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
-                       const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes, int flags,
-                       float* out, void* moment_rows, const float* mask_img, bfm_stream_t stream,
-                       const unsigned char* uni_flags, float* uni_acc, void* mask_ws, float* pool_out, void* pool_rows) {
-    const int accumulate = flags & 1;
-    if (flags & ~1) return BFM_E_ARG;                           // bit 0 = accumulate; nothing else is defined
-    if (!A || CA <= 0 || D <= 0 || H <= 0 || W <= 0 || !scale || !shift || !bound || G <= 0 || !wpacked || !out)
-        return BFM_E_ARG;
-    if (CA % KC || Cout % 64 || Cout <= 0) return BFM_E_SHAPE;
-    if (passes != 1 && passes != 3) return BFM_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(scale) & 15) ||
-        (reinterpret_cast<uintptr_t>(shift) & 15) || (reinterpret_cast<uintptr_t>(wpacked) & 15) ||
-        (reinterpret_cast<uintptr_t>(out) & 15))
-        return BFM_E_ARG;
-    if ((int64_t)D * H * W * CA > 0x7fffffffLL) return BFM_E_SHAPE;       // 32-bit staging offsets
-    const int npl = passes == 3 ? 2 : 1;
-    WinoParams p{};
-    p.A = A; p.CA = CA; p.D = D; p.H = H; p.W = W;
-    p.scale = scale; p.shift = shift; p.bound = bound; p.G = G;
-    p.wp = static_cast<const uint4*>(wpacked);
-    p.wexp = wexp; p.Cout = Cout; p.slope = slope; p.out = out; p.accum = accumulate ? 1 : 0;
-    p.mask_img = mask_img;
-    p.uni_flags = uni_flags;
-    p.uni_acc = uni_acc;
-    if (!choose_box(D, H, W, npl, p.TD, p.TH, p.TW)) return BFM_E_SHAPE;
-    p.HT = p.TH + 2; p.PW = p.TW / 2;
-    p.pw_shift = ilog2i(p.PW); p.thp_shift = ilog2i(p.TH * p.PW);
-    const int nTz = bfm_cdiv(D, p.TD);
-    p.nTy = bfm_cdiv(H, p.TH); p.nTx = bfm_cdiv(W, p.TW);
-    p.nMt = nTz * p.nTy * p.nTx;
-    p.uni_first = uni_flags ? reinterpret_cast<const int*>(uni_flags + (((size_t)p.nMt + 3) & ~(size_t)3)) : nullptr;
-    p.NT = Cout / 64;
-    p.KCN = CA / KC;
-    p.npos_lds = (p.TD + 2) * p.HT * p.PW;
-    p.plane_stride = ((p.npos_lds * 16 + 255) / 256) * 256 + 16;
-    size_t smem = (size_t)8 * npl * p.plane_stride;
-    const size_t epi = (size_t)4 * 128 * MLD * sizeof(float) + 6144;    // output-transform scratch + moment-row fold
-    if (smem < epi) smem = epi;
-    if (moment_rows) {
-        if (reinterpret_cast<uintptr_t>(moment_rows) & 7) return BFM_E_ARG;
-        char* rb = static_cast<char*>(moment_rows);
-        const size_t n = (size_t)p.nMt * Cout;
-        p.rsum = reinterpret_cast<double*>(rb);
-        p.rsq = reinterpret_cast<double*>(rb + n * 8);
-        p.rmn = reinterpret_cast<float*>(rb + n * 16);
-        p.rmx = reinterpret_cast<float*>(rb + n * 20);
-    }
-    if (pool_out) {                                            // the POOL kernels: box 8 x 8 x 4, every box inside the tensor
-        if (mask_img || !pool_ok_box(p.TD, p.TH, p.TW, D, H, W)) return BFM_E_SHAPE;
-        if (reinterpret_cast<uintptr_t>(pool_out) & 15) return BFM_E_ARG;
-        p.pool_out = pool_out;
-        if (pool_rows) {
-            if (reinterpret_cast<uintptr_t>(pool_rows) & 7) return BFM_E_ARG;
-            char* rb = static_cast<char*>(pool_rows);
-            const size_t n = (size_t)p.nMt * Cout;
-            p.prsum = reinterpret_cast<double*>(rb);
-            p.prsq = reinterpret_cast<double*>(rb + n * 8);
-            p.prmn = reinterpret_cast<float*>(rb + n * 16);
-            p.prmx = reinterpret_cast<float*>(rb + n * 20);
-        }
-    } else if (pool_rows) return BFM_E_ARG;
-    if ((int64_t)p.nMt * p.NT > 0x7fffffff) return BFM_E_SHAPE;
-    if (smem > 80 * 1024) return BFM_E_SHAPE;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_pool<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_pool<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_rest_pool<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_rest_pool<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_masked<3>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_masked<1>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_uniform<3>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_uniform<1>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_rest<3>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_rest<1>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        attr_done = true;
-    }
-    dim3 grid((unsigned)(p.nMt * p.NT));
-    // the sparse forms take their boxes from a list built on the device; workgroups beyond the list end at once
-    if (mask_img) {
-        if (!mask_ws) return BFM_E_ARG;
-        unsigned char* act = static_cast<unsigned char*>(mask_ws);
-        int* cnt = reinterpret_cast<int*>(act + (((size_t)p.nMt + 3) & ~(size_t)3));
-        hipLaunchKernelGGL(wino_box_active_kernel, dim3((unsigned)bfm_cdiv(p.nMt, 4)), dim3(256), 0, bfm_s(stream), mask_img,
-                           D, H, W, p.TD, p.TH, p.TW, p.nTy, p.nTx, p.nMt, act);
-        hipLaunchKernelGGL(wino_mask_list_kernel, dim3(1), dim3(1024), 0, bfm_s(stream), act, p.nMt, cnt + 1, cnt);
-        p.list = cnt + 1; p.list_n = cnt;
-        if (passes == 3) hipLaunchKernelGGL(conv_wino_masked<3>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-        else hipLaunchKernelGGL(conv_wino_masked<1>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-        return bfm_launch_status();
-    }
-    if (uni_flags && pool_out) {
-        const int* cnt = p.uni_first + 27;
-        p.list = cnt + 2; p.list_n = cnt;
-        if (passes == 3) hipLaunchKernelGGL(conv_wino_rest_pool<3>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-        else hipLaunchKernelGGL(conv_wino_rest_pool<1>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-        p.list = cnt + 2 + p.nMt; p.list_n = cnt + 1;
-        if (passes == 3) hipLaunchKernelGGL(conv_wino_uniform_pool<3>, grid, dim3(NTHR), 20480, bfm_s(stream), p);
-        else hipLaunchKernelGGL(conv_wino_uniform_pool<1>, grid, dim3(NTHR), 20480, bfm_s(stream), p);
-        return bfm_launch_status();
-    }
-    if (pool_out) {
-        if (passes == 3) hipLaunchKernelGGL(conv_wino_pool<3>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-        else hipLaunchKernelGGL(conv_wino_pool<1>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-        return bfm_launch_status();
-    }
-    if (uni_flags) {                                           // disjoint boxes: the two launches may overlap
-        const int* cnt = p.uni_first + 27;                     // uniform_lists_kernel: the two counts, then the two lists
-        p.list = cnt + 2; p.list_n = cnt;
-        if (passes == 3) hipLaunchKernelGGL(conv_wino_rest<3>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-        else hipLaunchKernelGGL(conv_wino_rest<1>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-        p.list = cnt + 2 + p.nMt; p.list_n = cnt + 1;
-        if (passes == 3) hipLaunchKernelGGL(conv_wino_uniform<3>, grid, dim3(NTHR), 6144, bfm_s(stream), p);
-        else hipLaunchKernelGGL(conv_wino_uniform<1>, grid, dim3(NTHR), 6144, bfm_s(stream), p);
-        return bfm_launch_status();
-    }
-    if (passes == 3) hipLaunchKernelGGL(conv_wino<3>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-    else hipLaunchKernelGGL(conv_wino<1>, grid, dim3(NTHR), smem, bfm_s(stream), p);
-    return bfm_launch_status();
+    WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, nullptr, stream};
+    a.mask = {mask_image, workspace};
+    return wino_launch(a);
 }

@@ -28,7 +28,6 @@
 // per (quad, cout) forms y0..y3, dequantises, optionally adds what `out` holds (accumulate mode), applies LeakyReLU and
 // stores.  Single-source inputs only, no split-K; the dense form and the masked form over the boxes the tile mask keeps
 // (conv_wino4_masked, the tile loop's last convolution); the uniform-box pair stays with F(2,3) (engine._needs_f23).
-#include "bfm_common.h"
 #include "wino_shared.h"
 #include <cstdlib>
 #include <type_traits>
@@ -73,24 +72,6 @@ struct W4Params {
     int dbg_sleep;                   // diagnostics builds: the first round's odd wave slots start this many kilocycles late
 };
 
-__device__ __forceinline__ int row_perm(int l) {        // as conv_mfma: each 16-lane b128 group reads 16 consecutive positions
-    if (l < 4) return l;
-    if (l < 12) return l + 12;
-    if (l < 16) return l - 8;
-    if (l < 20) return l + 8;
-    if (l < 28) return l - 12;
-    return l;
-}
-
-__device__ __forceinline__ int row_unperm(int q) {      // inverse of row_perm
-    if (q < 4) return q;
-    if (q < 8) return q + 8;
-    if (q < 16) return q + 12;
-    if (q < 24) return q - 12;
-    if (q < 28) return q - 8;
-    return q;
-}
-
 __device__ __forceinline__ void quad_coords(const W4Params& p, int q, int& d, int& h, int& j) {
     d = q >> p.thq_shift;
     const int rem = q & ((1 << p.thq_shift) - 1);
@@ -99,6 +80,7 @@ __device__ __forceinline__ void quad_coords(const W4Params& p, int q, int& d, in
 }
 
 // x = hi + lo in fp16 for four values, two per instruction (truncation: x - hi is exact in fp32)
+// (not in conv_shared.h: conv3d_wino.hip's split_store4 rounds lo to nearest with v_fma_mix, this one truncates it too)
 template <bool LO>
 __device__ __forceinline__ void split_store4(const float (&t)[4], unsigned char* dp, int plane_stride) {
     const fp16x2_t h01 = __builtin_amdgcn_cvt_pkrtz(t[0], t[1]);
@@ -1103,7 +1085,7 @@ extern "C" int bfm_pack_conv_weights_wino4(const float* w_oidhw, int Cin, int Co
 extern "C" int bfm_conv3x3x3_wino4_rows(int D, int H, int W, int passes) {
     int TD, TH, TW;
     if (D <= 0 || H <= 0 || W <= 0 || !choose_box_any(D, H, W, passes == 3 ? 2 : 1, TD, TH, TW)) return 0;
-    return bfm_cdiv(D, TD) * bfm_cdiv(H, TH) * bfm_cdiv(W, TW);
+    return (int)bfm_box_count(D, H, W, TD, TH, TW);
 }
 
 // the box of output voxels per workgroup for this volume (what the masked form's "boxes that hold input" are)
@@ -1114,34 +1096,23 @@ extern "C" int bfm_conv3x3x3_wino4_box(int D, int H, int W, int passes, int* box
     return BFM_OK;
 }
 
-// bytes of the masked form's workspace: box activity (padded to 4), the count, the list
+// bytes of the masked form's workspace (MaskListBuf)
 extern "C" size_t bfm_conv3x3x3_wino4_masked_workspace(int D, int H, int W, int passes) {
     const int n = bfm_conv3x3x3_wino4_rows(D, H, W, passes);
     if (n <= 0) return 0;
-    return (((size_t)n + 3) & ~(size_t)3) + 4 + (size_t)n * 4;
+    return MaskListBuf::bytes((size_t)n);
 }
 
-static int w4_launch(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift, const float* bound,
-                     int G, const void* wpacked, int wexp, int Cout, float slope, int passes, int flags, float* out,
-                     void* moment_rows, const float* mask_img, void* mask_ws, bfm_stream_t stream, int S = 1,
-                     int affine_stride = 0, const unsigned char* uni_flags = nullptr, float* uni_acc = nullptr) {
-    const int accumulate = flags & 1;
-    if (flags & ~1) return BFM_E_ARG;                           // bit 0 = accumulate; nothing else is defined
-    if (!A || CA <= 0 || D <= 0 || H <= 0 || W <= 0 || !scale || !shift || !bound || G <= 0 || !wpacked || !out)
-        return BFM_E_ARG;
-    if (CA % KC || Cout % 64 || Cout <= 0) return BFM_E_SHAPE;
-    if (passes != 1 && passes != 3) return BFM_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(scale) & 15) ||
-        (reinterpret_cast<uintptr_t>(shift) & 15) || (reinterpret_cast<uintptr_t>(wpacked) & 15) ||
-        (reinterpret_cast<uintptr_t>(out) & 15))
-        return BFM_E_ARG;
-    if ((int64_t)D * H * W * CA > 0x7fffffffLL) return BFM_E_SHAPE;       // 32-bit staging offsets
+static int w4_launch(const WinoLaunch& a) {
+    if (const int rc = bfm_wino_check(a, KC)) return rc;
+    const int D = a.D, H = a.H, W = a.W, CA = a.CA, Cout = a.Cout, passes = a.passes;
+    const int S = a.batch.S, affine_stride = a.batch.affine_stride;
     const int npl = passes == 3 ? 2 : 1;
     W4Params p{};
-    p.A = A; p.CA = CA; p.D = D; p.H = H; p.W = W;
-    p.scale = scale; p.shift = shift; p.bound = bound; p.G = G;
-    p.wp = static_cast<const uint4*>(wpacked);
-    p.wexp = wexp; p.Cout = Cout; p.slope = slope; p.out = out; p.accum = accumulate ? 1 : 0;
+    p.A = a.A; p.CA = CA; p.D = D; p.H = H; p.W = W;
+    p.scale = a.scale; p.shift = a.shift; p.bound = a.bound; p.G = a.G;
+    p.wp = static_cast<const uint4*>(a.wpacked);
+    p.wexp = a.wexp; p.Cout = Cout; p.slope = a.slope; p.out = a.out; p.accum = a.flags & 1;
     if (!choose_box_any(D, H, W, npl, p.TD, p.TH, p.TW)) return BFM_E_SHAPE;
     const bool dma = use_dma_kernel(D, H, W);
     if (dma && (int64_t)(DB_TD + 2) * H * W * CA >= (int64_t)1 << 30) return BFM_E_SHAPE;   // 32-bit byte offsets in a slab
@@ -1151,7 +1122,7 @@ static int w4_launch(const float* A, int CA, int D, int H, int W, const float* s
     p.nTy = bfm_cdiv(H, p.TH); p.nTx = bfm_cdiv(W, p.TW);
     p.nMt = nTz * p.nTy * p.nTx;
     if (S > 1 || affine_stride > 0) {                           // batch of S same-shape samples
-        if (mask_img || S < 1 || (affine_stride != 0 && (affine_stride < CA || (affine_stride & 3)))) return BFM_E_ARG;
+        if (a.mask.img || S < 1 || (affine_stride != 0 && (affine_stride < CA || (affine_stride & 3)))) return BFM_E_ARG;
         p.nMtS = p.nMt;
         p.nMt = S * p.nMtS;
         p.saff = affine_stride > 0 ? affine_stride : CA;
@@ -1166,63 +1137,45 @@ static int w4_launch(const float* A, int CA, int D, int H, int W, const float* s
     const size_t epi = (size_t)NPOS * 64 * MLD * sizeof(float) + (size_t)NRG * 32 * 24;   // output-transform scratch + moment fold
     if (smem < epi) smem = epi;
     if (smem > (dma ? 80u : 64u) * 1024) return BFM_E_SHAPE;
-    if (uni_flags) {                                            // the pair: conv_wino4d only, on conv_wino's box grid
+    const UniformFlagBuf fb{a.uniform.flags, (size_t)p.nMt};    // (one sample's boxes: the pair takes no batch)
+    if (fb.flags) {                                             // the pair: conv_wino4d only, on conv_wino's box grid
         int bd, bh, bw;
-        if (!dma || mask_img || S > 1 || affine_stride > 0 || !uni_acc) return BFM_E_ARG;
+        if (!dma || a.mask.img || S > 1 || affine_stride > 0 || !a.uniform.scratch) return BFM_E_ARG;
         if (!bfm_wino_choose_box(D, H, W, npl, bd, bh, bw) || bd != p.TD || bh != p.TH || bw != p.TW) return BFM_E_SHAPE;
-        p.uni_flags = uni_flags;
-        p.uni_acc = uni_acc;
+        p.uni_flags = fb.flags;
+        p.uni_acc = a.uniform.scratch;
     }
-    if (dma) {                                                  // more than 64 KB of dynamic LDS: once per process
+    if (dma) {                                                  // more than 64 KB of dynamic LDS
         static bool attr = false;
-        if (!attr) {
-            const int lim = 80 * 1024;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4d_rest<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4d_rest<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess)
-                return BFM_E_LAUNCH;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4d<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4d<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4d_masked<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4d_masked<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess)
-                return BFM_E_LAUNCH;
-            attr = true;
-        }
+        if (const int rc = bfm_raise_lds_limit(
+                attr,
+                {bfm_kernel(&conv_wino4d_rest<3>), bfm_kernel(&conv_wino4d_rest<1>), bfm_kernel(&conv_wino4d<3>),
+                 bfm_kernel(&conv_wino4d<1>), bfm_kernel(&conv_wino4d_masked<3>), bfm_kernel(&conv_wino4d_masked<1>)},
+                80 * 1024))
+            return rc;
     }
-    if (moment_rows) {
-        if (reinterpret_cast<uintptr_t>(moment_rows) & 7) return BFM_E_ARG;
-        char* rb = static_cast<char*>(moment_rows);
-        const size_t n = (size_t)p.nMt * Cout;
-        p.rsum = reinterpret_cast<double*>(rb);
-        p.rsq = reinterpret_cast<double*>(rb + n * 8);
-        p.rmn = reinterpret_cast<float*>(rb + n * 16);
-        p.rmx = reinterpret_cast<float*>(rb + n * 20);
-    }
+    MomentRows rows;
+    if (a.moment_rows && !rows.carve(a.moment_rows, (size_t)p.nMt * Cout)) return BFM_E_ARG;
+    rows.into(p);
     if ((int64_t)p.nMt * p.NT > 0x7fffffff) return BFM_E_SHAPE;
-    dim3 grid((unsigned)(p.nMt * p.NT));
-    hipStream_t st = bfm_s(stream);
+    const dim3 grid((unsigned)(p.nMt * p.NT)), block(NTHR);
+    hipStream_t st = bfm_s(a.stream);
     // the sparse forms take their boxes from a list built on the device; workgroups beyond the list end at once
-    if (mask_img) {
-        if (!mask_ws) return BFM_E_ARG;
-        const int rc = bfm_wino_mask_list(mask_img, D, H, W, p.TD, p.TH, p.TW, p.nTy, p.nTx, p.nMt, mask_ws, stream);
-        if (rc != BFM_OK) return rc;
-        int* cnt = reinterpret_cast<int*>(static_cast<unsigned char*>(mask_ws) + (((size_t)p.nMt + 3) & ~(size_t)3));
-        p.list = cnt + 1; p.list_n = cnt;
-        if (dma) {
-            if (passes == 3) hipLaunchKernelGGL(conv_wino4d_masked<3>, grid, dim3(NTHR), smem, st, p);
-            else hipLaunchKernelGGL(conv_wino4d_masked<1>, grid, dim3(NTHR), smem, st, p);
-        } else if (passes == 3) hipLaunchKernelGGL(conv_wino4_masked<3>, grid, dim3(NTHR), smem, st, p);
-        else hipLaunchKernelGGL(conv_wino4_masked<1>, grid, dim3(NTHR), smem, st, p);
+    if (a.mask.img) {
+        if (!a.mask.ws) return BFM_E_ARG;
+        const MaskListBuf mb{a.mask.ws, (size_t)p.nMt};
+        if (const int rc = bfm_wino_mask_list(a.mask.img, D, H, W, p.TD, p.TH, p.TW, p.nTy, p.nTx, p.nMt, a.mask.ws, a.stream))
+            return rc;
+        p.list = mb.list(); p.list_n = mb.count();
+        if (dma) bfm_launch_by_passes(passes, conv_wino4d_masked<3>, conv_wino4d_masked<1>, grid, block, smem, st, p);
+        else bfm_launch_by_passes(passes, conv_wino4_masked<3>, conv_wino4_masked<1>, grid, block, smem, st, p);
         return bfm_launch_status();
     }
-    if (uni_flags) {                                            // disjoint boxes: the two launches may overlap
-        // flags [nMt pad 4] | first box of each class [27] | the two counts | conv_wino4d_rest's list | conv_wino4d_uniform's
-        const int* cnt = reinterpret_cast<const int*>(uni_flags + (((size_t)p.nMt + 3) & ~(size_t)3)) + 27;
-        p.list = cnt + 2; p.list_n = cnt;
-        if (passes == 3) hipLaunchKernelGGL(conv_wino4d_rest<3>, grid, dim3(NTHR), smem, st, p);
-        else hipLaunchKernelGGL(conv_wino4d_rest<1>, grid, dim3(NTHR), smem, st, p);
-        p.list = cnt + 2 + p.nMt; p.list_n = cnt + 1;
-        if (passes == 3) hipLaunchKernelGGL(conv_wino4d_uniform<3>, grid, dim3(NTHR), 6144, st, p);
-        else hipLaunchKernelGGL(conv_wino4d_uniform<1>, grid, dim3(NTHR), 6144, st, p);
+    if (fb.flags) {                                             // disjoint boxes: the two launches may overlap
+        p.list = fb.rest_list(); p.list_n = fb.counts();
+        bfm_launch_by_passes(passes, conv_wino4d_rest<3>, conv_wino4d_rest<1>, grid, block, smem, st, p);
+        p.list = fb.uniform_list(); p.list_n = fb.counts() + 1;
+        bfm_launch_by_passes(passes, conv_wino4d_uniform<3>, conv_wino4d_uniform<1>, grid, block, 6144, st, p);
         return bfm_launch_status();
     }
 #ifdef BFM_W4_ABLATE
@@ -1240,19 +1193,15 @@ static int w4_launch(const float* A, int CA, int D, int H, int W, const float* s
         }
     }
 #endif
-    if (dma) {
-        if (passes == 3) hipLaunchKernelGGL(conv_wino4d<3>, grid, dim3(NTHR), smem, st, p);
-        else hipLaunchKernelGGL(conv_wino4d<1>, grid, dim3(NTHR), smem, st, p);
-    } else if (passes == 3) hipLaunchKernelGGL(conv_wino4<3>, grid, dim3(NTHR), smem, st, p);
-    else hipLaunchKernelGGL(conv_wino4<1>, grid, dim3(NTHR), smem, st, p);
+    if (dma) bfm_launch_by_passes(passes, conv_wino4d<3>, conv_wino4d<1>, grid, block, smem, st, p);
+    else bfm_launch_by_passes(passes, conv_wino4<3>, conv_wino4<1>, grid, block, smem, st, p);
     return bfm_launch_status();
 }
 
 extern "C" int bfm_conv3x3x3_wino4(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
                                    const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope,
                                    int passes, int flags, float* out, void* moment_rows, bfm_stream_t stream) {
-    return w4_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows,
-                     nullptr, nullptr, stream);
+    return w4_launch({A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream});
 }
 
 // A (S,D,H,W,CA) -> out (S,D,H,W,Cout): S same-shape samples in one launch, per-sample scale / shift (rows affine_stride
@@ -1263,8 +1212,9 @@ extern "C" int bfm_conv3x3x3_wino4_batch(const float* A, int CA, int S, int D, i
                                          int Cout, float slope, int passes, int flags, float* out, void* moment_rows,
                                          int affine_stride, bfm_stream_t stream) {
     if (S < 1) return BFM_E_ARG;
-    return w4_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows,
-                     nullptr, nullptr, stream, S, affine_stride > 0 ? affine_stride : CA);
+    WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
+    a.batch = {S, affine_stride > 0 ? affine_stride : CA};
+    return w4_launch(a);
 }
 
 // the tile loop's last convolution (boxes that hold input only); workspace: bfm_conv3x3x3_wino_masked_workspace() bytes
@@ -1276,8 +1226,9 @@ extern "C" int bfm_conv3x3x3_wino4_masked(const float* A, int CA, int D, int H, 
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3) ||
         workspace_bytes < bfm_conv3x3x3_wino4_masked_workspace(D, H, W, passes))
         return BFM_E_ARG;
-    return w4_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, nullptr,
-                     mask_image, workspace, stream);
+    WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, nullptr, stream};
+    a.mask = {mask_image, workspace};
+    return w4_launch(a);
 }
 
 // The uniform-box pair of the same kernel (bfm_conv3x3x3_wino_uniform's counterpart: same flags from bfm_uniform_boxes,
@@ -1294,6 +1245,7 @@ extern "C" int bfm_conv3x3x3_wino4_uniform(const float* A, int CA, int D, int H,
                                            const unsigned char* uniform_flags, void* scratch, bfm_stream_t stream) {
     if (!uniform_flags || !scratch || (reinterpret_cast<uintptr_t>(uniform_flags) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 15))
         return BFM_E_ARG;
-    return w4_launch(A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows,
-                     nullptr, nullptr, stream, 1, 0, uniform_flags, static_cast<float*>(scratch));
+    WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
+    a.uniform = {uniform_flags, static_cast<float*>(scratch)};
+    return w4_launch(a);
 }

@@ -115,17 +115,6 @@ __global__ void fake_cortical(const float* __restrict__ d, int64_t rs, int nd, f
     }
 }
 
-// encode_pathology (Generator/datasets.py:496-518): I + Pprob * (mu[round(P)] + sigma[round(P)] * randn), clamp >= 0
-__global__ void pathology_encode(const float* __restrict__ I, const float* __restrict__ P,
-                                 const float* __restrict__ Pprob, const float* __restrict__ rn, float mu0, float mu1,
-                                 float s0, float s1, int64_t n, float* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool one = rintf(P[i]) >= 1.f;
-        const float v = I[i] + Pprob[i] * ((one ? mu1 : mu0) + (one ? s1 : s0) * rn[i]);
-        out[i] = v < 0.f ? 0.f : v;
-    }
-}
-
 // max |x| over `rows` runs of `len` floats, `row_stride` apart (a contiguous tensor: one row), folded into *out with an
 // integer atomicMax on the bit pattern (non-negative floats order like unsigned integers; *out starts at +0): one launch,
 // any order.  NaNs do not take part (fmaxf), as max |w| of finite weights is what the callers want.
@@ -168,14 +157,6 @@ extern "C" int bfm_absmax_f32(const float* x, int64_t rows, int64_t len, int64_t
     const int gy = (int)std::min<int64_t>(rows, std::max<int64_t>(1, 2048 / gx));
     hipLaunchKernelGGL(absmax_kernel, dim3(gx, gy), dim3(256), 0, bfm_s(stream), x, rows, len, row_stride,
                        reinterpret_cast<unsigned*>(out_zeroed));
-    return bfm_launch_status();
-}
-
-extern "C" int bfm_pathology_encode(const float* I, const float* P, const float* Pprob, const float* randn, float mu0,
-                                    float mu1, float s0, float s1, int64_t n, float* out, bfm_stream_t stream) {
-    if (!I || !P || !Pprob || !randn || !out || n <= 0) return BFM_E_ARG;
-    hipLaunchKernelGGL(pathology_encode, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), I, P, Pprob, randn, mu0, mu1, s0,
-                       s1, n, out);
     return bfm_launch_status();
 }
 

@@ -161,15 +161,6 @@ __global__ void divide_multi_kernel(float* __restrict__ full, const float* __res
     }
 }
 
-// tile output * (tile_input != 0), flattened (what a rank ships to rank 0)
-__global__ void mask_kernel(const float* __restrict__ tile, const int64_t* __restrict__ tile_label,
-                            const float* __restrict__ tin, int64_t n, float* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool m = tin[i] != 0.f;
-        out[i] = !m ? 0.f : (tile_label ? (float)(int)(float)tile_label[i] : tile[i]);
-    }
-}
-
 __global__ void count_add_kernel(float* __restrict__ cnt, int H, int W, int z0, int z1, int y0, int y1, int x0,
                                  int x1) {
     const int tw = x1 - x0, th = y1 - y0, td = z1 - z0;
@@ -181,11 +172,6 @@ __global__ void count_add_kernel(float* __restrict__ cnt, int H, int W, int z0, 
         int z = (int)(t / th);
         cnt[((int64_t)(z0 + z) * H + (y0 + y)) * W + (x0 + x)] += 1.f;
     }
-}
-
-__global__ void divide_kernel(float* __restrict__ full, const float* __restrict__ cnt, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        full[i] = full[i] / cnt[i];
 }
 
 // The whole stitch of the multi-GPU path in one launch (scripts/demo_test.py:108-119): every tile's K masked rows are
@@ -603,13 +589,6 @@ extern "C" int bfm_stitch_accumulate_multi(const float* maps, int64_t map_stride
     return bfm_launch_status();
 }
 
-extern "C" int bfm_mask_tile(const float* tile, const int64_t* tile_label, const float* tile_input, int64_t n,
-                             float* out, bfm_stream_t stream) {
-    if ((!tile && !tile_label) || !tile_input || !out || n <= 0) return BFM_E_ARG;
-    hipLaunchKernelGGL(mask_kernel, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), tile, tile_label, tile_input, n, out);
-    return bfm_launch_status();
-}
-
 extern "C" int bfm_tile_count_add(float* cnt, int D, int H, int W, int z0, int z1, int y0, int y1, int x0, int x1,
                                   bfm_stream_t stream) {
     if (!cnt) return BFM_E_ARG;
@@ -654,12 +633,6 @@ extern "C" int bfm_stitch_gather_compact(const int64_t* tiles, int T, int K, con
     const int nb = (int)(lines > 65536 ? 65536 : lines);
     hipLaunchKernelGGL(stitch_gather_compact_kernel, dim3(nb), dim3(256), (size_t)T * sizeof(LineTileC), bfm_s(stream), tiles,
                        T, K, volume, full, D, H, W);
-    return bfm_launch_status();
-}
-
-extern "C" int bfm_divide_by_count(float* full, const float* cnt, int64_t n, bfm_stream_t stream) {
-    if (!full || !cnt || n <= 0) return BFM_E_ARG;
-    hipLaunchKernelGGL(divide_kernel, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), full, cnt, n);
     return bfm_launch_status();
 }
 

@@ -656,16 +656,6 @@ __global__ void sample_finalize(const float* __restrict__ I, const float* __rest
     }
 }
 
-// elementwise with the scalar operand in device memory: 0: x / s   1: x >= thres_rel * s (fp32 product)
-__global__ void ew_dev(int op, const float* __restrict__ x, int64_t n, const double* __restrict__ s, float a,
-                       float* __restrict__ out) {
-    const float sv = (float)s[0];
-    GRID_STRIDE(i, n) {
-        const float v = x[i];
-        out[i] = op == 0 ? v / sv : (v >= a * sv ? 1.f : 0.f);
-    }
-}
-
 }  // namespace
 
 extern "C" int bfm_randn_philox(float* out, int64_t n, uint64_t seed, uint64_t offset, float scale, bfm_stream_t stream) {
@@ -943,12 +933,5 @@ extern "C" int bfm_sample_finalize(const float* I, const float* high_res, int sx
     const int64_t n = (int64_t)sx * sy * sz;
     hipLaunchKernelGGL(sample_finalize, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), I, high_res, n, max_dev, sx,
                        (int64_t)sy * sz, flip0 ? 1 : 0, input_out, residual_out);
-    return bfm_launch_status();
-}
-
-extern "C" int bfm_ew_dev(int op, const float* x, int64_t n, const double* scalar_dev, float a, float* out,
-                          bfm_stream_t stream) {
-    if (!x || !scalar_dev || !out || n <= 0 || op < 0 || op > 1) return BFM_E_ARG;
-    hipLaunchKernelGGL(ew_dev, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), op, x, n, scalar_dev, a, out);
     return bfm_launch_status();
 }

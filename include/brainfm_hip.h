@@ -77,7 +77,6 @@ int bfm_gn_stats_train(const float* A, int CA, const float* B, int CB, int D, in
  *   passes=1 uses hi only (fast mode, ~2^-11).  `bound` = G per-group bounds
  *   from bfm_gn_stats (operand scale is derived from them on the device).
  *   splitk>1 needs workspace of splitk*nvox*Cout*4 bytes. */
-size_t bfm_pack_conv_weights_direct_bytes(int Cin, int Cout);
 int bfm_pack_conv_weights_direct(const float* w_oidhw, int Cin, int Cout, float* wpacked, bfm_stream_t stream);
 size_t bfm_pack_conv_weights_mfma_bytes(int Cin, int Cout);
 /* wmax_abs_host = max|w| (host scalar); returns the power-of-two weight scale exponent in *wexp_host */
@@ -96,10 +95,8 @@ int bfm_conv3x3x3_direct(const float* A, int CA, const float* B, int CB, int D, 
                          const float* wpacked, int Cout, float slope, float* out, bfm_stream_t stream);
 
 /* Cin == 1 stem (enc0.1) as a K = 32 (27 taps + padding) GEMM on the matrix core, same split-fp16 numerics as
- * _mfma; Cout in {32, 64}; weights in the _direct layout [27][Cout]; bound = the single GroupNorm bound. */
-int bfm_conv3x3x3_stem(const float* A, int D, int H, int W, const float* scale, const float* shift,
-                       const float* bound, const float* wpacked_direct, int Cout, float slope, float* out,
-                       bfm_stream_t stream);
+ * _mfma; Cout in {32, 64}; weights in the _direct layout [27][Cout]; bound = the single GroupNorm bound
+ * (bfm_conv3x3x3_stem_ex). */
 
 /* Winograd F(2,3)-along-x variant of the single-source 3x3x3 conv (SingleConv 'gcl', buildingblocks.py:31-60):
  * 4 transformed positions x 9 (kd,kh) taps for every pair of x-neighbouring outputs = 1.5x fewer matrix-core FLOPs
@@ -108,12 +105,6 @@ int bfm_conv3x3x3_stem(const float* A, int D, int H, int W, const float* scale, 
 size_t bfm_pack_conv_weights_wino_bytes(int Cin, int Cout, int passes);
 int bfm_pack_conv_weights_wino(const float* w_oidhw, int Cin, int Cout, float wmax_abs_host, int passes, void* wpacked,
                                int* wexp_host, bfm_stream_t stream);
-int bfm_conv3x3x3_wino(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
-                       const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
-                       int flags /* bit 0: accumulate onto out; bit 1: wave-specialised persistent kernel; bit 2: 8-wave
-                                    software-pipelined kernel */,
-                       float* out, bfm_stream_t stream);
-
 int bfm_conv3x3x3_wino_rows(int D, int H, int W, int passes);   /* moment rows of the 4-wave kernel (0: cannot run) */
 int bfm_conv3x3x3_wino_ex(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
                           const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
@@ -410,13 +401,9 @@ int bfm_stitch_accumulate(const float* tile, const int64_t* tile_label, const fl
 int bfm_stitch_accumulate_multi(const float* maps, int64_t map_stride, const int32_t* sel, int K,
                                 const int64_t* tile_label, const float* tile_input, int td, int th, int tw, float* full,
                                 int D, int H, int W, int z0, int y0, int x0, bfm_stream_t stream);
-/* tile_input == NULL in bfm_stitch_accumulate means "already masked".  bfm_mask_tile produces the
- * masked, float-typed tile a rank ships to rank 0 in the multi-GPU path. */
-int bfm_mask_tile(const float* tile, const int64_t* tile_label, const float* tile_input, int64_t n, float* out,
-                  bfm_stream_t stream);
+/* tile_input == NULL in bfm_stitch_accumulate means "already masked". */
 int bfm_tile_count_add(float* cnt, int D, int H, int W, int z0, int z1, int y0, int y1, int x0, int x1,
                        bfm_stream_t stream);
-int bfm_divide_by_count(float* full, const float* cnt, int64_t n, bfm_stream_t stream);
 /* the K keys of one tile, masked (x tile_input != 0) and float typed, packed [K][n]: the multi-GPU shipping form */
 int bfm_pack_tile_multi(const float* maps, int64_t map_stride, const int32_t* sel, int K, const int64_t* tile_label,
                         const float* tile_input, int64_t n, float* out, bfm_stream_t stream);
@@ -479,9 +466,6 @@ int bfm_softmax_cl(const float* x, int64_t x_row_stride, int C, float* y, int64_
                    bfm_stream_t stream);
 int bfm_argmax_lut_cl(const float* p, int64_t row_stride, int C, const int32_t* lut, int64_t* out, int64_t n,
                       bfm_stream_t stream);
-/* encode_pathology -- Generator/datasets.py:496-518 */
-int bfm_pathology_encode(const float* I, const float* P, const float* Pprob, const float* randn, float mu0, float mu1,
-                         float s0, float s1, int64_t n, float* out, bfm_stream_t stream);
 int bfm_fake_cortical(const float* dist, int64_t row_stride, int n_dist, float* out, int64_t n,
                       bfm_stream_t stream);
 
@@ -726,8 +710,6 @@ int bfm_interp3d_linear_axes(const float* X, int nx, int ny, int nz, const float
  * mirrored along axis 0 with flip0; max in device memory. */
 int bfm_sample_finalize(const float* I, const float* high_res, int sx, int sy, int sz, const double* max_dev, int flip0,
                         float* input_out, float* residual_out, bfm_stream_t stream);
-/* elementwise with the scalar in device memory: op 0: x / s, op 1: x >= a * s ? 1 : 0 (fp32). */
-int bfm_ew_dev(int op, const float* x, int64_t n, const double* scalar_dev, float a, float* out, bfm_stream_t stream);
 
 /* Dormand-Prince integration of AdvDiffPDE ('adv', div-free V) with the step controller on the device
  * (ShapeID/DiffEqs/dopri5.py:58-172, rk_common.py:22-61, misc.py:145-170, interp.py:5-65, pde.py:616-640): one kernel per

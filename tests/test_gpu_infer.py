@@ -1637,6 +1637,137 @@ def test_winograd_f43_batch_equals_one_launch_per_sample_bitwise(case):
                 assert torch.equal(got, r1[k * lo: k * hi]), (pitch, s_, lo)
 
 
+@pytest.mark.parametrize("dims", [(8, 8, 8), (4, 4, 16)])
+def test_winograd_f43_batch_accumulate_padded_affine_equals_per_sample_bitwise(dims):
+    """bfm_conv3x3x3_wino4_batch with everything the batch launch can combine at once: accumulate mode (flags = 1, onto a
+    prior tensor), the affine rows CA + 16 apart and moment rows.  Sample by sample `out` and the rows are the bits of
+    bfm_conv3x3x3_wino4 with flags = 1 on that sample alone.  8 x 8 x 8 is the smallest volume the LDS-DMA kernel takes
+    (D, H >= 8), 4 x 4 x 16 the smallest that stays with the older body on conv_wino's 4 x 4 x 16 box."""
+    from brainfm_amd import _lib as L
+    lib = L.load()
+    dev = _dev()
+    S, cin, cout = 2, 16, 64
+    box = (C.c_int * 3)()
+    L.check(lib.bfm_conv3x3x3_wino4_box(dims[0], dims[1], dims[2], 3, box), "box")
+    assert tuple(box) == ((8, 8, 4) if dims == (8, 8, 8) else (4, 4, 16))            # the body each volume is here for
+    g = torch.Generator().manual_seed(dims[2])
+    A = torch.randn(S, *dims, cin, generator=g).to(dev)
+    base = torch.randn(S, *dims, cout, generator=g).to(dev)
+    w = (torch.randn(cout, cin, 3, 3, 3, generator=g) * 0.05).to(dev).contiguous()
+    wp = torch.empty(lib.bfm_pack_conv_weights_wino4_bytes(cin, cout, 3), dtype=torch.uint8, device=dev)
+    wexp = C.c_int(0)
+    L.check(lib.bfm_pack_conv_weights_wino4(L.ptr(w), cin, cout, float(w.abs().max()), 3, L.ptr(wp), C.byref(wexp),
+                                            L.stream_ptr()), "pack_wino4")
+    n = lib.bfm_conv3x3x3_wino4_rows(dims[0], dims[1], dims[2], 3)
+    assert n > 0
+    k = n * cout
+    pitch = cin + 16
+    aff = torch.zeros(2, S, pitch, device=dev)
+    aff[0, :, :cin] = (torch.rand(S, cin, generator=g) + 0.5).to(dev)
+    aff[1, :, :cin] = (torch.randn(S, cin, generator=g) * 0.1).to(dev)
+    bound = torch.stack([torch.full((8,), float((A[s_].abs().amax((0, 1, 2)) * aff[0, s_, :cin] + aff[1, s_, :cin].abs()).max()))
+                         for s_ in range(S)]).to(dev).contiguous()
+    out = base.clone()
+    rows = torch.zeros(lib.bfm_moment_rows_bytes(S * n, cout), dtype=torch.uint8, device=dev)
+    L.check(lib.bfm_conv3x3x3_wino4_batch(L.ptr(A), cin, S, dims[0], dims[1], dims[2], L.ptr(aff[0]), L.ptr(aff[1]), L.ptr(bound),
+                                          8, L.ptr(wp), wexp.value, cout, 0.01, 3, 1, L.ptr(out), L.ptr(rows), pitch,
+                                          L.stream_ptr()), "conv_wino4_batch")
+    assert not bool(torch.isnan(out).any()) and not torch.equal(out, base)
+    K = S * k
+    for s_ in range(S):
+        one = base[s_].clone()
+        r1 = torch.zeros(lib.bfm_moment_rows_bytes(n, cout), dtype=torch.uint8, device=dev)
+        sc, sh = aff[0, s_, :cin].contiguous(), aff[1, s_, :cin].contiguous()
+        L.check(lib.bfm_conv3x3x3_wino4(L.ptr(A[s_]), cin, dims[0], dims[1], dims[2], L.ptr(sc), L.ptr(sh), L.ptr(bound[s_]), 8,
+                                        L.ptr(wp), wexp.value, cout, 0.01, 3, 1, L.ptr(one), L.ptr(r1), L.stream_ptr()),
+                "conv_wino4")
+        assert torch.equal(out[s_], one), s_
+        for lo, hi, width in ((0, 8, 8), (8, 16, 8), (16, 20, 4), (20, 24, 4)):           # sums, squares, minima, maxima
+            got = rows[K * lo + s_ * k * width: K * lo + (s_ + 1) * k * width]
+            assert torch.equal(got, r1[k * lo: k * hi]), (s_, lo)
+
+
+def test_winograd_launchers_reject_bad_arguments_with_the_documented_codes():
+    """The argument checks of the two Winograd launchers (one shared prelude, then each family's own): one violation at a
+    time, every call returns its code before any kernel is launched.  Null operand, undefined flag bit, passes = 2 and a
+    pointer off its 16-byte alignment are BFM_E_ARG; CA % 16 and Cout % 64 are BFM_E_SHAPE; the fused pooling on a tensor
+    its 8 x 8 x 4 box does not tile is BFM_E_SHAPE; a batch of no samples or with affine rows closer than CA is BFM_E_ARG;
+    the F(4,3) uniform-box pair is BFM_E_ARG where the LDS-DMA kernel does not run and BFM_E_SHAPE where its box is not
+    conv_wino's (the flags are per box of conv_wino's grid).  The buffers are large enough for every shape named here."""
+    from brainfm_amd import _lib as L
+    lib = L.load()
+    dev = _dev()
+    E_ARG, E_SHAPE = -1, -2
+    st = L.stream_ptr()
+    A = torch.zeros(16 * 16 * 16 * 32, device=dev)
+    out = torch.zeros(16 * 16 * 16 * 128, device=dev)
+    aff = torch.ones(2, 64, device=dev)
+    bound = torch.ones(8, device=dev)
+    wp = torch.zeros(max(lib.bfm_pack_conv_weights_wino_bytes(32, 128, 3), lib.bfm_pack_conv_weights_wino4_bytes(32, 128, 3)),
+                     dtype=torch.uint8, device=dev)
+    rows = torch.zeros(lib.bfm_moment_rows_bytes(256, 128), dtype=torch.uint8, device=dev)
+    good = dict(A=L.ptr(A).value, CA=16, D=8, H=8, W=8, scale=L.ptr(aff[0]).value, shift=L.ptr(aff[1]).value,
+                bound=L.ptr(bound).value, G=8, wp=L.ptr(wp).value, wexp=0, Cout=64, slope=0.01, passes=3, flags=0,
+                out=L.ptr(out).value, rows=L.ptr(rows).value)
+
+    def common(a):
+        return (a["A"], a["CA"], a["D"], a["H"], a["W"], a["scale"], a["shift"], a["bound"], a["G"], a["wp"], a["wexp"], a["Cout"],
+                a["slope"], a["passes"], a["flags"], a["out"], a["rows"])
+
+    def f23(**kw):
+        return lib.bfm_conv3x3x3_wino_ex(*common(dict(good, **kw)), st)
+
+    def f43(**kw):
+        return lib.bfm_conv3x3x3_wino4(*common(dict(good, **kw)), st)
+
+    for call in (f23, f43):
+        for name in ("A", "scale", "shift", "bound", "wp", "out"):
+            assert call(**{name: None}) == E_ARG, (call.__name__, name)
+        for name in ("A", "scale", "shift", "wp", "out"):
+            assert call(**{name: good[name] + 4}) == E_ARG, (call.__name__, name)
+        assert call(flags=2) == E_ARG, call.__name__
+        assert call(passes=2) == E_ARG, call.__name__
+        assert call(CA=24) == E_SHAPE, call.__name__
+        assert call(Cout=96) == E_SHAPE, call.__name__
+    # two faults in one call: the order of the checks decides (flags before operands before shape before passes)
+    assert f23(flags=2, CA=24) == E_ARG and f43(A=None, Cout=96) == E_ARG and f23(CA=24, passes=2) == E_SHAPE
+
+    a = dict(good, D=12)
+    assert lib.bfm_conv3x3x3_wino_pool_ok(12, 8, 8, 3) == 0
+    assert lib.bfm_conv3x3x3_wino_pool(*common(a), L.ptr(out), None, st) == E_SHAPE
+    assert lib.bfm_conv3x3x3_wino_pool(*common(good), None, None, st) == E_ARG
+
+    def batch(S, stride):
+        a = good
+        return lib.bfm_conv3x3x3_wino4_batch(a["A"], a["CA"], S, a["D"], a["H"], a["W"], a["scale"], a["shift"], a["bound"], a["G"],
+                                             a["wp"], a["wexp"], a["Cout"], a["slope"], a["passes"], a["flags"], a["out"], a["rows"],
+                                             stride, st)
+
+    assert batch(0, 0) == E_ARG
+    assert batch(2, good["CA"] - 4) == E_ARG
+
+    def boxes(d, h, w):
+        b2, b4 = (C.c_int * 3)(), (C.c_int * 3)()
+        L.check(lib.bfm_conv3x3x3_wino_box(d, h, w, 3, b2), "box")
+        L.check(lib.bfm_conv3x3x3_wino4_box(d, h, w, 3, b4), "box4")
+        return tuple(b2), tuple(b4)
+
+    scratch = torch.zeros(lib.bfm_conv3x3x3_wino4_uniform_scratch(64), dtype=torch.uint8, device=dev)
+
+    def uniform(d, h, w):
+        fl = torch.zeros(lib.bfm_uniform_boxes_bytes(d, h, w, 3), dtype=torch.uint8, device=dev)
+        return lib.bfm_conv3x3x3_wino4_uniform(*common(dict(good, D=d, H=h, W=w)), L.ptr(fl), L.ptr(scratch), st)
+
+    assert boxes(8, 8, 8) == ((8, 8, 4), (8, 8, 4))
+    assert boxes(4, 4, 16) == ((4, 4, 16), (4, 4, 16))
+    assert uniform(4, 4, 16) == E_ARG                                  # thinner than a box of the LDS-DMA kernel: no pair
+    other = [v for v in ((8, 12, 16), (8, 8, 16), (12, 12, 16), (16, 12, 16)) if min(v[:2]) >= 8 and boxes(*v)[0] != boxes(*v)[1]]
+    assert other, "no candidate volume whose F(4,3) box differs from conv_wino's"
+    for v in other:
+        assert uniform(*v) == E_SHAPE, v
+    torch.cuda.synchronize()
+
+
 def _rows_totals(buf, nrows, c):
     """Column totals of a moment-row table (sum, sum of squares in float64; min, max)."""
     raw = buf.cpu().numpy()
