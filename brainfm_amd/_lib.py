@@ -120,6 +120,7 @@ SIGNATURES = {
     "bfm_gn_stats_rows_batch": (_I, [_P, _I, _I, _P, _I, _I, C.c_double, _L, _I, _P, _P, _I, _F, _P, _P, _P, _P]),
     "bfm_conv3x3x3_stem_rows": (_I, [_I, _I, _I]),
     "bfm_conv3x3x3_stem_ex": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P]),
+    "bfm_conv3x3x3_stem_mc_ex": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P]),
     "bfm_gn_stats_rows_workspace": (_Z, [_I, _I, _I, _I]),
     "bfm_gn_stats_rows": (_I, [_P, _I, _I, _P, _I, _I, C.c_double, _L, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P, _P]),
     "bfm_gn_stats_rows_sliced": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.c_double, _L, _P, _P, _I, _F, _P, _P, _P, _P, _Z,
@@ -212,6 +213,7 @@ SIGNATURES = {
     "bfm_softmax_cl": (_I, [_P, _L, _I, _P, _L, _L, _P]),
     "bfm_argmax_lut_cl": (_I, [_P, _L, _I, _P, _P, _L, _P]),
     "bfm_fake_cortical": (_I, [_P, _L, _I, _P, _L, _P]),
+    "bfm_mask_concat2": (_I, [_P, _P, _L, _P, _P]),
     "bfm_interp3d_linear": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _F, _P, _P]),
     "bfm_interp3d_nearest": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
     "bfm_deformed_atlas": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), _L, _P, _P]),

@@ -147,7 +147,41 @@ __global__ void __launch_bounds__(256) absmax_kernel(const float* __restrict__ x
     if (threadIdx.x == 0) atomicMax(out, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
 }
 
+// the stage-1 input of the two-stage model (utils/test_utils.py:336-338 + the joiner's concat): out[v] = {x*(1-p), p}.
+// 1 - p and the product round separately (the library is built without contraction), as torch's two kernels do.
+__global__ void mask_concat2(const float* __restrict__ x, const float* __restrict__ p, int64_t n, float2* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float q = p[i];
+        const float keep = 1.f - q;
+        out[i] = make_float2(x[i] * keep, q);
+    }
+}
+
+// two voxels per lane: 8-byte loads, one 16-byte store
+__global__ void mask_concat2x2(const float2* __restrict__ x, const float2* __restrict__ p, int64_t n2, float4* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+        const float2 a = x[i], q = p[i];
+        const float k0 = 1.f - q.x, k1 = 1.f - q.y;
+        out[i] = make_float4(a.x * k0, q.x, a.y * k1, q.y);
+    }
+}
+
 }  // namespace
+
+extern "C" int bfm_mask_concat2(const float* x, const float* p, int64_t n, float* out, bfm_stream_t stream) {
+    if (!x || !p || !out || n <= 0 || (reinterpret_cast<uintptr_t>(out) & 7)) return BFM_E_ARG;
+    const int64_t n2 = n >> 1;
+    if (n2 > 0 && aligned16(out) && !(reinterpret_cast<uintptr_t>(x) & 7) && !(reinterpret_cast<uintptr_t>(p) & 7)) {
+        hipLaunchKernelGGL(mask_concat2x2, dim3(grid_for(n2)), dim3(256), 0, bfm_s(stream), (const float2*)x,
+                           (const float2*)p, n2, (float4*)out);
+        if (n & 1)
+            hipLaunchKernelGGL(mask_concat2, dim3(1), dim3(64), 0, bfm_s(stream), x + (n2 << 1), p + (n2 << 1), (int64_t)1,
+                               (float2*)out + (n2 << 1));
+        return bfm_launch_status();
+    }
+    hipLaunchKernelGGL(mask_concat2, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), x, p, n, (float2*)out);
+    return bfm_launch_status();
+}
 
 extern "C" int bfm_absmax_f32(const float* x, int64_t rows, int64_t len, int64_t row_stride, float* out_zeroed,
                               bfm_stream_t stream) {

@@ -197,6 +197,8 @@ class UNetEngine:
         self.fuse_stats = os.environ.get("BFM_FUSE_STATS", "1") != "0"
         # MaxPool3d(2) in the epilogue of the F(2,3) layers that feed it (round 5; 0: the separate launch, same bits)
         self.fuse_pool = os.environ.get("BFM_FUSE_POOL", "1") != "0"
+        # the 2..4-channel stem of a conditioned network on the matrix core (0: the exact-fp32 direct kernel)
+        self.stem_mc = os.environ.get("BFM_STEM_MC", "1") != "0"
         self.prof_reps = 1
         self.prof = None            # bench.py: list collecting (start_event, end_event, flops, bytes) per MFMA conv launch
         sd = self._normalise_keys(state_dict)
@@ -746,6 +748,16 @@ class UNetEngine:
                                                    L.ptr(ly.wpacked), ly.cout, self.slope, L.ptr(out),
                                                    L.ptr(rows[0]) if rows is not None else None, st),
                     "conv_stem " + ly.name)
+            if rows is not None:
+                out._bfm_rows = rows
+        elif ca in (2, 3, 4) and cb == 0 and ly.cout in (32, 64) and not self.force_direct and self.stem_mc:
+            # the stem of a conditioned / two-stage network (image + condition channels): GroupNorm(1, ca), one bound
+            rows = self._rows_buf(ly.cout, 1, self.lib.bfm_conv3x3x3_stem_rows, D, H, W)
+            L.check(self.lib.bfm_conv3x3x3_stem_mc_ex(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound),
+                                                      L.ptr(ly.wpacked), ly.cout, self.slope, L.ptr(out),
+                                                      L.ptr(rows[0]) if rows is not None else None, st),
+                    "conv_stem_mc " + ly.name)
+            ly.kind = "stem_mc"
             if rows is not None:
                 out._bfm_rows = rows
         else:

@@ -12,6 +12,14 @@ from . import _lib as L
 from . import generator_utils as GU
 
 
+def merge_list_of_dict(dict_list_a, dict_list_b):
+    """utils/misc.py:639-643: update every dict of the first list with its partner in the second; returns the first."""
+    assert len(dict_list_a) == len(dict_list_b)
+    for i in range(len(dict_list_a)):
+        dict_list_a[i].update(dict_list_b[i])
+    return dict_list_a
+
+
 # ----------------------------------------------------------------------------- orientation
 def get_ras_axes(aff, n_dims=3):
     """utils/misc.py:226-235."""

@@ -814,7 +814,15 @@ def build_backbone(args, backbone, num_cond=0):
 
 
 def get_head(train_args, f_maps_list, out_channels, is_3d, out_feat_level, stage=0, exclude_keys=[]):
-    """head.py:175-183 (plain unet3d branch)."""
+    """head.py:175-183: the plain unet3d branch, and the two-stage one ('+' in train_args.backbone): stage 0 carries the
+    pathology head alone, stage 1 every head but pathology."""
+    backbone = getattr(train_args, "backbone", "")
+    if "sep" in backbone:
+        raise NotImplementedError("separate-decoder heads ('sep' backbones) are outside the hot path")
+    if "+" in backbone:
+        if stage == 0:
+            return TaskHead(train_args, f_maps_list, OrderedDict(pathology=1), is_3d, out_feat_level)
+        return TaskHead(train_args, f_maps_list, out_channels, is_3d, out_feat_level, exclude_keys=["pathology"])
     return TaskHead(train_args, f_maps_list, out_channels, is_3d, out_feat_level, exclude_keys)
 
 
@@ -836,6 +844,52 @@ def build_model(gen_args, train_args, device="cpu"):
     criterion = get_criterion(gen_args, train_args, gen_args.tasks, device)
     model.to(device)
     return gen_args, train_args, model, processors, criterion, get_postprocessor
+
+
+def _head_settings(head, gen_args):
+    head.left_hemis_only = bool(gen_args.generator.left_hemis_only)
+    head.max_surf_distance = float(gen_args.max_surf_distance)
+    return head
+
+
+def build_conditioned_model(gen_args, train_args, device="cpu"):
+    """Trainer/models/__init__.py:423-437 (mask-conditioned inpainting): one backbone whose input is the image and
+    len(train_args.condition.split('+')) condition channels, every head but pathology.  Called as
+    model(samples, cond=[...]); criterion as in build_model."""
+    gen_args, train_args = process_args(gen_args, train_args, task=gen_args.task)
+    backbone = build_backbone(train_args, train_args.backbone, num_cond=len(train_args.condition.split("+")))
+    head = _head_settings(get_head(train_args, train_args.task_f_maps, train_args.out_channels, True, -1, stage=1,
+                                   exclude_keys=["pathology"]), gen_args)
+    model = get_joiner(gen_args.tasks, backbone, head, device)
+    processors = get_processors(gen_args, train_args, gen_args.tasks, device, exclude_keys=["pathology"])
+    criterion = get_criterion(gen_args, train_args, gen_args.tasks, device, exclude_keys=["pathology"])
+    model.to(device)
+    return gen_args, train_args, model, processors, criterion, get_postprocessor
+
+
+def build_inpaint_model(gen_args, train_args, device="cpu"):
+    """Trainer/models/__init__.py:441-463 (two-stage inpainting; train_args.backbone = 'unet3d+unet3d'): stage 0 predicts
+    the pathology probability from the image (outputs 'feat_pathol', 'pathology'), stage 1 takes the masked image and that
+    probability as two channels (outputs 'feat_task' and every other head).  The pathology processors are
+    get_processors(gen_args, train_args, ['pathology'], device) -- the reference's own call lacks gen_args."""
+    gen_args, train_args = process_args(gen_args, train_args, task=gen_args.task)
+    names = train_args.backbone.split("+")
+    if len(names) != 2:
+        raise L.BfmError("build_inpaint_model needs a two-stage backbone 'a+b' (got '%s')" % train_args.backbone)
+    pathol_backbone = build_backbone(train_args, names[0], num_cond=0)
+    pathol_head = _head_settings(get_head(train_args, train_args.task_f_maps, train_args.out_channels, True, -1, stage=0),
+                                 gen_args)
+    pathol_model = get_joiner(gen_args.tasks, pathol_backbone, pathol_head, device, postfix="_pathol")
+    pathol_processors = get_processors(gen_args, train_args, ["pathology"], device)
+    task_backbone = build_backbone(train_args, names[1], num_cond=1)
+    task_head = _head_settings(get_head(train_args, train_args.task_f_maps, train_args.out_channels, True, -1, stage=1),
+                               gen_args)
+    task_model = get_joiner(gen_args.tasks, task_backbone, task_head, device, postfix="_task")
+    task_processors = get_processors(gen_args, train_args, gen_args.tasks, device, exclude_keys=["pathology"])
+    criterion = get_criterion(gen_args, train_args, gen_args.tasks, device)
+    pathol_model.to(device)
+    task_model.to(device)
+    return gen_args, train_args, pathol_model, task_model, pathol_processors, task_processors, criterion, get_postprocessor
 
 
 # --------------------------------------------------------------------------- checkpoint loading

@@ -219,6 +219,15 @@ int bfm_conv3x3x3_stem_rows(int D, int H, int W);
 int bfm_conv3x3x3_stem_ex(const float* A, int D, int H, int W, const float* scale, const float* shift,
                           const float* bound, const float* wpacked_direct, int Cout, float slope, float* out,
                           void* moment_rows /*or NULL*/, bfm_stream_t stream);
+/* The stem of a conditioned network, Cin in {2, 3, 4} (build_conditioned_model / build_inpaint_model,
+ * Trainer/models/__init__.py:423-463: backbone.py:21-26 with num_cond; the first SingleConv is GroupNorm(1, Cin) +
+ * Conv3d(Cin, Cout, 3), buildingblocks.py:31-60): K = 27 * Cin (+ zero columns to a multiple of 16) on the matrix core,
+ * A channels-last [D][H][W][Cin] (aligned to Cin floats for Cin 2 and 4), scale / shift per channel, one bound,
+ * weights in the _direct layout [27][Cin][Cout], Cout in {32, 64}, D*H*W*Cin < 2^31 (BFM_E_SHAPE otherwise).
+ * Moment rows: bfm_conv3x3x3_stem_rows(D, H, W). */
+int bfm_conv3x3x3_stem_mc_ex(const float* A, int Cin, int D, int H, int W, const float* scale, const float* shift,
+                             const float* bound, const float* wpacked_direct, int Cout, float slope, float* out,
+                             void* moment_rows /*or NULL*/, bfm_stream_t stream);
 /* GroupNorm scale/shift/bound from moment rows.  Source A: rowsA [nrowsA][CA]; optional source B (the low-res half of
  * a decoder concat, every voxel replicated weightB times by the nearest upsample: 8 for an exact 2x): rowsB.
  * nvox = voxels per channel of the normalised tensor (D*H*W of the full-res grid). */
@@ -468,6 +477,10 @@ int bfm_argmax_lut_cl(const float* p, int64_t row_stride, int C, const int32_t* 
                       bfm_stream_t stream);
 int bfm_fake_cortical(const float* dist, int64_t row_stride, int n_dist, float* out, int64_t n,
                       bfm_stream_t stream);
+/* Stage-1 input of the two-stage (inpainting) model in one pass: out[v] = { x[v] * (1 - p[v]), p[v] }, channels-last
+ * [n][2] (utils/test_utils.py:336-338: samples[i]['input'] * (1 - outputs_pathol[i]['pathology']), then joiner.py's
+ * torch.concat([x, cond], dim=1)).  1 - p and the product are two fp32 roundings, bit-equal to torch.  out 8-byte aligned. */
+int bfm_mask_concat2(const float* x, const float* p, int64_t n, float* out, bfm_stream_t stream);
 
 /* ---------------------------------------------------------------- synthesis
  * Gather / resample kernels of Generator/utils.py and utils/interpol (fp32, results bit-identical to the
