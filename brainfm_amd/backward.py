@@ -28,6 +28,14 @@ from .engine import _Layer
 
 TRAIN_FAST = os.environ.get("BFM_TRAIN_FAST", "1") != "0"
 WGRAD_PASSES = int(os.environ.get("BFM_WGRAD_PASSES", "3"))     # 3: split-fp16 matrix core; 0: exact fp32 matrix core
+# the conditioned stem's backward as one correlation (bfm_stem_mc_bwd); opt-in until it is timed against the generic route
+STEM_MC_BWD = os.environ.get("BFM_STEM_MC_BWD", "0") == "1"
+
+
+def stem_mc_bwd_ok(ly, ca, cb, need_input_grad):
+    """Whether backward_single_conv takes the one-correlation route (bfm_stem_mc_bwd): the first layer of a conditioned
+    network -- no input gradient wanted, one source of 2..4 channels under one GroupNorm group, 32 or 64 outputs."""
+    return (not need_input_grad and cb == 0 and ca in (2, 3, 4) and ly.cout in (32, 64) and ly.groups == 1)
 
 
 class ConvTape:
@@ -144,12 +152,26 @@ def backward_single_conv(eng, t, dY, need_input_grad=True):
     dP = torch.empty_like(dY)
     bnd = torch.empty(1, dtype=torch.float32, device=dev)         # max |dP|, written by the same kernel
     L.check(lib.bfm_lrelu_bwd_ex(L.ptr(dY), L.ptr(t.out), dY.numel(), eng.slope, L.ptr(dP), L.ptr(bnd), st), "lrelu_bwd")
+    sink = getattr(eng, "grad_sink", None)                       # train.GradStore: gradients land in their flat slot
+    if STEM_MC_BWD and stem_mc_bwd_ok(ly, ca, cb, need_input_grad):
+        # the conditioned stem: dW, dgamma, dbeta from one correlation of dP with the raw input (no dXn, no gn_bwd)
+        names = [ly.name + s for s in (".conv.weight", ".groupnorm.weight", ".groupnorm.bias")]
+        shapes = [(ly.cout, ly.cin, 3, 3, 3), (ly.cin,), (ly.cin,)]
+        outs = [sink.out(n, sh) if sink is not None else torch.empty(sh, dtype=torch.float32, device=dev)
+                for n, sh in zip(names, shapes)]
+        ws = torch.empty(lib.bfm_stem_mc_bwd_workspace(ca, ly.cout, D, H, W), dtype=torch.uint8, device=dev)
+        L.check(lib.bfm_stem_mc_bwd(L.ptr(dP), ly.cout, L.ptr(t.A), ca, D, H, W, L.ptr(ly.w_raw), L.ptr(t.scale),
+                                    L.ptr(t.shift), L.ptr(t.mean), L.ptr(t.rstd), L.ptr(outs[0]), L.ptr(outs[1]),
+                                    L.ptr(outs[2]), L.ptr(ws), ws.numel(), st), "stem_mc_bwd " + ly.name)
+        if sink is not None:
+            for n in names:
+                sink.done(n)
+        return None, None, OrderedDict(zip(names, outs))
     up = eng._upsample_desc(t.lo_dims, t.dims) if t.B is not None else None
     upp = C.byref(up) if up is not None else None
     # ---- weight gradient (split-fp16 matrix-core kernel on the wide layers, exact fp32 one elsewhere / on request)
     wsb = lib.bfm_conv3x3x3_wgrad_workspace(ly.cin, ly.cout, D, H, W)
     ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
-    sink = getattr(eng, "grad_sink", None)                       # train.GradStore: gradients land in their flat slot
     dW = (sink.out(ly.name + ".conv.weight", (ly.cout, ly.cin, 3, 3, 3)) if sink is not None else
           torch.empty((ly.cout, ly.cin, 3, 3, 3), dtype=torch.float32, device=dev))
     L.check(lib.bfm_conv3x3x3_wgrad_ex(L.ptr(dP), ly.cout, L.ptr(t.A), ca, L.ptr(t.B), cb, D, H, W, upp, L.ptr(t.scale),

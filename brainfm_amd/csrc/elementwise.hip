@@ -166,7 +166,49 @@ __global__ void mask_concat2x2(const float2* __restrict__ x, const float2* __res
     }
 }
 
+// the input of a mask-conditioned network in training (Trainer/engine.py:102-112 + the joiner's concat, joiner.py:178),
+// channels-last: mode 0 'mask' {m, p}, 1 'flip' {x, x[D-1-d]}, 2 'mask+flip' {m, m[D-1-d], p}, m = x * (1 - p) with the
+// two roundings of torch's two kernels.  masked / flipped (optional) are m and the flipped image as plain volumes.
+__global__ void condition_input_kernel(const float* __restrict__ x, const float* __restrict__ p, int mode, int64_t n, int64_t hw,
+                                       int D, float* __restrict__ out, float* __restrict__ masked, float* __restrict__ flipped) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t d = i / hw;
+        const int64_t mi = ((int64_t)(D - 1) - d) * hw + (i - d * hw);
+        float a = x[i], f = 0.f, q = 0.f;
+        if (mode != 1) {
+            q = p[i];
+            const float keep = 1.f - q;
+            a = a * keep;
+        }
+        if (mode != 0) {
+            f = x[mi];
+            if (mode == 2) {
+                const float keep = 1.f - p[mi];
+                f = f * keep;
+            }
+        }
+        if (mode == 0) {
+            out[2 * i] = a; out[2 * i + 1] = q;
+        } else if (mode == 1) {
+            out[2 * i] = a; out[2 * i + 1] = f;
+        } else {
+            out[3 * i] = a; out[3 * i + 1] = f; out[3 * i + 2] = q;
+        }
+        if (masked && mode != 1) masked[i] = a;
+        if (flipped && mode != 0) flipped[i] = f;
+    }
+}
+
 }  // namespace
+
+extern "C" int bfm_condition_input(const float* x, const float* p, int mode, int D, int H, int W, float* out, float* masked,
+                                   float* flipped, bfm_stream_t stream) {
+    if (!x || !out || D <= 0 || H <= 0 || W <= 0 || mode < 0 || mode > 2 || (mode != 1 && !p)) return BFM_E_ARG;
+    const int64_t n = (int64_t)D * H * W;
+    hipLaunchKernelGGL(condition_input_kernel, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), x, p, mode, n, (int64_t)H * W, D,
+                       out, masked, flipped);
+    return bfm_launch_status();
+}
 
 extern "C" int bfm_mask_concat2(const float* x, const float* p, int64_t n, float* out, bfm_stream_t stream) {
     if (!x || !p || !out || n <= 0 || (reinterpret_cast<uintptr_t>(out) & 7)) return BFM_E_ARG;

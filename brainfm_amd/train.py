@@ -688,13 +688,18 @@ class TrainStep:
         return OrderedDict((("loss_" + n), out["loss_" + n]) for n in self.loss_names if ("loss_" + n) in out)
 
     # ------------------------------------------------------------------ forward + backward
-    def _one_sample(self, x, target, sample, scale):
-        """Forward, losses and backward of one augmented sample on the current stream.  Returns (grads, slots, vals)."""
+    def _one_sample(self, x, target, sample, scale, x_cl=None):
+        """Forward, losses and backward of one augmented sample on the current stream.  Returns (grads, slots, vals).
+        x_cl: the network's channels-last input where it is not x itself (condition_inputs)."""
         eng, tail, lib = self.eng, self.tail, self.lib
         dims = tuple(x.shape[-3:])
         nvox = dims[0] * dims[1] * dims[2]
         st = L.stream_ptr()
-        x_cl = eng.to_cl(x)
+        if x_cl is None:
+            x_cl = eng.to_cl(x)
+        elif tuple(x_cl.shape) != dims + (eng.in_channels,) or x_cl.dtype != torch.float32 or not x_cl.is_contiguous():
+            raise L.BfmError("conditioned input %s %s: the network reads contiguous fp32 %s"
+                             % (tuple(x_cl.shape), x_cl.dtype, dims + (eng.in_channels,)))
         feats, tape = BW.backbone_forward_train(eng, x_cl, dims)
         feat_last = feats[-1][0]
         n_out, cf = tail.n_out, tail.c_feat
@@ -776,9 +781,10 @@ class TrainStep:
         return float(a)
 
     @L.on_device(lambda self, *a, **k: self.dev)
-    def loss_and_grads(self, xs, target, samples):
+    def loss_and_grads(self, xs, target, samples, cond=None):
         """xs: list of (1,C,D,H,W) inputs (one per augmented sample); target / samples as the reference's dicts
-        (NCDHW tensors).  Returns (loss_dict, total, grads) with grads = d(scale * total)/d(parameter) summed over the
+        (NCDHW tensors).  cond: what condition_inputs returned for these samples -- the network then reads those
+        channels-last inputs (xs gives the sizes only; no permute of xs is made).  Returns (loss_dict, total, grads) with grads = d(scale * total)/d(parameter) summed over the
         samples in sample order (scale = the loss scaler's).
         With sample_lanes > 1 (default 2, BFM_TRAIN_LANES) consecutive samples run on separate streams from the second
         iteration on -- the packed weights are all in place by then (apply() rebuilds them eagerly) and the conv variants
@@ -788,6 +794,9 @@ class TrainStep:
         eng = self.eng
         scale = self.scaler.scale
         n = len(xs)
+        if cond is not None and len(cond) != n:
+            raise L.BfmError("%d conditioned inputs for %d samples" % (len(cond), n))
+        cls = list(cond) if cond is not None else [None] * n
         self._touched_heads = set()
         lanes = self.sample_lanes if (n > 1 and self.t >= 1) else 1
         nvox = None
@@ -808,8 +817,8 @@ class TrainStep:
         n_head = n - 1 if use_store else n                 # samples that go the ordinary way
         store = None
         if lanes <= 1 or n_head <= 1:
-            for x, sample in zip(xs[:n_head], samples[:n_head]):
-                results.append(self._one_sample(x, target, sample, scale) + (None,))
+            for x, sample, x_cl in zip(xs[:n_head], samples[:n_head], cls):
+                results.append(self._one_sample(x, target, sample, scale, x_cl) + (None,))
         else:
             main = torch.cuda.current_stream(self.dev)
             while len(self._lane_streams) < lanes:
@@ -828,7 +837,7 @@ class TrainStep:
                 eng.lane, self._lane = k, k
                 try:
                     with torch.cuda.stream(st):
-                        g, slots, vals = self._one_sample(x, target, sample, scale)
+                        g, slots, vals = self._one_sample(x, target, sample, scale, cls[i])
                         ev = torch.cuda.Event()
                         ev.record(st)
                 finally:
@@ -847,7 +856,7 @@ class TrainStep:
                 part = r[0] if part is None else OrderedDict((k_, part[k_] + v_) for k_, v_ in r[0].items())
             eng.grad_sink = _Sink(store, part, self.tail.row_of)
             try:
-                results.append(self._one_sample(xs[-1], target, samples[-1], scale) + (None,))
+                results.append(self._one_sample(xs[-1], target, samples[-1], scale, cls[-1]) + (None,))
             finally:
                 eng.grad_sink = None
         grads = None
@@ -951,14 +960,14 @@ class TrainStep:
         return True, norms
 
     @L.on_device(lambda self, *a, **k: self.dev)
-    def step(self, xs, target, samples, lr=None, weight_decay=None, group=None):
-        """One full iteration (Trainer/engine.py:96-147).  Returns (loss_dict, total, stepped).  With more than one rank
+    def step(self, xs, target, samples, lr=None, weight_decay=None, group=None, cond=None):
+        """One full iteration (Trainer/engine.py:96-147; cond as loss_and_grads takes it).  Returns (loss_dict, total, stepped).  With more than one rank
         the loss dictionary is averaged over the ranks first (utils.reduce_dict, engine.py:124-130) and the skip decision
         is taken on that reduced value, so every rank skips -- or enters the gradient all-reduce -- together."""
         import torch.distributed as dist
         self._group = group
         self._store_next = True
-        loss_dict, total, grads = self.loss_and_grads(xs, target, samples)
+        loss_dict, total, grads = self.loss_and_grads(xs, target, samples, cond=cond)
         store = self.__dict__.pop("_store_live", None)
         touched = set(self._touched_heads)
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -996,6 +1005,70 @@ class TrainStep:
                 grads.pop("head." + k_, None)
         stepped, _ = self.apply(grads, lr, weight_decay, grad_div=grad_div)
         return loss_dict, total, stepped
+
+
+CONDITION_MODES = {frozenset(["mask"]): 0, frozenset(["flip"]): 1, frozenset(["mask", "flip"]): 2}
+
+
+def condition_inputs(samples, target, condition, device=None, in_channels=None):
+    """Trainer/engine.py:102-112 on the device, with the concat of joiner.py:178 and the channels-last repack, one
+    bfm_condition_input launch per sample.  condition: 'mask', 'flip' or 'mask+flip' (train_args.condition).  Returns the
+    per-sample (D,H,W,Cin) inputs of the conditioned network (channels: image, flipped image, mask) and leaves in
+    samples[i]['input'] the masked image and in samples[i]['input_flip'] its flip, as the reference does.
+    A target['pathology'] that is not a tensor (the generator stores 0. for a case without pathology) is an all-zero mask.
+    in_channels: the engine's input channels; a condition that gives another count raises."""
+    parts = frozenset(str(condition).split("+")) if condition else frozenset()
+    if parts not in CONDITION_MODES:
+        raise L.BfmError("unknown condition %r: 'mask', 'flip' or 'mask+flip'" % (condition,))
+    mode = CONDITION_MODES[parts]
+    cin = 3 if mode == 2 else 2
+    if in_channels is not None and int(in_channels) != cin:
+        raise L.BfmError("condition %r gives %d input channels, the network reads %d" % (condition, cin, in_channels))
+    lib = L.load()
+    out = []
+    for sample in samples:
+        x = sample["input"]
+        dev = torch.device(device) if device is not None else x.device
+        if dev.type != "cuda":
+            raise L.BfmError("condition_inputs runs on a HIP device only; there is no CPU fallback in the product path")
+        if x.dim() != 5 or x.shape[0] != 1 or x.shape[1] != 1:
+            raise L.BfmError("expected a (1,1,D,H,W) input, got %s" % (tuple(x.shape),))
+        D, H, W = (int(v) for v in x.shape[2:])
+        with torch.cuda.device(dev):
+            xd = x.to(device=dev, dtype=torch.float32).contiguous()
+            p = None
+            if mode != 1:
+                p = target.get("pathology") if target is not None else None
+                if isinstance(p, torch.Tensor):
+                    if p.numel() != D * H * W:
+                        raise L.BfmError("target['pathology'] %s does not match the input %s" % (tuple(p.shape), tuple(x.shape)))
+                    p = p.to(device=dev, dtype=torch.float32).contiguous()
+                else:
+                    p = torch.zeros((D, H, W), dtype=torch.float32, device=dev)
+            x_cl = torch.empty((D, H, W, cin), dtype=torch.float32, device=dev)
+            masked = torch.empty_like(xd) if mode != 1 else None
+            flipped = torch.empty_like(xd) if mode != 0 else None
+            L.check(lib.bfm_condition_input(L.ptr(xd), L.ptr(p), mode, D, H, W, L.ptr(x_cl), L.ptr(masked), L.ptr(flipped),
+                                            L.stream_ptr()), "condition_input")
+        if masked is not None:
+            sample["input"] = masked
+        if flipped is not None:
+            sample["input_flip"] = flipped
+        out.append(x_cl)
+    return out
+
+
+def conditioned_train_step(gen_args, train_args, model, weights_ce, all_samples, **kw):
+    """The TrainStep of a mask-conditioned model: (gen_args, train_args, model) as build_conditioned_model returns them
+    (Trainer/models/__init__.py:423-437), losses as its get_criterion(..., exclude_keys=['pathology']) call builds them."""
+    eng = model.backbone.engine(model.head)
+    names, weights = criterion_losses(train_args, gen_args.tasks, exclude_keys=("pathology",))
+    n_cond = len(str(train_args.condition).split("+"))
+    if eng.in_channels != 1 + n_cond:
+        raise L.BfmError("condition %r needs %d input channels, the backbone has %d"
+                         % (train_args.condition, 1 + n_cond, eng.in_channels))
+    kw.setdefault("max_surf_distance", float(gen_args.max_surf_distance))
+    return TrainStep(eng, model.head.tail(eng), names, weights, weights_ce, all_samples, **kw)
 
 
 class _NoHead:
@@ -1049,14 +1122,16 @@ class ContrastiveStep(TrainStep):
         return BW.backbone_backward(self.eng, tape, [None] * (len(feats) - 1) + [dfeat.view(dims + (self.c_feat,))])
 
     @L.on_device(lambda self, *a, **k: self.dev)
-    def loss_and_grads(self, xs, target=None, samples=None):
+    def loss_and_grads(self, xs, target=None, samples=None, cond=None):
         """xs: the augmented samples' inputs, (1,C,D,H,W) each, at least two; target / samples are not read (the loss has no
-        target).  Returns ({'loss_contrastive': v}, weight * v, grads) with grads = d(scale * weight * v)/d(parameter)
+        target); cond must be None: the contrastive backbone is not mask-conditioned.  Returns ({'loss_contrastive': v}, weight * v, grads) with grads = d(scale * weight * v)/d(parameter)
         under the backbone's parameter names: sample 0's gradient + sample 1's, added on the caller's stream.
         With sample_lanes > 1 (from the second iteration on, as TrainStep) the two forwards run on two streams, the loss
         kernel on the caller's stream after both, and the two backward passes on the two streams again; every kernel sees
         the same inputs as with one lane, so the result is the same bits."""
         self.__dict__.pop("_store_next", None)
+        if cond is not None:
+            raise L.BfmError("ContrastiveStep takes no conditioned inputs: its backbone reads the one-channel samples")
         if len(xs) < 2:
             raise L.BfmError("the contrastive loss compares two augmented samples; got %d" % len(xs))
         if any(x.shape[0] != 1 for x in xs[:2]) or tuple(xs[0].shape) != tuple(xs[1].shape):

@@ -481,6 +481,16 @@ int bfm_fake_cortical(const float* dist, int64_t row_stride, int n_dist, float* 
  * [n][2] (utils/test_utils.py:336-338: samples[i]['input'] * (1 - outputs_pathol[i]['pathology']), then joiner.py's
  * torch.concat([x, cond], dim=1)).  1 - p and the product are two fp32 roundings, bit-equal to torch.  out 8-byte aligned. */
 int bfm_mask_concat2(const float* x, const float* p, int64_t n, float* out, bfm_stream_t stream);
+/* The input of a mask-conditioned network in training, in one pass (Trainer/engine.py:102-112: samples[i]['input'] *=
+ * 1 - target['pathology'], torch.flip(samples[i]['input'], dims=[2]) and the concat of the condition channels; then
+ * joiner.py:178's torch.concat([x, cond], dim=1) and the channels-last repack).  x, p: (D,H,W) volumes.
+ *   mode 0 'mask'       out [D][H][W][2] = { m, p }               m = x * (1 - p), two fp32 roundings as in torch
+ *   mode 1 'flip'       out [D][H][W][2] = { x, x[D-1-d] }        (p unused, may be NULL)
+ *   mode 2 'mask+flip'  out [D][H][W][3] = { m, m[D-1-d], p }     the flip is of the masked input, first spatial axis
+ * masked / flipped (each may be NULL): m and the flipped image as (D,H,W) volumes -- what the reference leaves in
+ * samples[i]['input'] and samples[i]['input_flip'].  Bit-equal to the torch expressions.  Must not alias x or p. */
+int bfm_condition_input(const float* x, const float* p, int mode, int D, int H, int W, float* out, float* masked,
+                        float* flipped, bfm_stream_t stream);
 
 /* ---------------------------------------------------------------- synthesis
  * Gather / resample kernels of Generator/utils.py and utils/interpol (fp32, results bit-identical to the
@@ -758,6 +768,20 @@ int bfm_lrelu_bwd(const float* dY, const float* Y, int64_t n, float slope, float
 int bfm_lrelu_bwd_ex(const float* dY, const float* Y, int64_t n, float slope, float* dP, float* absmax,
                      bfm_stream_t stream);
 size_t bfm_conv3x3x3_wgrad_workspace(int Cin, int Cout, int D, int H, int W);
+/* The whole backward of the first SingleConv of a conditioned network (GroupNorm(1, Cin) + Conv3d(Cin, Cout, 3) on the
+ * network's input; torch autograd over buildingblocks.py:31-60 for the model of Trainer/models/__init__.py:423-437) as ONE
+ * correlation on the exact-fp32 matrix core.  The input is data, so no input gradient is formed: over the raw input x,
+ *   Q[o,c,t] = sum_v dP[v,o] x[v+t,c],  S[o,t] = sum_v dP[v,o]   (v+t inside the volume)
+ *   dW[o,c,t] = scale_c Q + shift_c S,  dgamma_c = rstd sum_{o,t} W (Q - mean S),  dbeta_c = sum_{o,t} W S.
+ * dP [D][H][W][Cout] (after lrelu_bwd, 16-byte aligned), x channels-last [D][H][W][Cin], w_raw [Cout][Cin][27], scale /
+ * shift [Cin] and mean / rstd [1] as bfm_gn_stats_train wrote them (one group).  Cin in {2,3,4}, Cout in {32,64}, any
+ * D,H,W >= 1 with D*H*W < 2^31; BFM_E_SHAPE otherwise, nothing launched.  Per-workgroup fp32 partials folded in fp64 in a
+ * fixed order, no atomics: the same bits on every run.  workspace: bfm_stem_mc_bwd_workspace() bytes, 8-byte aligned. */
+size_t bfm_stem_mc_bwd_workspace(int Cin, int Cout, int D, int H, int W);
+int bfm_stem_mc_bwd(const float* dP, int Cout, const float* x, int Cin, int D, int H, int W, const float* w_raw,
+                    const float* scale, const float* shift, const float* mean, const float* rstd,
+                    float* dW /*[Cout][Cin][27]*/, float* dgamma /*[Cin]*/, float* dbeta /*[Cin]*/, void* workspace,
+                    size_t workspace_bytes, bfm_stream_t stream);
 int bfm_conv3x3x3_wgrad(const float* dP, int Cout, const float* A, int CA, const float* B, int CB, int D, int H, int W,
                         const bfm_upsample_t* up, const float* scale, const float* shift, float* dW /*[Cout][Cin][27]*/,
                         void* workspace, size_t workspace_bytes, bfm_stream_t stream);
