@@ -172,6 +172,8 @@ SIGNATURES = {
     "bfm_conv3x3x3_wgrad_ex": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _P]),
     "bfm_stem_mc_bwd_workspace": (_Z, [_I, _I, _I, _I, _I]),
     "bfm_stem_mc_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "bfm_stem_mc_dgrad": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _L, _P]),
+    "bfm_mask_chain_bwd": (_I, [_P, _L, _P, _P, _L, _P, _L, _L, _P]),
     "bfm_gn_bwd_workspace": (_Z, [_I, _I, _I, _I]),
     "bfm_gn_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "bfm_maxpool2_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
@@ -217,6 +219,7 @@ SIGNATURES = {
     "bfm_fake_cortical": (_I, [_P, _L, _I, _P, _L, _P]),
     "bfm_mask_concat2": (_I, [_P, _P, _L, _P, _P]),
     "bfm_condition_input": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "bfm_twostage_train_input": (_I, [_P, _P, _L, _L, _P, _L, _P, _P, _P, _P]),
     "bfm_interp3d_linear": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _F, _P, _P]),
     "bfm_interp3d_nearest": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
     "bfm_deformed_atlas": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), _L, _P, _P]),

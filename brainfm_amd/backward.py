@@ -32,6 +32,29 @@ WGRAD_PASSES = int(os.environ.get("BFM_WGRAD_PASSES", "3"))     # 3: split-fp16 
 STEM_MC_BWD = os.environ.get("BFM_STEM_MC_BWD", "0") == "1"
 
 
+# with an input-gradient request (two-stage training): bfm_stem_mc_bwd + bfm_stem_mc_dgrad instead of the generic kernels
+# + bfm_mask_chain_bwd (BFM_STEM_MC_DGRAD=0); on by default: 2.4x the generic route at 128^3 and 160^3, profiles/stem_dgrad.txt
+STEM_MC_DGRAD = os.environ.get("BFM_STEM_MC_DGRAD", "1") != "0"
+
+
+class InputGrad:
+    """A request for the first layer's gradient with respect to ONE input channel, chained through the masking of the
+    two-stage model (Trainer/engine.py:238: input_masked = input * (1 - p), p = sigmoid of a stage-0 head output) into that
+    head's gradient buffer: dRaw[col_offset + u * voxel_stride] += -x_raw[u] * dX[u] * p[u] * (1 - p[u]).
+    x_raw, p: (D,H,W) fp32 volumes; dRaw: the stage-0 step's head-gradient buffer."""
+    __slots__ = ("channel", "x_raw", "p", "dRaw", "col_offset", "voxel_stride")
+
+    def __init__(self, channel, x_raw, p, dRaw, col_offset, voxel_stride):
+        self.channel, self.x_raw, self.p, self.dRaw = int(channel), x_raw, p, dRaw
+        self.col_offset, self.voxel_stride = int(col_offset), int(voxel_stride)
+
+
+def stem_mc_dgrad_ok(ly, ca, cb):
+    """Whether an input-gradient request can take the fused pair (bfm_stem_mc_bwd + bfm_stem_mc_dgrad): one source of
+    2..4 channels under one GroupNorm group, 32 or 64 outputs."""
+    return cb == 0 and ca in (2, 3, 4) and ly.cout in (32, 64) and ly.groups == 1
+
+
 def stem_mc_bwd_ok(ly, ca, cb, need_input_grad):
     """Whether backward_single_conv takes the one-correlation route (bfm_stem_mc_bwd): the first layer of a conditioned
     network -- no input gradient wanted, one source of 2..4 channels under one GroupNorm group, 32 or 64 outputs."""
@@ -138,8 +161,9 @@ def _add(a, b):
     return ew_binary(L.EW_ADD, a, b)
 
 
-def backward_single_conv(eng, t, dY, need_input_grad=True):
-    """Returns (dA, dB, grads) for one taped SingleConv; dB is the gradient of the LOW-RES tensor (or None)."""
+def backward_single_conv(eng, t, dY, need_input_grad=True, input_grad=None):
+    """Returns (dA, dB, grads) for one taped SingleConv; dB is the gradient of the LOW-RES tensor (or None).
+    input_grad: an InputGrad -- the gradient of one input channel is chained into input_grad.dRaw (two-stage training)."""
     ly = t.ly
     D, H, W = t.dims
     nv = D * H * W
@@ -153,7 +177,17 @@ def backward_single_conv(eng, t, dY, need_input_grad=True):
     bnd = torch.empty(1, dtype=torch.float32, device=dev)         # max |dP|, written by the same kernel
     L.check(lib.bfm_lrelu_bwd_ex(L.ptr(dY), L.ptr(t.out), dY.numel(), eng.slope, L.ptr(dP), L.ptr(bnd), st), "lrelu_bwd")
     sink = getattr(eng, "grad_sink", None)                       # train.GradStore: gradients land in their flat slot
-    if STEM_MC_BWD and stem_mc_bwd_ok(ly, ca, cb, need_input_grad):
+    if input_grad is not None:
+        ig = input_grad
+        if cb or not 0 <= ig.channel < ca:
+            raise L.BfmError("input gradient of channel %d: the layer reads %d + %d channels" % (ig.channel, ca, cb))
+        for v in (ig.x_raw, ig.p):
+            if v.numel() != nv or v.dtype != torch.float32 or not v.is_contiguous():
+                raise L.BfmError("input-gradient request: x_raw and p are contiguous fp32 volumes of %d voxels" % nv)
+        if ig.col_offset + (nv - 1) * ig.voxel_stride >= ig.dRaw.numel():
+            raise L.BfmError("input-gradient request: dRaw of %d values is too short" % ig.dRaw.numel())
+    fused_dgrad = input_grad is not None and STEM_MC_DGRAD and stem_mc_dgrad_ok(ly, ca, cb)
+    if fused_dgrad or (input_grad is None and STEM_MC_BWD and stem_mc_bwd_ok(ly, ca, cb, need_input_grad)):
         # the conditioned stem: dW, dgamma, dbeta from one correlation of dP with the raw input (no dXn, no gn_bwd)
         names = [ly.name + s for s in (".conv.weight", ".groupnorm.weight", ".groupnorm.bias")]
         shapes = [(ly.cout, ly.cin, 3, 3, 3), (ly.cin,), (ly.cin,)]
@@ -163,6 +197,12 @@ def backward_single_conv(eng, t, dY, need_input_grad=True):
         L.check(lib.bfm_stem_mc_bwd(L.ptr(dP), ly.cout, L.ptr(t.A), ca, D, H, W, L.ptr(ly.w_raw), L.ptr(t.scale),
                                     L.ptr(t.shift), L.ptr(t.mean), L.ptr(t.rstd), L.ptr(outs[0]), L.ptr(outs[1]),
                                     L.ptr(outs[2]), L.ptr(ws), ws.numel(), st), "stem_mc_bwd " + ly.name)
+        if fused_dgrad:
+            # before `done`: a GradStore slot holds this sample's dgamma / dbeta only until the earlier samples' are added
+            L.check(lib.bfm_stem_mc_dgrad(L.ptr(dP), ly.cout, L.ptr(t.A), ca, D, H, W, L.ptr(ly.w_raw), L.ptr(ly.gamma),
+                                          L.ptr(t.mean), L.ptr(t.rstd), L.ptr(outs[1]), L.ptr(outs[2]), ig.channel, None,
+                                          L.ptr(ig.x_raw), L.ptr(ig.p), L.ptr(ig.dRaw), ig.col_offset, ig.voxel_stride, st),
+                    "stem_mc_dgrad " + ly.name)
         if sink is not None:
             for n in names:
                 sink.done(n)
@@ -221,6 +261,9 @@ def backward_single_conv(eng, t, dY, need_input_grad=True):
     L.check(lib.bfm_gn_bwd(L.ptr(dXn), L.ptr(t.A), ca, L.ptr(t.B), cb, D, H, W, upp, L.ptr(starts[0]), L.ptr(starts[1]),
                            L.ptr(starts[2]), L.ptr(t.mean), L.ptr(t.rstd), L.ptr(ly.gamma), ly.groups, L.ptr(dA),
                            L.ptr(dB), L.ptr(dgamma), L.ptr(dbeta), L.ptr(wsg), wsg.numel(), st), "gn_bwd " + ly.name)
+    if input_grad is not None:
+        L.check(lib.bfm_mask_chain_bwd(C.c_void_p(dA.data_ptr() + 4 * ig.channel), ca, L.ptr(ig.x_raw), L.ptr(ig.p), nv,
+                                       L.ptr(ig.dRaw), ig.col_offset, ig.voxel_stride, st), "mask_chain_bwd " + ly.name)
     if sink is not None:
         sink.done(ly.name + ".groupnorm.weight")
         sink.done(ly.name + ".groupnorm.bias")
@@ -285,9 +328,10 @@ def backbone_forward_train(eng, x_cl, dims, fast=None):
     return feats, tape
 
 
-def backbone_backward(eng, tape, dfeats):
+def backbone_backward(eng, tape, dfeats, input_grad=None):
     """dfeats: gradients w.r.t. the decoder feature maps returned by backbone_forward_train (same order, channels-last;
-    None = zero).  Returns {parameter name: gradient}."""
+    None = zero).  Returns {parameter name: gradient}.
+    input_grad: an InputGrad for the first layer (default: no input gradient is delivered)."""
     grads = OrderedDict()
     nlev = len(tape["enc"])
     dskip = [None] * nlev                       # gradient flowing into encoder level i's output from its decoder use
@@ -312,7 +356,8 @@ def backbone_backward(eng, tape, dfeats):
             g = _add(g, dskip[i]) if g is not None else dskip[i]
         dy, _, gr = backward_single_conv(eng, t2, g)
         grads.update(gr)
-        dx, _, gr = backward_single_conv(eng, t1, dy, need_input_grad=i > 0)
+        dx, _, gr = backward_single_conv(eng, t1, dy, need_input_grad=i > 0 or input_grad is not None,
+                                         input_grad=input_grad if i == 0 else None)
         grads.update(gr)
         if i > 0:
             xin, din = tape["pool"][i - 1]

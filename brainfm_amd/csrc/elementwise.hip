@@ -199,7 +199,36 @@ __global__ void condition_input_kernel(const float* __restrict__ x, const float*
     }
 }
 
+// the stage-1 input of the two-stage model in TRAINING (Trainer/engine.py:230-243): p = sigmoid(raw0) (PatholProcessor,
+// joiner.py:79-87) with the expression of bfm_loss_pathol, so that the loss and the mask see the same p;
+// out[v] = {x (1 - p), t} with torch's two roundings, t the target mask (NULL: zeros).  raw0 of voxel v is
+// raw0[col_off + v * vstride], as in bfm_loss_pathol.
+__global__ void twostage_train_input_kernel(const float* __restrict__ x, const float* __restrict__ raw0, int64_t col_off,
+                                            int64_t vstride, const float* __restrict__ t, int64_t n, float2* __restrict__ out,
+                                            float* __restrict__ p_out, float* __restrict__ masked) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float r = raw0[col_off + i * vstride];
+        const float p = 1.0f / (1.0f + expf(-r));
+        const float keep = 1.f - p;
+        const float m = x[i] * keep;
+        out[i] = make_float2(m, t ? t[i] : 0.f);
+        p_out[i] = p;
+        if (masked) masked[i] = m;
+    }
+}
+
 }  // namespace
+
+extern "C" int bfm_twostage_train_input(const float* x, const float* raw0, int64_t col_offset, int64_t voxel_stride,
+                                        const float* t, int64_t n, float* out, float* p_out, float* masked_out,
+                                        bfm_stream_t stream) {
+    if (!x || !raw0 || !out || !p_out || n <= 0 || col_offset < 0 || voxel_stride < 1 ||
+        (reinterpret_cast<uintptr_t>(out) & 7))
+        return BFM_E_ARG;
+    hipLaunchKernelGGL(twostage_train_input_kernel, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), x, raw0, col_offset,
+                       voxel_stride, t, n, (float2*)out, p_out, masked_out);
+    return bfm_launch_status();
+}
 
 extern "C" int bfm_condition_input(const float* x, const float* p, int mode, int D, int H, int W, float* out, float* masked,
                                    float* flipped, bfm_stream_t stream) {

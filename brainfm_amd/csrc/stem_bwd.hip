@@ -248,3 +248,189 @@ extern "C" int bfm_stem_mc_bwd(const float* dP, int Cout, const float* x, int Ci
                        dW, dgamma, dbeta);
     return bfm_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Input gradient of the same layer with respect to ONE input channel c, and its chain through the masking of the two-stage
+// model into the stage-0 logit (Trainer/engine.py:238: input_masked = input * (1 - sigmoid(raw0)); torch autograd over
+// buildingblocks.py:31-60).  With xhat = (X - mean) rstd, N = Cin D H W:
+//
+//     G_c[u]  = sum_{o,k} dP[u - k + 1, o] W[o, c, k]                      (zero outside the volume)
+//     dX_c[u] = rstd (gamma_c G_c[u] - m1 - xhat_c[u] m2),   m1 = sum_c' gamma_c' dbeta_c' / N,  m2 = sum_c' gamma_c' dgamma_c' / N
+//     dRaw[col_offset + u voxel_stride] += -x_raw[u] dX_c[u] p[u] (1 - p[u])
+//
+// The group sums are the dgamma / dbeta the parameter backward has already produced, so only channel c's G is formed: one
+// launch, no reduction pass, no dXn tensor.
+//
+// stem_mc_dgrad_kernel<COUT>: workgroups over 4x4x16-voxel tiles.  Per tile, T[v, k] = sum_o dP[v, o] W[o, c, k] over the
+// tile's voxels and their one-voxel halo (648 voxels) is a GEMM M = 648 (21 blocks of 32), K = COUT, N = 27 of 32 on the
+// exact-fp32 matrix core.  The A operand comes straight from HBM: lane (l32, lh) reads the COUT / 2 consecutive channels
+// lh COUT / 2 .. of voxel l32 (the order of the K steps is free, so the two lane halves take the two halves of a voxel's
+// row), the B operand (this channel's weights) stays in registers.  T goes to LDS as [tap][voxel] (odd pitch), and
+// G[u] = sum_k T[k][u - k + 1] is 27 LDS reads per lane in tap order.  One writer per voxel, no atomics: the same bits on
+// every run.
+namespace {
+
+constexpr int DG_TP = SH_VOX + 1;                           // odd pitch: a wave's 27 taps of one voxel hit different banks
+constexpr int DG_MB = (SH_VOX + 31) / 32;                   // 21
+constexpr int DG_THREADS = ST_VOX;                          // one lane per tile voxel in the second phase
+
+// the mask chain of one voxel: bfm_stem_mc_dgrad's epilogue and bfm_mask_chain_bwd share the expression (and its bits)
+__device__ __forceinline__ float mask_chain_term(float xr, float dx, float p) {
+    const float a = -xr * dx;
+    const float b = a * p;
+    return b * (1.f - p);
+}
+
+struct StemDgradParams {
+    const float* dP;                  // [D][H][W][COUT]
+    const float* x;                   // [D][H][W][Cin]
+    const float* w;                   // [COUT][Cin][27]
+    const float *gamma, *mean, *rstd, *dgamma, *dbeta;
+    int Cin, D, H, W, channel;
+    int nby, nbx, ntiles;
+    float* dx;                        // [D][H][W] or NULL
+    const float *x_raw, *p;           // [D][H][W] each, or both NULL
+    float* dRaw;
+    int64_t col_offset, voxel_stride;
+};
+
+template <int COUT>
+__global__ void __launch_bounds__(DG_THREADS) stem_mc_dgrad_kernel(const StemDgradParams q) {
+    extern __shared__ float Ts[];                           // [27][DG_TP]
+    constexpr int HALF = COUT / 2;
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63, l32 = lane & 31, lh = lane >> 5;
+    const int c = q.channel;
+    // B[k = (lh, j)][n = l32] = W[o = lh HALF + j][c][tap l32]
+    float breg[HALF];
+#pragma unroll
+    for (int j = 0; j < HALF; ++j)
+        breg[j] = l32 < 27 ? q.w[((lh * HALF + j) * q.Cin + c) * 27 + l32] : 0.f;
+    // the two group means of the GroupNorm backward, from the parameter gradients
+    double s1 = 0.0, s2 = 0.0;
+    for (int k = 0; k < q.Cin; ++k) {
+        s1 += (double)q.gamma[k] * (double)q.dbeta[k];
+        s2 += (double)q.gamma[k] * (double)q.dgamma[k];
+    }
+    const double nrm = (double)q.Cin * (double)q.D * (double)q.H * (double)q.W;
+    const float m1 = (float)(s1 / nrm), m2 = (float)(s2 / nrm);
+    const float mean = q.mean[0], rstd = q.rstd[0], gam = q.gamma[c];
+    const int zl = tid >> 6, yl = (tid >> 4) & 3, xl = tid & 15;
+
+    for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
+        const int bx = tile % q.nbx;
+        const int t2 = tile / q.nbx;
+        const int by = t2 % q.nby, bz = t2 / q.nby;
+        const int z0 = bz * ST_Z, y0 = by * ST_Y, x0 = bx * ST_X;
+        __syncthreads();                                    // the previous tile's reads of Ts are done
+        for (int mb = wave; mb < DG_MB; mb += DG_THREADS / 64) {
+            const int hv = mb * 32 + l32;
+            const int hz = hv / (SH_Y * SH_X);
+            const int r = hv - hz * (SH_Y * SH_X);
+            const int hy = r / SH_X, hx = r - hy * SH_X;
+            const int zz = z0 + hz - 1, yy = y0 + hy - 1, xx = x0 + hx - 1;
+            const bool in = hv < SH_VOX && zz >= 0 && zz < q.D && yy >= 0 && yy < q.H && xx >= 0 && xx < q.W;
+            float4 a[HALF / 4];
+            if (in) {
+                const float4* src = reinterpret_cast<const float4*>(q.dP + ((int64_t)(zz * q.H + yy) * q.W + xx) * COUT + lh * HALF);
+#pragma unroll
+                for (int j = 0; j < HALF / 4; ++j) a[j] = src[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < HALF / 4; ++j) a[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            floatx16 acc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+            for (int j = 0; j < HALF / 4; ++j) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j].x, breg[4 * j + 0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j].y, breg[4 * j + 1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j].z, breg[4 * j + 2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j].w, breg[4 * j + 3], acc, 0, 0, 0);
+            }
+            if (l32 < 27) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int row = mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh;
+                    if (row < SH_VOX) Ts[l32 * DG_TP + row] = acc[i];
+                }
+            }
+        }
+        __syncthreads();
+        const int z = z0 + zl, y = y0 + yl, x = x0 + xl;
+        if (z < q.D && y < q.H && x < q.W) {
+            float g = 0.f;
+#pragma unroll
+            for (int k = 0; k < 27; ++k) {
+                const int kd = k / 9, kh = (k / 3) % 3, kw = k % 3;
+                g += Ts[k * DG_TP + ((zl + 2 - kd) * SH_Y + (yl + 2 - kh)) * SH_X + (xl + 2 - kw)];
+            }
+            const int64_t u = (int64_t)(z * q.H + y) * q.W + x;
+            const float xhat = (q.x[u * q.Cin + c] - mean) * rstd;
+            const float dxv = rstd * (gam * g - m1 - xhat * m2);
+            if (q.dx) q.dx[u] = dxv;
+            if (q.p) {
+                const int64_t o = q.col_offset + u * q.voxel_stride;
+                q.dRaw[o] += mask_chain_term(q.x_raw[u], dxv, q.p[u]);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) mask_chain_bwd_kernel(const float* __restrict__ dx, int64_t dx_stride,
+                                                             const float* __restrict__ x_raw, const float* __restrict__ p,
+                                                             int64_t n, float* __restrict__ dRaw, int64_t col_offset,
+                                                             int64_t voxel_stride) {
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < n; u += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = col_offset + u * voxel_stride;
+        dRaw[o] += mask_chain_term(x_raw[u], dx[u * dx_stride], p[u]);
+    }
+}
+
+}  // namespace
+
+extern "C" int bfm_stem_mc_dgrad(const float* dP, int Cout, const float* x_cl, int Cin, int D, int H, int W, const float* w_raw,
+                                 const float* gamma, const float* mean, const float* rstd, const float* dgamma,
+                                 const float* dbeta, int channel, float* dx, const float* x_raw, const float* p, float* dRaw,
+                                 int64_t col_offset, int64_t voxel_stride, bfm_stream_t stream) {
+    if (!dP || !x_cl || !w_raw || !gamma || !mean || !rstd || !dgamma || !dbeta) return BFM_E_ARG;
+    const bool chain = x_raw || p;
+    if (chain && (!x_raw || !p || !dRaw || col_offset < 0 || voxel_stride < 1)) return BFM_E_ARG;
+    if (!chain && !dx) return BFM_E_ARG;                    // nothing to write
+    if (!sb_shape_ok(Cin, Cout, D, H, W) || channel < 0 || channel >= Cin) return BFM_E_SHAPE;
+    if (reinterpret_cast<uintptr_t>(dP) & 15) return BFM_E_ARG;
+    const SbPlan pl = sb_plan(D, H, W);
+    StemDgradParams q{};
+    q.dP = dP; q.x = x_cl; q.w = w_raw; q.gamma = gamma; q.mean = mean; q.rstd = rstd; q.dgamma = dgamma; q.dbeta = dbeta;
+    q.Cin = Cin; q.D = D; q.H = H; q.W = W; q.channel = channel;
+    q.nby = pl.nby; q.nbx = pl.nbx; q.ntiles = pl.ntiles;
+    q.dx = dx; q.x_raw = x_raw; q.p = p; q.dRaw = dRaw; q.col_offset = col_offset; q.voxel_stride = voxel_stride;
+    const int grid = std::min(pl.ntiles, 4096);
+    constexpr int lds = 27 * DG_TP * (int)sizeof(float);    // 70 KB: above the static limit
+    // the attribute belongs to the device: one flag per device and kernel (setting it twice is harmless)
+    static bool attr[2][64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return BFM_E_LAUNCH;
+    const int wide = Cout == 64 ? 1 : 0;
+    const void* fn = wide ? reinterpret_cast<const void*>(&stem_mc_dgrad_kernel<64>)
+                          : reinterpret_cast<const void*>(&stem_mc_dgrad_kernel<32>);
+    if (dev < 0 || dev >= 64 || !attr[wide][dev]) {
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return BFM_E_LAUNCH;
+        if (dev >= 0 && dev < 64) attr[wide][dev] = true;
+    }
+    if (wide)
+        hipLaunchKernelGGL(stem_mc_dgrad_kernel<64>, dim3(grid), dim3(DG_THREADS), lds, bfm_s(stream), q);
+    else
+        hipLaunchKernelGGL(stem_mc_dgrad_kernel<32>, dim3(grid), dim3(DG_THREADS), lds, bfm_s(stream), q);
+    return bfm_launch_status();
+}
+
+extern "C" int bfm_mask_chain_bwd(const float* dx, int64_t dx_stride, const float* x_raw, const float* p, int64_t n, float* dRaw,
+                                  int64_t col_offset, int64_t voxel_stride, bfm_stream_t stream) {
+    if (!dx || !x_raw || !p || !dRaw || n <= 0 || dx_stride < 1 || col_offset < 0 || voxel_stride < 1) return BFM_E_ARG;
+    const int grid = (int)std::min<int64_t>(bfm_cdiv64(n, 256), 4096);
+    hipLaunchKernelGGL(mask_chain_bwd_kernel, dim3(grid), dim3(256), 0, bfm_s(stream), dx, dx_stride, x_raw, p, n, dRaw,
+                       col_offset, voxel_stride);
+    return bfm_launch_status();
+}

@@ -160,6 +160,26 @@ def allreduce_mean_(grads, group=None, events=None):
     return grads
 
 
+def reduce_losses_(loss_dict, touched, loss_names, tasks, loss_weights, device, group=None):
+    """utils.reduce_dict of the loss dictionary over the ranks (Trainer/engine.py:124-130) and, in the same collective, the
+    union of the heads some rank's loss reached (DDP's find_unused_parameters=True).  loss_names / tasks give the fixed
+    layout: a rank may lack a loss another one has.  Returns (loss_dict, total, touched) as every rank now sees them."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    keys = list(loss_names)
+    # gloo reduces on the host, RCCL on the device
+    rdev = device if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    t = torch.tensor([loss_dict.get("loss_" + k, 0.0) for k in keys] +
+                     [1.0 if ("loss_" + k) in loss_dict else 0.0 for k in keys] +
+                     [1.0 if task in touched else 0.0 for task in tasks], dtype=torch.float64, device=rdev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    t = t.cpu().tolist()
+    nk = len(keys)
+    loss_dict = OrderedDict(("loss_" + k, t[i] / world) for i, k in enumerate(keys) if t[nk + i] > 0)
+    total = sum(v * loss_weights.get(k, 0.0) for k, v in loss_dict.items() if k in loss_weights)
+    return loss_dict, total, {task for j, task in enumerate(tasks) if t[2 * nk + j] > 0}
+
+
 class _Sink:
     """What the backward pass sees of a GradStore (engine.grad_sink): `out` hands a kernel its slot, `done` adds the
     earlier samples' sum for that slot and counts its bucket down."""
@@ -691,10 +711,15 @@ class TrainStep:
     def _one_sample(self, x, target, sample, scale, x_cl=None):
         """Forward, losses and backward of one augmented sample on the current stream.  Returns (grads, slots, vals).
         x_cl: the network's channels-last input where it is not x itself (condition_inputs)."""
-        eng, tail, lib = self.eng, self.tail, self.lib
+        ctx = self._sample_forward(x, x_cl)
+        self._sample_criterion(ctx, target, sample, scale)
+        return self._sample_backward(ctx, target, scale)
+
+    def _sample_forward(self, x, x_cl=None):
+        """Backbone and heads of one sample in training mode.  Returns the sample's context: tape, head outputs `raw`, the
+        zeroed head-gradient buffer `dRaw` (rows: both are (n_out, nvox) rows, otherwise channels-last)."""
+        eng, tail = self.eng, self.tail
         dims = tuple(x.shape[-3:])
-        nvox = dims[0] * dims[1] * dims[2]
-        st = L.stream_ptr()
         if x_cl is None:
             x_cl = eng.to_cl(x)
         elif tuple(x_cl.shape) != dims + (eng.in_channels,) or x_cl.dtype != torch.float32 or not x_cl.is_contiguous():
@@ -711,8 +736,28 @@ class TrainStep:
         if fn is None:
             fn = feat_last
         dRaw = torch.zeros_like(raw)
-        vals = torch.zeros(4 * len(self.loss_names) + 2 * tail.n_out + 8, dtype=torch.float64, device=self.dev)
-        slots, k_used = self._sample_losses(raw, dims, target, sample, dRaw, vals, scale, rows=rows)
+        return dict(dims=dims, feats=feats, tape=tape, feat_last=feat_last, rows=rows, raw=raw, fn=fn, dRaw=dRaw)
+
+    def _sample_criterion(self, ctx, target, sample, scale):
+        """Every loss of the sample: values into the context's fp64 slots, gradients added into its dRaw."""
+        vals = torch.zeros(4 * len(self.loss_names) + 2 * self.tail.n_out + 8, dtype=torch.float64, device=self.dev)
+        ctx["slots"], ctx["k_used"] = self._sample_losses(ctx["raw"], ctx["dims"], target, sample, ctx["dRaw"], vals, scale,
+                                                          rows=ctx["rows"])
+        ctx["vals"], ctx["active"], ctx["keep"] = vals, self._active_rows, self._keep
+
+    def _sample_backward(self, ctx, target, scale, pre_heads=None, input_grad=None):
+        """Backward of one sample from its head-gradient buffer.  Returns (grads, slots, vals).
+        pre_heads: called with the context first; it may add into ctx['dRaw'] before the heads' backward reads it, and may
+        run the sample's criterion itself (two-stage training: the stage-1 gradient through the mask).
+        input_grad: a backward.InputGrad for the first layer."""
+        if pre_heads is not None:
+            pre_heads(ctx)
+        eng, tail, lib = self.eng, self.tail, self.lib
+        dims, feats, tape, feat_last, rows = ctx["dims"], ctx["feats"], ctx["tape"], ctx["feat_last"], ctx["rows"]
+        fn, dRaw, slots, k_used, vals = ctx["fn"], ctx["dRaw"], ctx["slots"], ctx["k_used"], ctx["vals"]
+        nvox = dims[0] * dims[1] * dims[2]
+        n_out, cf = tail.n_out, tail.c_feat
+        st = L.stream_ptr()
         age_tape = None
         if self.age is not None:
             _, age_tape = self.age.forward(fn, dims)
@@ -756,7 +801,7 @@ class TrainStep:
             L.check(lib.bfm_normalize_bwd(L.ptr(feat_last), L.ptr(dFn), cf, nvox, 1e-12, L.ptr(dfeat), st), "normalize_bwd")
         else:
             dfeat = dFn
-        g = BW.backbone_backward(eng, tape, [None] * (len(feats) - 1) + [dfeat.view(dims + (cf,))])
+        g = BW.backbone_backward(eng, tape, [None] * (len(feats) - 1) + [dfeat.view(dims + (cf,))], input_grad=input_grad)
         for task, (r0, n) in tail.row_of.items():
             g["head.final_conv_%s.weight" % task] = dW[r0:r0 + n]
             g["head.final_conv_%s.bias" % task] = db[r0:r0 + n]
@@ -765,7 +810,7 @@ class TrainStep:
         # heads no loss of this sample reached: the reference leaves their .grad None (the all-zero rows above only keep
         # the gradient dictionary's layout fixed for the flat all-reduce); loss_and_grads collects who was reached
         self._touched_heads.update(task for task, (r0, n) in tail.row_of.items()
-                                   if any(r in self._active_rows for r in range(r0, r0 + n)))
+                                   if any(r in ctx["active"] for r in range(r0, r0 + n)))
         return g, slots, vals
 
     @staticmethod
@@ -884,9 +929,18 @@ class TrainStep:
         """unscale -> per-parameter clip (utils/misc.py:1329-1338) -> AdamW -> scaler.update.  Returns
         (stepped, norms): stepped is False when a non-finite gradient made the scaler skip the step.
         grad_div: the gradients hold a SUM over that many ranks (GradStore); the mean's division is folded into the unscale."""
+        plan = self._measure(grads, grad_div)
+        if plan["found_inf"]:
+            self.scaler.update(True)
+            return False, plan["norms"]
+        self._update(plan, lr, weight_decay)
+        self.scaler.update(False)
+        return True, plan["norms"]
+
+    def _measure(self, grads, grad_div=1.0):
+        """First half of apply: the optimiser state of every parameter with a gradient, each gradient's norm (unscaled) and
+        whether any is non-finite.  Nothing is updated; the scaler is not touched."""
         lib, st = self.lib, L.stream_ptr()
-        lr = self.lr if lr is None else float(lr)
-        wd = self.wd if weight_decay is None else float(weight_decay)
         params = self.parameters()
         names = [k for k in params if k in grads]
         sums = torch.zeros(len(names), dtype=torch.float64, device=self.dev)
@@ -928,9 +982,16 @@ class TrainStep:
         found_inf = bool(flag.item())
         norms = [math.sqrt(v) * inv if math.isfinite(v) else float("inf") for v in sums.cpu().tolist()]
         found_inf = found_inf or any(not math.isfinite(v) for v in norms)
-        if found_inf:
-            self.scaler.update(True)
-            return False, norms
+        return dict(grads=grads, params=params, names=names, norms=norms, inv=inv, found_inf=found_inf, multi=multi,
+                    desc=desc if multi else None, CH=CH if multi else 0)
+
+    def _update(self, plan, lr=None, weight_decay=None):
+        """Second half of apply: per-parameter clip and AdamW on what _measure prepared, then the packed weights."""
+        lib, st = self.lib, L.stream_ptr()
+        lr = self.lr if lr is None else float(lr)
+        wd = self.wd if weight_decay is None else float(weight_decay)
+        grads, params, names, norms, inv = plan["grads"], plan["params"], plan["names"], plan["norms"], plan["inv"]
+        multi, desc, CH = plan["multi"], plan["desc"], plan["CH"]
         self.t += 1
         for i, (k, nrm) in enumerate(zip(names, norms)):
             p, g = params[k], grads[k]
@@ -956,8 +1017,6 @@ class TrainStep:
                                              self.betas[0], self.betas[1], self.eps, wd, st), "adamw_multi")
             self._keep_desc = tdev
         self._weights_changed()
-        self.scaler.update(False)
-        return True, norms
 
     @L.on_device(lambda self, *a, **k: self.dev)
     def step(self, xs, target, samples, lr=None, weight_decay=None, group=None, cond=None):
@@ -975,20 +1034,9 @@ class TrainStep:
             store.finish()                                     # every rank, whatever its loss: the collectives are in flight
             self.allreduce_events = list(store.events) if store.events else []
         if multi:
-            world = dist.get_world_size(group)
             tasks = list(self.tail.row_of.keys()) + (["age"] if self.age is not None else [])
-            keys = list(self.loss_names)                       # fixed layout: a rank may lack a loss another one has
-            # gloo reduces on the host, RCCL on the device
-            rdev = self.dev if dist.get_backend(group) == "nccl" else torch.device("cpu")
-            t = torch.tensor([loss_dict.get("loss_" + k, 0.0) for k in keys] +
-                             [1.0 if ("loss_" + k) in loss_dict else 0.0 for k in keys] +
-                             [1.0 if task in touched else 0.0 for task in tasks], dtype=torch.float64, device=rdev)
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-            t = t.cpu().tolist()
-            nk = len(keys)
-            loss_dict = OrderedDict(("loss_" + k, t[i] / world) for i, k in enumerate(keys) if t[nk + i] > 0)
-            total = sum(v * self.loss_weights.get(k, 0.0) for k, v in loss_dict.items() if k in self.loss_weights)
-            touched = {task for j, task in enumerate(tasks) if t[2 * nk + j] > 0}     # find_unused_parameters=True
+            loss_dict, total, touched = reduce_losses_(loss_dict, touched, self.loss_names, tasks, self.loss_weights, self.dev,
+                                                       group)
         if not math.isfinite(total):
             return loss_dict, total, False                     # engine.py:129-136: non-finite loss -> skip the iteration
         grad_div = 1.0
@@ -1069,6 +1117,213 @@ def conditioned_train_step(gen_args, train_args, model, weights_ce, all_samples,
                          % (train_args.condition, 1 + n_cond, eng.in_channels))
     kw.setdefault("max_surf_distance", float(gen_args.max_surf_distance))
     return TrainStep(eng, model.head.tail(eng), names, weights, weights_ce, all_samples, **kw)
+
+
+class TwoStageTrainStep:
+    """One joint iteration of the two-stage (pathology-robust, "inpainting") model: Trainer/engine.py:193-318,
+    train_one_epoch_twostage, the loop that produces the two checkpoints evaluate_image_twostage loads.  Per sample
+    (engine.py:230-253, without autocast as TrainStep):
+
+        outputs_pathol = pathol_model(samples); PatholProcessor       stage-0 forward (tape kept), p = sigmoid(raw0)
+        samples[i]['input_masked'] = input * (1 - p)                  bfm_twostage_train_input, with cond = target['pathology']
+        outputs_task = task_model(samples, 'input_masked', cond)      stage-1 forward, its losses, its backward; the first
+                                                                      layer's input gradient goes through the mask into
+                                                                      stage 0's head gradient (backward.InputGrad)
+        criterion(merge(outputs_task, outputs_pathol), ...)           pathol_ce / pathol_dice on stage 0's output
+        backward                                                      stage-0 backward
+
+    pathol_step / task_step: the TrainStep of each model (loss names pathol_* and all the others).  One LossScaler is shared;
+    `step` takes one skip decision for both models and hands the same lr / weight decay / clip to both AdamW states, which
+    is the arithmetic of the reference's single optimiser over both models' parameters.  The samples run one after the
+    other on the caller's stream (no sample lanes, no GradStore overlap).  A target['pathology'] that is not a tensor is an
+    all-zero mask, and the pathology losses are then absent (condition_inputs has the same rule)."""
+
+    PREFIX = ("pathol.", "task.")
+
+    def __init__(self, pathol_step, task_step, loss_names=None):
+        s0, s1 = pathol_step, task_step
+        for s_ in (s0, s1):
+            if torch.device(s_.dev).type != "cuda":
+                raise L.BfmError("TwoStageTrainStep runs on a HIP device only; there is no CPU fallback in the product path")
+        if torch.device(s0.dev) != torch.device(s1.dev):
+            raise L.BfmError("the two stages live on %s and %s: one device trains both" % (s0.dev, s1.dev))
+        if s0.eng.in_channels != 1 or s1.eng.in_channels != 2:
+            raise L.BfmError("two-stage training reads a 1-channel image (stage 0) and {masked image, mask} (stage 1); "
+                             "the backbones read %d and %d channels" % (s0.eng.in_channels, s1.eng.in_channels))
+        if "pathology" not in s0.tail.row_of or s0.tail.row_of["pathology"][1] != 1:
+            raise L.BfmError("stage 0 needs the one-channel pathology head")
+        bad = [n for n in s0.loss_names if not n.startswith("pathol_")] + [n for n in s1.loss_names if n.startswith("pathol_")]
+        if bad:
+            raise L.BfmError("losses on the wrong stage: %s (pathol_* act on stage 0, every other name on stage 1)" % bad)
+        self.pathol_step, self.task_step = s0, s1
+        self.dev, self.lib = s0.dev, s0.lib
+        self.scaler = s0.scaler
+        s1.scaler = self.scaler                            # ONE GradScaler (engine.py:280-287)
+        self.loss_names = list(loss_names) if loss_names is not None else list(s1.loss_names) + list(s0.loss_names)
+        if sorted(self.loss_names) != sorted(list(s0.loss_names) + list(s1.loss_names)):
+            raise L.BfmError("loss names %s are not those of the two steps" % (self.loss_names,))
+        self.loss_weights = dict(s1.loss_weights)
+        self.loss_weights.update(s0.loss_weights)
+
+    def parameters(self):
+        """{'pathol.' / 'task.' + reference parameter name: device tensor} of both models."""
+        out = OrderedDict()
+        for pre, s_ in zip(self.PREFIX, (self.pathol_step, self.task_step)):
+            out.update((pre + k, v) for k, v in s_.parameters().items())
+        return out
+
+    def _split(self, grads):
+        return tuple(OrderedDict((k[len(pre):], v) for k, v in grads.items() if k.startswith(pre)) for pre in self.PREFIX)
+
+    def _sample(self, x, target, sample, scale):
+        """engine.py:230-253 and the backward of one sample.  Returns the results of _sample_backward of stage 0 and of
+        stage 1, and (stage-0 logits as a strided view of the head outputs, p)."""
+        s0, s1, lib = self.pathol_step, self.task_step, self.lib
+        if x.dim() != 5 or x.shape[0] != 1 or x.shape[1] != 1:
+            raise L.BfmError("expected a (1,1,D,H,W) input, got %s" % (tuple(x.shape),))
+        dims = tuple(int(v) for v in x.shape[2:])
+        nvox = dims[0] * dims[1] * dims[2]
+        xd = x.to(device=self.dev, dtype=torch.float32).contiguous()
+        t = target.get("pathology") if target is not None else None
+        target0 = target
+        if isinstance(t, torch.Tensor):
+            if t.numel() != nvox:
+                raise L.BfmError("target['pathology'] %s does not match the input %s" % (tuple(t.shape), tuple(x.shape)))
+            t = t.to(device=self.dev, dtype=torch.float32).contiguous()
+        else:
+            t = None                                       # the generator's 0.: a zero mask and no pathology loss
+            target0 = {k: v for k, v in (target or {}).items() if k != "pathology"}
+        ctx0 = s0._sample_forward(xd)
+        raw0 = ctx0["raw"]
+        co = s0._col("pathology")
+        off, vs = (co * raw0.stride(0), 1) if ctx0["rows"] else (co, s0.tail.n_out)
+        xin = torch.empty(dims + (2,), dtype=torch.float32, device=self.dev)
+        p = torch.empty(dims, dtype=torch.float32, device=self.dev)
+        masked = torch.empty_like(xd)
+        L.check(lib.bfm_twostage_train_input(L.ptr(xd), L.ptr(raw0), off, vs, L.ptr(t), nvox, L.ptr(xin), L.ptr(p),
+                                             L.ptr(masked), L.stream_ptr()), "twostage_train_input")
+        sample["input_masked"] = masked
+        res = {}
+
+        def stage1_then_pathol_losses(ctx):
+            ctx1 = s1._sample_forward(xd, xin)
+            s1._sample_criterion(ctx1, target, sample, scale)
+            ig = BW.InputGrad(0, xd, p, ctx["dRaw"], off, vs)
+            res[1] = s1._sample_backward(ctx1, target, scale, input_grad=ig)
+            s0._sample_criterion(ctx, target0, sample, scale)
+
+        res[0] = s0._sample_backward(ctx0, target0, scale, pre_heads=stage1_then_pathol_losses)
+        return res[0], res[1], (raw0.reshape(-1)[off:off + (nvox - 1) * vs + 1:vs], p)
+
+    @L.on_device(lambda self, *a, **k: self.dev)
+    def loss_and_grads(self, xs, target, samples, masks=None):
+        """xs: list of (1,1,D,H,W) inputs; target / samples as the reference's dicts.  Leaves samples[i]['input_masked'].
+        masks: a list that receives each sample's (stage-0 logits, p = their sigmoid) as the mask was built from them.
+        Returns (loss_dict, total, grads): the merged loss dictionary in the criterion's order, and grads =
+        d(scale * total)/d(parameter) of both models under parameters()' names, summed over the samples in sample order."""
+        s0, s1 = self.pathol_step, self.task_step
+        scale = self.scaler.scale
+        s0._touched_heads, s1._touched_heads = set(), set()
+        for s_ in (s0, s1):
+            s_.__dict__.pop("_store_next", None)
+        sums = [None, None]
+        per = ([], [])
+        nvox = None
+        for x, sample in zip(xs, samples):
+            nvox = x.shape[-3] * x.shape[-2] * x.shape[-1]
+            r0, r1, mask = self._sample(x, target, sample, scale)
+            if masks is not None:
+                masks.append(mask)
+            for j, (g, slots, vals) in enumerate((r0, r1)):
+                per[j].append((slots, vals))
+                if sums[j] is None:
+                    sums[j] = g
+                else:
+                    for k_, v_ in g.items():
+                        sums[j][k_] = sums[j][k_] + v_
+        s0._touched_heads.add("pathology")                 # reached through the mask whatever the pathology losses do
+        found = OrderedDict()
+        found.update(s1._finish_losses(per[1], nvox))
+        found.update(s0._finish_losses(per[0], nvox))
+        loss_dict = OrderedDict(("loss_" + n, found["loss_" + n]) for n in self.loss_names if "loss_" + n in found)
+        total = sum(v * self.loss_weights.get(k, 0.0) for k, v in loss_dict.items() if k in self.loss_weights)
+        grads = OrderedDict()
+        for pre, g in zip(self.PREFIX, sums):
+            grads.update((pre + k, v) for k, v in g.items())
+        return loss_dict, total, grads
+
+    @L.on_device(lambda self, *a, **k: self.dev)
+    def step(self, xs, target, samples, lr=None, weight_decay=None, group=None):
+        """One full joint iteration (engine.py:217-287).  Returns (loss_dict, total, stepped).  A non-finite gradient in
+        either model skips both and backs the shared scale off once; with more than one rank the loss dictionary is averaged
+        first and the merged gradient dictionary goes through allreduce_mean_."""
+        import torch.distributed as dist
+        s0, s1 = self.pathol_step, self.task_step
+        loss_dict, total, grads = self.loss_and_grads(xs, target, samples)
+        touched = set(s1._touched_heads)
+        heads = list(s1.tail.row_of.keys())
+        tasks = heads + (["age"] if s1.age is not None else [])
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            loss_dict, total, touched = reduce_losses_(loss_dict, touched, self.loss_names, tasks, self.loss_weights, self.dev,
+                                                       group)
+        if not math.isfinite(total):
+            return loss_dict, total, False
+        allreduce_mean_(grads, group)
+        g0, g1 = self._split(grads)
+        for task in heads:                                 # stage-1 heads nobody's loss reached: no gradient, no step
+            if task not in touched:
+                g1.pop("head.final_conv_%s.weight" % task, None)
+                g1.pop("head.final_conv_%s.bias" % task, None)
+        if s1.age is not None and "age" not in touched:
+            for k_ in s1.age.params:
+                g1.pop("head." + k_, None)
+        plans = (s0._measure(g0), s1._measure(g1))
+        if plans[0]["found_inf"] or plans[1]["found_inf"]:
+            self.scaler.update(True)
+            return loss_dict, total, False
+        s0._update(plans[0], lr, weight_decay)
+        s1._update(plans[1], lr, weight_decay)
+        self.scaler.update(False)
+        return loss_dict, total, True
+
+    def save_checkpoint(self, pathol_path, task_path, epoch=0, **extra):
+        """The two checkpoints TwoStageSession / evaluate_image_twostage load (scripts/train.py:205-214 per model)."""
+        self.pathol_step.save_checkpoint(pathol_path, epoch=epoch, **extra)
+        self.task_step.save_checkpoint(task_path, epoch=epoch, **extra)
+
+
+def twostage_train_step(gen_args, train_args, pathol_model, task_model, weights_ce, all_samples, **kw):
+    """The TwoStageTrainStep of the two models build_inpaint_model returns (Trainer/models/__init__.py:441-463), losses as
+    its get_criterion(gen_args, train_args, gen_args.tasks) builds them: pathol_ce / pathol_dice go to stage 0, every other
+    name to stage 1, and the merged dictionary keeps the criterion's order.  train_args.condition None or 'mask' is the
+    loop's runnable path; with 'flip' the reference concatenates three channels into a backbone built with num_cond=1
+    (engine.py:240-242 against models/__init__.py:451), which cannot run, so it is refused here."""
+    cond = getattr(train_args, "condition", None)
+    if cond and "flip" in str(cond):
+        raise L.BfmError("condition %r: the reference's two-stage loop builds a 3-channel input with 'flip' for a stage-1 "
+                         "backbone of 2 channels (num_cond=1) and cannot run; two-stage training takes None or 'mask'" % (cond,))
+    if cond and str(cond) != "mask":
+        raise L.BfmError("unknown condition %r for two-stage training: None or 'mask'" % (cond,))
+    eng0 = pathol_model.backbone.engine(pathol_model.head)
+    eng1 = task_model.backbone.engine(task_model.head)
+    for e_ in (eng0, eng1):
+        if torch.device(e_.device).type != "cuda":
+            raise L.BfmError("two-stage training runs on a HIP device only; there is no CPU fallback in the product path")
+    if eng0.in_channels != 1 or eng1.in_channels != 2:
+        raise L.BfmError("two-stage training reads a 1-channel image (stage 0) and {masked image, mask} (stage 1); the "
+                         "backbones read %d and %d channels" % (eng0.in_channels, eng1.in_channels))
+    names, weights = criterion_losses(train_args, gen_args.tasks)
+    n0 = [n for n in names if n.startswith("pathol_")]
+    n1 = [n for n in names if not n.startswith("pathol_")]
+    kw.setdefault("max_surf_distance", float(gen_args.max_surf_distance))
+    scaler = kw.pop("scaler", None)
+    if scaler is None:
+        scaler = LossScaler(enabled=False)
+    age_head = kw.pop("age_head", None)                    # the pooled scalar head belongs to stage 1 (every head but pathology)
+    s0 = TrainStep(eng0, pathol_model.head.tail(eng0), n0, weights, weights_ce, all_samples, scaler=scaler, **kw)
+    s1 = TrainStep(eng1, task_model.head.tail(eng1), n1, weights, weights_ce, all_samples, scaler=scaler, age_head=age_head,
+                   **kw)
+    return TwoStageTrainStep(s0, s1, loss_names=names)
 
 
 class _NoHead:

@@ -491,6 +491,15 @@ int bfm_mask_concat2(const float* x, const float* p, int64_t n, float* out, bfm_
  * samples[i]['input'] and samples[i]['input_flip'].  Bit-equal to the torch expressions.  Must not alias x or p. */
 int bfm_condition_input(const float* x, const float* p, int mode, int D, int H, int W, float* out, float* masked,
                         float* flipped, bfm_stream_t stream);
+/* The stage-1 input of the two-stage model in training, in one pass (Trainer/engine.py:230-243: PatholProcessor's sigmoid,
+ * joiner.py:79-87; samples[i]['input_masked'] = samples[i]['input'] * (1 - outputs_pathol[i]['pathology']); cond =
+ * target['pathology']; joiner.py:178's concat).  raw0 of voxel v is raw0[col_offset + v * voxel_stride] (bfm_loss_pathol's
+ * addressing).  p_out [n] = sigmoid(raw0) = 1 / (1 + expf(-raw0)), the expression bfm_loss_pathol evaluates, so the loss and
+ * the mask see the same p; out [n][2] = { x * (1 - p), t }, two fp32 roundings as in torch; t NULL: a zero mask.
+ * masked_out [n] (may be NULL): x * (1 - p) as a volume (samples[i]['input_masked']).  out 8-byte aligned. */
+int bfm_twostage_train_input(const float* x, const float* raw0, int64_t col_offset, int64_t voxel_stride, const float* t,
+                             int64_t n, float* out /*[n][2]*/, float* p_out /*[n]*/, float* masked_out /*[n] or NULL*/,
+                             bfm_stream_t stream);
 
 /* ---------------------------------------------------------------- synthesis
  * Gather / resample kernels of Generator/utils.py and utils/interpol (fp32, results bit-identical to the
@@ -782,6 +791,28 @@ int bfm_stem_mc_bwd(const float* dP, int Cout, const float* x, int Cin, int D, i
                     const float* scale, const float* shift, const float* mean, const float* rstd,
                     float* dW /*[Cout][Cin][27]*/, float* dgamma /*[Cin]*/, float* dbeta /*[Cin]*/, void* workspace,
                     size_t workspace_bytes, bfm_stream_t stream);
+/* The input gradient of the same layer (GroupNorm(1, Cin) + Conv3d(Cin, Cout, 3, padding=1)) with respect to ONE input
+ * channel, optionally chained through the masking of the two-stage model into the stage-0 logit (torch autograd over
+ * buildingblocks.py:31-60 and Trainer/engine.py:238, input_masked = input * (1 - sigmoid(raw0)), in
+ * train_one_epoch_twostage, engine.py:193-318).  With xhat = (x_cl - mean) rstd and N = Cin D H W:
+ *   G_c[u]  = sum_{o,k} dP[u - k + 1, o] W[o, c, k]                        (zero outside the volume; c = channel)
+ *   dX_c[u] = rstd (gamma_c G_c[u] - m1 - xhat_c[u] m2),  m1 = sum gamma dbeta / N,  m2 = sum gamma dgamma / N
+ *   dRaw[col_offset + u voxel_stride] += -x_raw[u] dX_c[u] p[u] (1 - p[u])
+ * dgamma / dbeta [Cin]: what the layer's parameter backward (bfm_stem_mc_bwd or bfm_gn_bwd) produced for the same dP.
+ * Only channel c's G is formed (exact-fp32 matrix core), in one launch.  dx [D][H][W] (may be NULL) receives dX_c; x_raw
+ * and p (both NULL: no chain) are the unmasked image and sigmoid(raw0); dRaw is added to, one writer per voxel, no
+ * atomics: the same bits on every run.  Shapes as bfm_stem_mc_bwd, 0 <= channel < Cin: BFM_E_SHAPE otherwise; a NULL
+ * mandatory pointer (or neither dx nor the chain asked for): BFM_E_ARG; nothing is launched or written on error.
+ * dP 16-byte aligned. */
+int bfm_stem_mc_dgrad(const float* dP, int Cout, const float* x_cl, int Cin, int D, int H, int W, const float* w_raw,
+                      const float* gamma, const float* mean, const float* rstd, const float* dgamma, const float* dbeta,
+                      int channel, float* dx /*[D][H][W] or NULL*/, const float* x_raw, const float* p, float* dRaw,
+                      int64_t col_offset, int64_t voxel_stride, bfm_stream_t stream);
+/* The chain alone, for an input gradient that already exists (bfm_gn_bwd's dA, read with a stride):
+ * dRaw[col_offset + u voxel_stride] += -x_raw[u] dx[u dx_stride] p[u] (1 - p[u]), u < n.  The same expression, and the
+ * same bits, as bfm_stem_mc_dgrad's epilogue (Trainer/engine.py:238 under autograd). */
+int bfm_mask_chain_bwd(const float* dx, int64_t dx_stride, const float* x_raw, const float* p, int64_t n, float* dRaw,
+                       int64_t col_offset, int64_t voxel_stride, bfm_stream_t stream);
 int bfm_conv3x3x3_wgrad(const float* dP, int Cout, const float* A, int CA, const float* B, int CB, int D, int H, int W,
                         const bfm_upsample_t* up, const float* scale, const float* shift, float* dW /*[Cout][Cin][27]*/,
                         void* workspace, size_t workspace_bytes, bfm_stream_t stream);
