@@ -101,6 +101,8 @@ __device__ __forceinline__ void split_store4(const float (&t)[4], unsigned char*
 // the bits its own main loop and transform would have produced -- in the same thread order, and runs the rest of the
 // epilogue (accumulate mode, activation, store, moment rows) on them: no staging, no weights, no matrix products, no LDS.  Two kernels rather than a branch: a second loop body in one kernel made the
 // allocator spill 54 registers and the layer 25 % slower.
+// That replay is for accumulating launches only (a mate adds its own voxels of `out`).  Without accumulation a mate's
+// stored bits are its representative's: conv_wino_rest leaves no sums and class_fill (below) copies the boxes.
 // POOL = 1 (encoder layers whose output nn.MaxPool3d(2) reads next, buildingblocks.py:185-186; box 8 x 8 x 4 with every box
 // inside the tensor, checked by the host): the epilogue also writes the pooled tensor and its moment rows -- the 2 x 2 x 2
 // windows are whole inside a box, so the separate pooling launch and its read of the full-resolution output go away.  A
@@ -150,7 +152,7 @@ __device__ __forceinline__ void conv_wino_body(const WinoParams& p) {
     // its class mates; conv_wino_uniform's list: those mates
     int cls = 0;                                         // 1 + class of a flagged box
     if constexpr (BY_FLAG) cls = __builtin_amdgcn_readfirstlane((int)p.uni_flags[mt]);
-    const bool rep = MODE == 2 && cls != 0;
+    const bool rep = MODE == 2 && cls != 0 && p.accum;   // (no accumulate: class_fill copies the stored box, no sums wanted)
 
     float bmax = 0.f;
     for (int g = 0; g < p.G; ++g) bmax = fmaxf(bmax, p.bound[g]);
@@ -581,6 +583,78 @@ __global__ void __launch_bounds__(NTHR, 2) conv_wino_rest(const WinoParams p) { 
 template <int NPASS>
 __global__ void __launch_bounds__(NTHR, 2) conv_wino_uniform(const WinoParams p) { conv_wino_body<NPASS, 3>(p); }
 
+// conv_wino_uniform[_pool] for a launch that does not accumulate: a class mate's sums, activation, pooling windows and moment
+// rows are then its class representative's, value for value and in the same order, and the representative's are what
+// conv_wino_rest[_pool] has just stored in the same tensors (same stream, so they are complete).  So a mate's box of `out`,
+// its pooled box and its rows of the two moment tables are copies: 16-byte loads (27 representatives x 64 KB per cout
+// tile: they stay in L2) and 16-byte stores, 256 contiguous bytes per voxel and cout tile, no LDS, no arithmetic.
+// Grid as conv_wino_uniform's: one workgroup per (box, cout tile), those beyond the list end after one scalar read.  A box
+// cut by a far face is the last of its axis, and so is its representative: both are clipped alike.
+struct FillParams {
+    float* out;
+    int D, H, W, Cout, NT;
+    int TD, TH, TW, nTy, nTx;
+    int tw_shift, thw_shift;         // log2(TW), log2(TH*TW)
+    const unsigned char* flags;      // UniformFlagBuf: 1 + class of every listed box
+    const int* first;                // [27] the representatives
+    const int* list;                 // the mates, ascending
+    const int* list_n;
+    double *rsum, *rsq;              // optional moment rows [nMt][Cout]
+    float *rmn, *rmx;
+    float* pool_out;                 // optional (box 8 x 8 x 4 tiling the tensor): (D/2,H/2,W/2,Cout) and its rows
+    double *prsum, *prsq;
+    float *prmn, *prmx;
+};
+
+__global__ void __launch_bounds__(NTHR) class_fill(const FillParams p) {
+    const int bid = blockIdx.x;
+    if (bid >= p.list_n[0] * p.NT) return;
+    const int tid = threadIdx.x;
+    const int mt = p.list[bid / p.NT], nt = bid % p.NT;
+    const int rp = p.first[p.flags[mt] - 1];
+    const int z0 = (mt / (p.nTx * p.nTy)) * p.TD, y0 = ((mt / p.nTx) % p.nTy) * p.TH, x0 = (mt % p.nTx) * p.TW;
+    const int rz0 = (rp / (p.nTx * p.nTy)) * p.TD, ry0 = ((rp / p.nTx) % p.nTy) * p.TH, rx0 = (rp % p.nTx) * p.TW;
+    const int c4 = tid & 15;                                       // 16-byte piece of the 64 couts
+    {
+        const size_t dbase = (((size_t)z0 * p.H + y0) * p.W + x0) * p.Cout + nt * 64 + c4 * 4;
+        const size_t sbase = (((size_t)rz0 * p.H + ry0) * p.W + rx0) * p.Cout + nt * 64 + c4 * 4;
+        for (int r = 0; r < 4; ++r) {                              // 256 voxels = 4 rounds x 4 x 16 per workgroup
+            float4 v[4];
+            size_t off[4];
+            bool in[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int vox = (r * 4 + k) * 16 + (tid >> 4);
+                const int w = vox & (p.TW - 1), h = (vox >> p.tw_shift) & (p.TH - 1), d = vox >> p.thw_shift;
+                in[k] = z0 + d < p.D && y0 + h < p.H && x0 + w < p.W;
+                off[k] = (((size_t)d * p.H + h) * p.W + w) * p.Cout;
+                v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (in[k]) v[k] = *reinterpret_cast<const float4*>(p.out + sbase + off[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (in[k]) *reinterpret_cast<float4*>(p.out + dbase + off[k]) = v[k];
+        }
+    }
+    if (p.pool_out != nullptr) {                                   // 4 x 4 x 2 pooled voxels: 2 x 16 per workgroup, no clipping
+        const int H2 = p.H >> 1, W2 = p.W >> 1;
+        const size_t dbase = (((size_t)(z0 >> 1) * H2 + (y0 >> 1)) * W2 + (x0 >> 1)) * p.Cout + nt * 64 + c4 * 4;
+        const size_t sbase = (((size_t)(rz0 >> 1) * H2 + (ry0 >> 1)) * W2 + (rx0 >> 1)) * p.Cout + nt * 64 + c4 * 4;
+        const int vox = tid >> 4;                                  // and vox + 16: two slices further
+        const size_t off0 = (((size_t)(vox >> 3) * H2 + ((vox >> 1) & 3)) * W2 + (vox & 1)) * p.Cout;
+        const size_t off1 = off0 + (size_t)2 * H2 * W2 * p.Cout;
+        const float4 v0 = *reinterpret_cast<const float4*>(p.pool_out + sbase + off0);
+        const float4 v1 = *reinterpret_cast<const float4*>(p.pool_out + sbase + off1);
+        *reinterpret_cast<float4*>(p.pool_out + dbase + off0) = v0;
+        *reinterpret_cast<float4*>(p.pool_out + dbase + off1) = v1;
+    }
+    if (tid < 64) {                                                // the box's rows of the moment tables, this cout tile
+        const size_t d = (size_t)mt * p.Cout + nt * 64 + tid, s = (size_t)rp * p.Cout + nt * 64 + tid;
+        if (p.rsum != nullptr) { p.rsum[d] = p.rsum[s]; p.rsq[d] = p.rsq[s]; p.rmn[d] = p.rmn[s]; p.rmx[d] = p.rmx[s]; }
+        if (p.prsum != nullptr) { p.prsum[d] = p.prsum[s]; p.prsq[d] = p.prsq[s]; p.prmn[d] = p.prmn[s]; p.prmx[d] = p.prmx[s]; }
+    }
+}
+
 // Work lists for the sparse forms: list[] = the boxes with pred(box), ascending; returns their number (thread 0's value
 // is the total).  One workgroup of 1024 threads; `sh` = 17 ints of LDS.
 template <class Pred>
@@ -673,24 +747,142 @@ __global__ void __launch_bounds__(256) uniform_boxes_kernel(const float* __restr
 // first[c] = index of the first box of class c (n: none), and the two work lists of the pair of launches that uses the
 // flags: cnt[0], rest[] = the unflagged boxes and every class's first flagged box (conv_wino_rest: computed in full);
 // cnt[1], uni[] = the other flagged boxes (conv_wino_uniform: their class's sums through the epilogue).  One workgroup.
+// (AGENT: the flags were written by other workgroups of this launch -- uniform_levels_kernel -- and are read past the L2s
+// that may not have seen them)
+template <bool AGENT>
+__device__ __forceinline__ void uniform_lists_body(const unsigned char* flags, int n, int* __restrict__ first,
+                                                   int* __restrict__ cnt, int* __restrict__ rest, int* __restrict__ uni,
+                                                   int* sh, int* fst) {
+    auto flag = [&](int i) -> int {
+        if constexpr (AGENT) return __hip_atomic_load(flags + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else return flags[i];
+    };
+    if (threadIdx.x < 27) fst[threadIdx.x] = n;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const int f = flag(i);
+        if (f != 0) atomicMin(&fst[f - 1], i);              // integer minimum: order independent
+    }
+    __syncthreads();
+    if (threadIdx.x < 27) first[threadIdx.x] = fst[threadIdx.x];
+    const int n0 = wino_compact(n, [&](int mt) { const int f = flag(mt); return f == 0 || fst[f - 1] == mt; }, rest, sh);
+    if (threadIdx.x == 0) cnt[0] = n0;
+    __syncthreads();
+    const int n1 = wino_compact(n, [&](int mt) { const int f = flag(mt); return f != 0 && fst[f - 1] != mt; }, uni, sh);
+    if (threadIdx.x == 0) cnt[1] = n1;
+}
+
 __global__ void __launch_bounds__(1024) uniform_lists_kernel(const unsigned char* __restrict__ flags, int n,
                                                              int* __restrict__ first, int* __restrict__ cnt,
                                                              int* __restrict__ rest, int* __restrict__ uni) {
     __shared__ int sh[17];
     __shared__ int fst[27];
-    if (threadIdx.x < 27) fst[threadIdx.x] = n;
+    uniform_lists_body<false>(flags, n, first, cnt, rest, uni, sh, fst);
+}
+
+// uniform_boxes_kernel + uniform_lists_kernel for every level of one image in one launch (a tile asks for levels 0 and 1:
+// four launches at the head of its chain become one).  A workgroup is four groups of 256 threads, a group tests one box at
+// a time as uniform_boxes_kernel's workgroup does (same region, same flag), `per` boxes one after the other -- 4 at level
+// 0, 1 below, where a box's region is 12 times larger -- so a launch has ~1 500 workgroups and as many arrivals on the
+// ticket, not one per box (16 000 arrivals on one counter cost more than the launches they replaced:
+// profiles/r05_small_measurements.txt).  The last workgroup to arrive builds every level's class table and lists, in box
+// order as uniform_lists_kernel does: nothing depends on which workgroup that is.  *ticket is 0 on entry and left 0.
+constexpr int UL_MAX = 4;       // levels per launch
+constexpr int UL_LOADS = 8;     // loads a thread has in flight
+struct UniLevel {
+    int TD, TH, TW, nTz, nTy, nTx, L, R;
+    int n, per, wg0;                 // boxes, boxes per group, first workgroup of the level
+    unsigned char* flags;
+    int* first;                      // UniformFlagBuf{flags, n}.first()
+};
+struct UniLevels {
+    const float* img;
+    int D, H, W, nlev, nwg;
+    int* ticket;
+    UniLevel lv[UL_MAX];
+};
+
+__global__ void __launch_bounds__(1024) uniform_levels_kernel(const UniLevels p) {
+    __shared__ int sh[17];
+    __shared__ int fst[27];
+    __shared__ int bad_w[16];
+    __shared__ int is_last;
+    const int tid = threadIdx.x, grp = tid >> 8, t = tid & 255;
+    int li = 0;
+    for (int i = 1; i < p.nlev; ++i)
+        if ((int)blockIdx.x >= p.lv[i].wg0) li = i;
+    const UniLevel& v = p.lv[li];
+    const int D = p.D, H = p.H, W = p.W, L = v.L, R = v.R;
+    const int box0 = ((int)blockIdx.x - v.wg0) * 4 * v.per;
+    for (int r = 0; r < v.per; ++r) {                          // (workgroup-uniform trip count: barriers inside)
+        const int mt = box0 + r * 4 + grp;
+        const bool live = mt < v.n;
+        int bad = 0;
+        int tx = 0, ty = 0, tz = 0;
+        if (live) {
+            tx = mt % v.nTx; ty = (mt / v.nTx) % v.nTy; tz = mt / (v.nTx * v.nTy);
+            const int z0 = max(((tz * v.TD) << L) - R, 0), y0 = max(((ty * v.TH) << L) - R, 0);
+            const int x0 = max(((tx * v.TW) << L) - R, 0);
+            const int z1 = min((((tz + 1) * v.TD) << L) + R, D), y1 = min((((ty + 1) * v.TH) << L) + R, H);
+            const int x1 = min((((tx + 1) * v.TW) << L) + R, W);
+            const int eh = y1 - y0, ew = x1 - x0, nq = (z1 - z0) * eh * ew;
+            const unsigned ref = __float_as_uint(p.img[((int64_t)z0 * H + y0) * W + x0]);
+            // voxel q = t + 256 j of the region, j = 0, 1, ...: (w, h, d) advance by the digits of 256 in the region's mixed
+            // radix instead of being divided out of q for every load (the divisions were most of uniform_boxes_kernel's
+            // instructions); eight loads in flight; a wave that has seen a difference stops
+            int w = t % ew, h = (t / ew) % eh, d = (t / ew) / eh;
+            const int sw = 256 % ew, sh_ = (256 / ew) % eh, sd = (256 / ew) / eh;
+            const float* const base = p.img + ((int64_t)z0 * H + y0) * W + x0;
+            for (int qb = 0; qb < nq && !bad; qb += UL_LOADS * 256) {
+                unsigned val[UL_LOADS];
+#pragma unroll
+                for (int k = 0; k < UL_LOADS; ++k) {
+                    val[k] = ref;
+                    if (qb + k * 256 + t < nq) val[k] = __float_as_uint(base[(unsigned)(d * H + h) * (unsigned)W + (unsigned)w]);
+                    w += sw;
+                    if (w >= ew) { w -= ew; ++h; }
+                    h += sh_;
+                    if (h >= eh) { h -= eh; ++d; }
+                    d += sd;
+                }
+                int diff = 0;
+#pragma unroll
+                for (int k = 0; k < UL_LOADS; ++k) diff |= val[k] != ref ? 1 : 0;
+                bad = __any(diff) ? 1 : 0;
+            }
+        }
+        if ((tid & 63) == 0) bad_w[tid >> 6] = bad;
+        __syncthreads();
+        if (live && t == 0) {
+            const int any_bad = bad_w[grp * 4] | bad_w[grp * 4 + 1] | bad_w[grp * 4 + 2] | bad_w[grp * 4 + 3];
+            const int cz = tz == 0 ? 0 : (tz == v.nTz - 1 ? 2 : 1), cy = ty == 0 ? 0 : (ty == v.nTy - 1 ? 2 : 1);
+            const int cx = tx == 0 ? 0 : (tx == v.nTx - 1 ? 2 : 1);
+            const int dl = (D >> L) << L, hl = (H >> L) << L, wl = (W >> L) << L;          // (see uniform_boxes_kernel)
+            const bool far = (tz != v.nTz - 1 && ((((tz + 1) * v.TD) << L) + R > dl)) ||
+                             (ty != v.nTy - 1 && ((((ty + 1) * v.TH) << L) + R > hl)) ||
+                             (tx != v.nTx - 1 && ((((tx + 1) * v.TW) << L) + R > wl));
+            __hip_atomic_store(v.flags + mt, any_bad || far ? (unsigned char)0 : (unsigned char)(1 + 9 * cz + 3 * cy + cx),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();                                           // bad_w is rewritten by the next round
+    }
+    // publish the flags and take a ticket (rows_group_finalize's protocol, gn_stats.hip)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int i = threadIdx.x; i < n; i += 1024) {
-        const int f = flags[i];
-        if (f != 0) atomicMin(&fst[f - 1], i);              // integer minimum: order independent
+    if (tid == 0) {
+        const int got = __hip_atomic_fetch_add(p.ticket, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        is_last = got == p.nwg - 1;
+        if (is_last) __hip_atomic_store(p.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
-    if (threadIdx.x < 27) first[threadIdx.x] = fst[threadIdx.x];
-    const int n0 = wino_compact(n, [&](int mt) { const int f = flags[mt]; return f == 0 || fst[f - 1] == mt; }, rest, sh);
-    if (threadIdx.x == 0) cnt[0] = n0;
-    __syncthreads();
-    const int n1 = wino_compact(n, [&](int mt) { const int f = flags[mt]; return f != 0 && fst[f - 1] != mt; }, uni, sh);
-    if (threadIdx.x == 0) cnt[1] = n1;
+    if (!is_last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    for (int i = 0; i < p.nlev; ++i) {
+        const int n = p.lv[i].n;
+        int* const first = p.lv[i].first;                          // UniformFlagBuf: first[27] | counts[2] | rest[n] | uniform[n]
+        uniform_lists_body<true>(p.lv[i].flags, n, first, first + 27, first + 29, first + 29 + n, sh, fst);
+        __syncthreads();                                           // sh and fst start over
+    }
 }
 
 // packed[ntile64][pos 4][kc][(kd,kh) 9][nb 2][hl][lane] (uint4 = 8 halfs): lane l holds
@@ -886,6 +1078,45 @@ extern "C" int bfm_uniform_boxes(const float* image, int D, int H, int W, int ra
     return bfm_uniform_boxes_level(image, D, H, W, 0, radius, passes, flags, stream);
 }
 
+// bfm_uniform_boxes_level for nlevels levels of one image (ascending or not, each at most once in practice) in one launch:
+// flags[i] receives what bfm_uniform_boxes_level(levels[i], radii[i]) writes, byte for byte.  ticket: one int on the device,
+// zero before the first call and left zero by every call; calls that may run at the same time take different tickets.
+extern "C" int bfm_uniform_boxes_levels(const float* image, int D, int H, int W, int nlevels, const int* levels,
+                                        const int* radii, int passes, unsigned char* const* flags, int* ticket,
+                                        bfm_stream_t stream) {
+    if (!image || !levels || !radii || !flags || !ticket || D <= 0 || H <= 0 || W <= 0 || nlevels < 1 || nlevels > UL_MAX)
+        return BFM_E_ARG;
+    if (reinterpret_cast<uintptr_t>(ticket) & 3) return BFM_E_ARG;
+    if ((int64_t)D * H * W > 0x7fffffffLL) return BFM_E_SHAPE;                     // 32-bit offsets inside a box's region
+    UniLevels p{};
+    p.img = image; p.D = D; p.H = H; p.W = W; p.nlev = nlevels; p.ticket = ticket;
+    int64_t nwg = 0;
+    for (int i = 0; i < nlevels; ++i) {
+        const int level = levels[i], radius = radii[i];
+        if (!flags[i] || radius < 0 || radius > 64 || level < 0 || level > 4) return BFM_E_ARG;
+        if (reinterpret_cast<uintptr_t>(flags[i]) & 3) return BFM_E_ARG;
+        const int d = D >> level, h = H >> level, w = W >> level;
+        UniLevel& v = p.lv[i];
+        if (d <= 0 || h <= 0 || w <= 0 || !choose_box(d, h, w, passes == 3 ? 2 : 1, v.TD, v.TH, v.TW)) return BFM_E_SHAPE;
+        if ((v.TD << level) < radius || (v.TH << level) < radius || (v.TW << level) < radius) return BFM_E_SHAPE;
+        v.nTz = bfm_cdiv(d, v.TD); v.nTy = bfm_cdiv(h, v.TH); v.nTx = bfm_cdiv(w, v.TW);
+        v.L = level; v.R = radius; v.flags = flags[i];
+        const int64_t n = (int64_t)v.nTz * v.nTy * v.nTx;
+        if (n > 0x7fffffff) return BFM_E_SHAPE;
+        v.n = (int)n;
+        v.first = UniformFlagBuf{flags[i], (size_t)n}.first();
+        v.per = level == 0 ? 4 : 1;
+        v.wg0 = (int)nwg;
+        nwg += bfm_cdiv64(n, 4 * v.per);
+    }
+    p.nwg = (int)nwg;
+    hipStream_t st = bfm_s(stream);
+    hipLaunchKernelGGL(uniform_levels_kernel, dim3((unsigned)nwg), dim3(1024), 0, st, p);
+    const int rc = bfm_launch_status();
+    if (rc != BFM_OK) (void)hipMemsetAsync(ticket, 0, sizeof(int), st);           // never leave a partial count behind
+    return rc;
+}
+
 extern "C" size_t bfm_conv3x3x3_wino_uniform_scratch(int Cout) {
     return Cout > 0 && Cout % 64 == 0 ? (size_t)27 * (Cout / 64) * 2 * 16 * NTHR * 2 * sizeof(float) : 0;
 }
@@ -956,11 +1187,23 @@ static int wino_launch(const WinoLaunch& a) {
         bfm_launch_by_passes(passes, conv_wino_masked<3>, conv_wino_masked<1>, grid, block, smem, st, p);
         return bfm_launch_status();
     }
-    if (fb.flags) {                                            // disjoint boxes: the two launches may overlap
+    if (fb.flags) {
         p.list = fb.rest_list(); p.list_n = fb.counts();
         if (a.pool.out) bfm_launch_by_passes(passes, conv_wino_rest_pool<3>, conv_wino_rest_pool<1>, grid, block, smem, st, p);
         else bfm_launch_by_passes(passes, conv_wino_rest<3>, conv_wino_rest<1>, grid, block, smem, st, p);
         p.list = fb.uniform_list(); p.list_n = fb.counts() + 1;
+        if (!p.accum) {                                        // the mates are copies of what the launch above stored
+            FillParams f{};
+            f.out = p.out; f.D = D; f.H = H; f.W = W; f.Cout = Cout; f.NT = p.NT;
+            f.TD = p.TD; f.TH = p.TH; f.TW = p.TW; f.nTy = p.nTy; f.nTx = p.nTx;
+            f.tw_shift = ilog2i(p.TW); f.thw_shift = ilog2i(p.TH * p.TW);
+            f.flags = fb.flags; f.first = fb.first(); f.list = p.list; f.list_n = p.list_n;
+            f.rsum = p.rsum; f.rsq = p.rsq; f.rmn = p.rmn; f.rmx = p.rmx;
+            f.pool_out = p.pool_out; f.prsum = p.prsum; f.prsq = p.prsq; f.prmn = p.prmn; f.prmx = p.prmx;
+            hipLaunchKernelGGL(class_fill, grid, block, 0, st, f);
+            return bfm_launch_status();
+        }
+        // accumulate mode: a mate adds its own voxels of `out`, so it runs the epilogue on its class's sums (disjoint boxes)
         // conv_wino_uniform's LDS: its row fold; with the pooling, the windows' exchange and the pooled rows' fold behind it
         if (a.pool.out) bfm_launch_by_passes(passes, conv_wino_uniform_pool<3>, conv_wino_uniform_pool<1>, grid, block, 20480, st, p);
         else bfm_launch_by_passes(passes, conv_wino_uniform<3>, conv_wino_uniform<1>, grid, block, 6144, st, p);

@@ -186,6 +186,7 @@ class UNetEngine:
         # arrival counters of the one-launch GroupNorm rows form, made here -- outside any graph capture -- for the lanes a
         # session may use (zero on first use, left zero by every call)
         self._gn_tickets = {ln: torch.zeros(16, dtype=torch.int32, device=self.device) for ln in range(4)}
+        self._uf_tickets = {ln: torch.zeros(1, dtype=torch.int32, device=self.device) for ln in range(4)}
         self.gn_one_launch = os.environ.get("BFM_GN_ONE_LAUNCH", "1") != "0"
         self._plan_cache = {}
         self._tuned = set()
@@ -391,6 +392,13 @@ class UNetEngine:
                 self._ws_retired.append(ws)       # captured graphs of smaller shapes keep pointing into it
             ws = self._ws_lanes[self.lane] = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=self.device)
         return ws
+
+    def _uf_ticket(self):
+        """The arrival counter of bfm_uniform_boxes_levels, as _gn_ticket: zero before its first use, left zero, one per lane."""
+        t = self._uf_tickets
+        if self.lane not in t:
+            t[self.lane] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return t[self.lane]
 
     def _gn_ticket(self):
         """The arrival counter of bfm_gn_stats_rows' one-launch form: zero before its first use, left zero by every
@@ -807,6 +815,23 @@ class UNetEngine:
         if ckey in cache:
             return cache[ckey]
         D, H, W = dims
+        # every level the net will ask for, in one launch (their flags go into the cache under their own keys); a level
+        # without a box grid or with boxes shorter than its radius sends each level through its own call below
+        lv = sorted({k[1] for k in self.UNIFORM_RADIUS})
+        rad = [max(r for k, r in self.UNIFORM_RADIUS.items() if k[1] == l) for l in lv]
+        if level in lv and radius == rad[lv.index(level)]:
+            nb = [self.lib.bfm_uniform_boxes_bytes(D >> l, H >> l, W >> l, self.passes) for l in lv]
+            if min(nb) > 0:
+                bufs = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in nb]
+                rc = self.lib.bfm_uniform_boxes_levels(L.ptr(x_cl), D, H, W, len(lv), (C.c_int * len(lv))(*lv),
+                                                       (C.c_int * len(lv))(*rad), self.passes,
+                                                       (C.c_void_p * len(lv))(*[b.data_ptr() for b in bufs]),
+                                                       L.ptr(self._uf_ticket()), L.stream_ptr())
+                if rc != -2:
+                    L.check(rc, "uniform_boxes_levels")
+                    for l, r, b in zip(lv, rad, bufs):
+                        cache[ckey[:2] + (int(l), int(r)) + ckey[4:]] = b
+                    return cache[ckey]
         n = self.lib.bfm_uniform_boxes_bytes(D >> level, H >> level, W >> level, self.passes)
         if n <= 0:
             return None

@@ -124,8 +124,10 @@ int bfm_conv3x3x3_wino_ex(const float* A, int CA, int D, int H, int W, const flo
  * bfm_uniform_boxes_bytes() bytes, 4-byte aligned: one byte per box, then the first box of each of the 27 classes.
  * bfm_conv3x3x3_wino_uniform is bfm_conv3x3x3_wino_ex that computes the unflagged boxes and the first flagged box of each
  * class in full, and gives every other flagged box its class's accumulators (the bits its own main loop would produce: same
- * operands, same order) before the normal epilogue -- no staging, weights or matrix products there.  scratch:
- * bfm_conv3x3x3_wino_uniform_scratch(Cout) bytes, 16-byte aligned.  The caller passes radius = (number of 3x3x3
+ * operands, same order) before the normal epilogue -- no staging, weights or matrix products there.  Without accumulation
+ * (flags bit 0 clear) those boxes' outputs, pooled outputs and moment rows are the first box's, and are copied from it.
+ * scratch: bfm_conv3x3x3_wino_uniform_scratch(Cout) bytes, 16-byte aligned (written by accumulating calls only).  The
+ * caller passes radius = (number of 3x3x3
  * convolutions between the image and this layer's OUTPUT): 2 for encoders.0's second conv, 3 for the skip half of the last
  * decoder's first conv. */
 size_t bfm_uniform_boxes_bytes(int D, int H, int W, int passes);
@@ -138,6 +140,14 @@ int bfm_uniform_boxes(const float* image, int D, int H, int W, int radius, int p
  * bfm_uniform_boxes_bytes(D >> level, H >> level, W >> level, passes) bytes. */
 int bfm_uniform_boxes_level(const float* image, int D, int H, int W, int level, int radius, int passes, unsigned char* flags,
                             bfm_stream_t stream);
+/* bfm_uniform_boxes_level for several levels of one image in one launch (a tile's encoder pools its first activations once,
+ * Encoder.forward, buildingblocks.py:185-186, so levels 0 and 1 both have layers that read them): flags[i] receives, byte
+ * for byte, what bfm_uniform_boxes_level(levels[i], radii[i]) writes.  1 <= nlevels <= 4; levels, radii and flags are host
+ * arrays.  ticket: one int on the device, 4-byte aligned, zero before the first call and left zero by every call; calls
+ * that may run concurrently take different tickets.  BFM_E_SHAPE when any level has no box grid or a box side shorter than
+ * its radius (nothing launched: ask level by level then). */
+int bfm_uniform_boxes_levels(const float* image, int D, int H, int W, int nlevels, const int* levels, const int* radii,
+                             int passes, unsigned char* const* flags, int* ticket, bfm_stream_t stream);
 size_t bfm_conv3x3x3_wino_uniform_scratch(int Cout);
 int bfm_conv3x3x3_wino_uniform(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
                                const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
