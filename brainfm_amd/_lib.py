@@ -293,6 +293,9 @@ SIGNATURES = {
     "bfm_age_mlp_bwd_workspace": (_Z, []),
     "bfm_age_mlp_bwd": (_I, [_P, _I, C.POINTER(AgeParams), _I, _P, _P, _P, _P, C.c_double, _F, _P, C.POINTER(AgeGrads),
                              _P, _P, _Z, _P]),
+    "bfm_head_bias_lrelu": (_I, [_P, _P, _I, _L, _F, _P, _P, _P]),
+    "bfm_head_bias_lrelu_bwd_workspace": (_Z, [_I, _L]),
+    "bfm_head_bias_lrelu_bwd": (_I, [_P, _P, _I, _L, _F, _P, _P, _P, _P, _Z, _P]),
 }
 
 _lib = None

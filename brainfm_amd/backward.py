@@ -366,3 +366,58 @@ def backbone_backward(eng, tape, dfeats, input_grad=None):
                                              L.ptr(dIn), L.stream_ptr()), "maxpool2_bwd")
             g = dIn
     return grads
+
+
+def backward_head_layer(eng, hl, x, x_bound, y, dY, dims, need_input_grad=True):
+    """Backward of one hidden task-head layer (torch autograd over head.py:161-167: Conv3d(3, p=1, bias) + LeakyReLU(0.2), no
+    GroupNorm).  x (D,H,W,cin): the layer's input, x_bound: device float >= max |x| (the forward's bound); y: its output;
+    dY: the gradient of y.  One pass forms dP, max |dP| and dbias (bfm_head_bias_lrelu_bwd); dW = bfm_conv3x3x3_wgrad_ex
+    and dX = the data-gradient convolution, both with the identity affine; the convolution's variant comes from the
+    engine's fixed shape rule (_head_cfg), never from a timing.  Returns (dX or None, {name: gradient})."""
+    from .engine import HEAD_SLOPE
+    D, H, W = dims
+    nv = D * H * W
+    dev, lib, st = eng.device, eng.lib, L.stream_ptr()
+    sink = getattr(eng, "grad_sink", None)
+
+    def slot(name, shape):
+        return sink.out(name, shape) if sink is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+
+    dY = dY.contiguous()
+    dP = torch.empty_like(dY)
+    bnd = torch.empty(1, dtype=torch.float32, device=dev)
+    db = slot(hl.name + ".bias", (hl.cout,))
+    wsb = torch.empty(max(lib.bfm_head_bias_lrelu_bwd_workspace(hl.cout, nv), 256), dtype=torch.uint8, device=dev)
+    L.check(lib.bfm_head_bias_lrelu_bwd(L.ptr(dY), L.ptr(y), hl.cout, nv, HEAD_SLOPE, L.ptr(dP), L.ptr(db), L.ptr(bnd),
+                                        L.ptr(wsb), wsb.numel(), st), "head_bias_lrelu_bwd " + hl.name)
+    if sink is not None:
+        sink.done(hl.name + ".bias")
+    ones, zeros = _identity_affine(eng, hl.cin)
+    ws = torch.empty(max(lib.bfm_conv3x3x3_wgrad_workspace(hl.cin, hl.cout, D, H, W), 256), dtype=torch.uint8, device=dev)
+    dW = slot(hl.name + ".weight", (hl.cout, hl.cin, 3, 3, 3))
+    L.check(lib.bfm_conv3x3x3_wgrad_ex(L.ptr(dP), hl.cout, L.ptr(x), hl.cin, None, 0, D, H, W, None, L.ptr(ones),
+                                       L.ptr(zeros), L.ptr(bnd), L.ptr(x_bound), 1, WGRAD_PASSES, L.ptr(dW), L.ptr(ws),
+                                       ws.numel(), st), "conv_wgrad " + hl.name)
+    if sink is not None:
+        sink.done(hl.name + ".weight")
+    grads = OrderedDict([(hl.name + ".weight", dW), (hl.name + ".bias", db)])
+    if not need_input_grad:
+        return None, grads
+    dg = hl.packs.get("dgrad_layer")
+    if dg is None:
+        dg = hl.packs["dgrad_layer"] = _dgrad_layer(eng, hl)
+    hl.touch("dgrad_layer")
+    ones_o, zeros_o = _identity_affine(eng, hl.cout)
+    dX = torch.empty((D, H, W, dg.cout), dtype=torch.float32, device=dev)
+    if hl.cout % 16 == 0 and dg.cout % 64 == 0:
+        cfg = eng._head_cfg(dg, dims)
+        ws2 = torch.empty(max(lib.bfm_conv3x3x3_mfma_workspace(hl.cout, dg.cout, D, H, W, cfg[5]), 256), dtype=torch.uint8,
+                          device=dev)
+        eng._conv_launch(dg, dP, hl.cout, None, 0, dims, None, ones_o, zeros_o, bnd, 1, cfg, dX, ws2, None, slope=1.0)
+        if dg.cout != hl.cin:
+            dX = dX[..., :hl.cin].contiguous()
+    else:
+        eng._pack(dg, False)
+        L.check(lib.bfm_conv3x3x3_direct(L.ptr(dP), hl.cout, None, 0, D, H, W, None, L.ptr(ones_o), L.ptr(zeros_o),
+                                         L.ptr(dg.wpacked), hl.cin, 1.0, L.ptr(dX), st), "conv dgrad(direct) " + hl.name)
+    return dX, grads

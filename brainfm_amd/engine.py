@@ -141,6 +141,15 @@ class _Layer:
         u.add(layout)
 
 
+HEAD_SLOPE = 0.2            # nn.LeakyReLU(0.2) of a hidden head layer (head.py:162)
+
+
+class _HeadLayer(_Layer):
+    """One hidden task-head layer (head.py:152-167, `head.layers.{i}.main`): a conv layer without GroupNorm (gamma and
+    beta stay None, one group) that has a bias."""
+    __slots__ = ("bias",)
+
+
 class UNetEngine:
     """Weights + kernels for UNet3D('gcl') inference.
 
@@ -159,7 +168,11 @@ class UNetEngine:
     _same_box_cache = None
     _uf_cache = None
     _deep_ok = None
-    tape = None                 # training (backward.py): list that single_conv / maxpool append their records to
+    _head_layers = None         # (task_f_maps, [_HeadLayer]) once a head with hidden layers asked for them (head_layers)
+    _unit_bound = None
+    _no_heads = None
+    dense_last = False
+    tape = None                # training (backward.py): list that single_conv / maxpool append their records to
     grad_sink = None            # training (train.GradStore through train._Sink): where the backward kernels put gradients
     prof_reps = 1
     use_upfold = False
@@ -216,6 +229,9 @@ class UNetEngine:
             self.dec.append([self._make_layer(sd, "backbone.decoders.%d.basic_module.SingleConv1" % i, ci, co),
                              self._make_layer(sd, "backbone.decoders.%d.basic_module.SingleConv2" % i, co, co)])
         self.sd = sd
+        # a head with hidden layers (task_f_maps longer than one) reads a one-voxel halo around every box it computes:
+        # the backbone's last convolution then never leaves boxes out (backbone_cl(mask_last=True) runs dense)
+        self.dense_last = any(k.startswith("head.layers.") for k in sd)
 
     # ------------------------------------------------------------------ weights
     @staticmethod
@@ -317,7 +333,9 @@ class UNetEngine:
         jobs = []                                          # (layer, layout, max|w| tensor)
         self.weights_epoch += 1
 
-        slots = torch.zeros(4 * (len(self.enc) + len(self.dec)) * 4 + 16, dtype=torch.float32, device=self.device)
+        hidden = self._head_layers[1] if self._head_layers is not None else []
+        slots = torch.zeros(4 * (len(self.enc) + len(self.dec) + len(hidden)) * 4 + 16, dtype=torch.float32,
+                            device=self.device)
         nslot = [0]
 
         def absmax(t):                                     # one launch per tensor into its slot of one vector
@@ -359,7 +377,7 @@ class UNetEngine:
                 ly.skip.w_raw.copy_(ly.w_raw[:, :ly.skip.cin])
                 visit(ly.skip)
 
-        for pair in self.enc + self.dec:
+        for pair in self.enc + self.dec + [hidden]:
             for ly in pair:
                 visit(ly)
         host = slots[:nslot[0]].cpu().tolist() if nslot[0] else []
@@ -1207,6 +1225,7 @@ class UNetEngine:
         if self.has_deep_region():
             return self.backbone_batch([x_cl], dims, mask_last=mask_last)[0]
         self._uf_cache = {}                                  # flags live for one pass (keyed by the image's address)
+        mask_last = mask_last and not self.dense_last
         mask_img = x_cl if (mask_last and self.mask_skip and x_cl.shape[-1] == 1) else None
         skips = self.encoder_top(x_cl, dims, len(self.enc))  # no batched region: every level, then every decoder
         x, d = skips.pop()
@@ -1254,6 +1273,7 @@ class UNetEngine:
         remaining decoders per sample.  Returns one feature list per sample (deepest first, like backbone_cl).
         mask_last: as in backbone_cl."""
         self._uf_cache = {}                                  # flags live for one pass (keyed by the image's address)
+        mask_last = mask_last and not self.dense_last
         df = self.region_start(dims)
         tops = [self.encoder_top(x, dims, df) for x in xs]
         out, d, deep_feats = self.deep_region([t[-1] for t in tops], df)
@@ -1281,6 +1301,131 @@ class UNetEngine:
         x = x.to(device=self.device, dtype=torch.float32)
         return x[0].permute(1, 2, 3, 0).contiguous()
 
+    # ------------------------------------------------------------------ hidden task-head layers
+    def head_layers(self, widths):
+        """The _HeadLayer records of TaskHead.layers (head.py:27-31) for task_f_maps = widths, read from the state dict's
+        ``head.layers.{i}.main.{weight,bias}``; made once per engine."""
+        key = tuple(int(w) for w in widths)
+        if self._head_layers is None or self._head_layers[0] != key:
+            layers = []
+            for i in range(len(key) - 1):
+                name = "head.layers.%d.main" % i
+                hl = _HeadLayer()
+                hl.name, hl.cin, hl.cout, hl.groups = name, key[i], key[i + 1], 1
+                if hl.cin % 4 or hl.cout % 4:
+                    raise L.BfmError("task_f_maps %s: the hidden head layers take widths that are multiples of 4" % (list(key),))
+                hl.gamma = hl.beta = None
+                hl.w_raw = self._dev(self.sd[name + ".weight"])
+                hl.bias = self._dev(self.sd[name + ".bias"])
+                if tuple(hl.w_raw.shape) != (hl.cout, hl.cin, 3, 3, 3) or tuple(hl.bias.shape) != (hl.cout,):
+                    raise L.BfmError("%s has shapes %s / %s, expected %s / %s" % (name, tuple(hl.w_raw.shape), tuple(hl.bias.shape),
+                                                                                 (hl.cout, hl.cin, 3, 3, 3), (hl.cout,)))
+                hl.kind, hl.wpacked, hl.wexp, hl.packs, hl.skip = None, None, 0, {}, None
+                layers.append(hl)
+            self._head_layers = (key, layers)
+        return self._head_layers[1]
+
+    def _head_cfg(self, hl, dims):
+        """The conv variant of a hidden head layer, by a fixed rule from the shape alone (never timed: the variants differ
+        in the last bits): F(4,3) conv_wino4d where the volume holds its 8 x 8 x 4 box, conv_mfma elsewhere."""
+        key = ("head", hl.cin, hl.cout, tuple(dims))
+        if key not in self._plan_cache:
+            cfg = (C.c_int * 8)()
+            L.check(self.lib.bfm_conv3x3x3_mfma_plan(hl.cin, hl.cout, dims[0], dims[1], dims[2], cfg), "mfma_plan")
+            box = (C.c_int * 3)()
+            # D, H >= 8 and W >= 4: where bfm_conv3x3x3_wino4 dispatches to conv_wino4d (conv3d_wino4.hip, use_dma_kernel)
+            f43 = (dims[0] >= 8 and dims[1] >= 8 and dims[2] >= 4
+                   and self.lib.bfm_conv3x3x3_wino4_box(dims[0], dims[1], dims[2], self.passes, box) == 0
+                   and list(box) == [8, 8, 4]
+                   and self.lib.bfm_pack_conv_weights_wino4_bytes(hl.cin, hl.cout, self.passes) > 0)
+            cfg[6], cfg[7] = (4 if f43 else 0), 0
+            self._plan_cache[key] = cfg
+        return self._plan_cache[key]
+
+    def unit_bound(self):
+        """A device float holding 1: the prescale bound of a tensor of unit vectors."""
+        if self._unit_bound is None:
+            self._unit_bound = torch.ones(1, dtype=torch.float32, device=self.device)
+        return self._unit_bound
+
+    def absmax(self, x):
+        """max |x| of a contiguous fp32 tensor as a device float (bfm_absmax_f32)."""
+        out = torch.zeros(1, dtype=torch.float32, device=self.device)
+        L.check(self.lib.bfm_absmax_f32(L.ptr(x), 1, x.numel(), x.numel(), L.ptr(out), L.stream_ptr()), "absmax")
+        return out
+
+    def normalize(self, feat_cl, dims):
+        """F.normalize(dim=1) of a (D,H,W,C) map alone: the tail kernel with no heads."""
+        D, H, W = dims
+        c = feat_cl.shape[-1]
+        if c > 64 or c % 8:
+            raise L.BfmError("unit_feat needs c_feat <= 64 and a multiple of 8 (got %d)" % c)
+        if self._no_heads is None:
+            self._no_heads = (torch.zeros(1, dtype=torch.float32, device=self.device),
+                              torch.zeros(1, dtype=torch.int32, device=self.device))
+        z, zi = self._no_heads
+        desc = L.TailDesc(0, c, z.data_ptr(), z.data_ptr(), zi.data_ptr(), zi.data_ptr(), 0, 0, zi.data_ptr(), 0, 0, 0.0,
+                          1, -1, -1, 0)
+        out = torch.empty_like(feat_cl)
+        L.check(self.lib.bfm_tail_heads(L.ptr(feat_cl), None, D * H * W, C.byref(desc), L.ptr(out), None, None, None, None,
+                                        L.stream_ptr()), "normalize")
+        return out
+
+    def run_head_layers(self, layers, feat_cl, dims, mask_img=None, tape=None):
+        """The hidden head layers on the backbone's raw last feature map (D,H,W,C): F.normalize first where the backbone
+        has unit_feat (unet3d/model.py:207-208 runs before the head), then every layer (head.py:54-55).  Returns (the last
+        layer's output, the feature map as the reference's out['feat'][-1] holds it).  mask_img: the caller keeps the
+        heads' outputs only where this (D,H,W) image is non-zero (the tile loop); the last layer leaves out what it can.
+        tape: a list that receives (layer, input, input bound, output) per layer (training)."""
+        if feat_cl.shape[-1] != layers[0].cin:
+            raise L.BfmError("task_f_maps starts at %d channels but the backbone's last feature map has %d"
+                             % (layers[0].cin, feat_cl.shape[-1]))
+        if self.unit_feat:
+            fnorm = self.normalize(feat_cl, dims)
+            bound = self.unit_bound()                        # unit vectors: every |x| <= 1
+        else:
+            fnorm = feat_cl
+            bound = self.absmax(feat_cl)
+        x = fnorm
+        for i, hl in enumerate(layers):
+            last = i + 1 == len(layers)
+            y, nb = self.head_conv(hl, x, dims, bound, mask_img=mask_img if last else None,
+                                   want_bound=(not last) or tape is not None)
+            if tape is not None:
+                tape.append((hl, x, bound, y))
+            x, bound = y, nb
+        return x, fnorm
+
+    def head_conv(self, hl, x, dims, bound, mask_img=None, want_bound=True):
+        """One hidden head layer, Conv3d(3, p=1) + bias + LeakyReLU(0.2) (head.py:161-167), on x (D,H,W,cin) whose
+        max |x| the device float `bound` holds: the convolution through the matrix-core kernels with the identity affine
+        and slope 1 (widths they do not take: conv_direct), then bfm_head_bias_lrelu in place, which also writes the
+        output's own bound.  mask_img: the caller reads the output only where this (D,H,W) image is non-zero; the F(4,3)
+        kernel then leaves out the boxes without such a voxel.  Returns (y, bound of y or None)."""
+        D, H, W = dims
+        st = L.stream_ptr()
+        from .backward import _identity_affine
+        ones, zeros = _identity_affine(self, hl.cin)
+        out = torch.empty((D, H, W, hl.cout), dtype=torch.float32, device=self.device)
+        if self._mfma_ok(hl, hl.cin, 0):
+            cfg = self._head_cfg(hl, dims)
+            ws = self._workspace(self.lib.bfm_conv3x3x3_mfma_workspace(hl.cin, hl.cout, D, H, W, cfg[5]))
+            if mask_img is not None and not (cfg[6] == 4 and self.mask_skip and self.tape is None):
+                mask_img = None
+            self._bracket(lambda: self._conv_launch(hl, x, hl.cin, None, 0, dims, None, ones, zeros, bound, 1, cfg, out, ws,
+                                                    None, slope=1.0, mask_img=mask_img),
+                          lambda: (2.0 * 27 * hl.cin * hl.cout * D * H * W, 4.0 * D * H * W * (hl.cin + hl.cout),
+                                   hl.name.replace("head.", ""), hl.cin, hl.cout, dims, cfg))
+        else:
+            mask_img = None
+            self._pack(hl, False)
+            L.check(self.lib.bfm_conv3x3x3_direct(L.ptr(x), hl.cin, None, 0, D, H, W, None, L.ptr(ones), L.ptr(zeros),
+                                                  L.ptr(hl.wpacked), hl.cout, 1.0, L.ptr(out), st), "conv_direct " + hl.name)
+        nb = torch.empty(1, dtype=torch.float32, device=self.device) if want_bound else None
+        L.check(self.lib.bfm_head_bias_lrelu(L.ptr(out), L.ptr(hl.bias), hl.cout, D * H * W, HEAD_SLOPE, L.ptr(mask_img),
+                                             L.ptr(nb), st), "head_bias_lrelu " + hl.name)
+        return out, nb
+
     # ------------------------------------------------------------------ tail
     def make_tail(self, out_channels, left_hemis_only=False, max_surf_distance=3.0, uncertainty=False):
         return Tail(self, out_channels, left_hemis_only, max_surf_distance)
@@ -1288,13 +1433,18 @@ class UNetEngine:
 
 class Tail:
     """Head weights + role table for bfm_tail_heads (data-driven head set)."""
+    hidden = ()                 # the engine's _HeadLayer records when the head has hidden layers (TaskHead.tail sets it)
 
-    def __init__(self, eng, out_channels, left_hemis_only, max_surf_distance):
+    def __init__(self, eng, out_channels, left_hemis_only, max_surf_distance, c_feat=None, unit_feat=None):
+        """c_feat / unit_feat: a head with hidden layers (task_f_maps longer than one) applies the 1x1x1 heads to the last
+        hidden layer's task_f_maps[-1] channels, which are not normalised again (head.py:53-59); the defaults are the
+        backbone's last width and its unit_feat."""
         self.eng = eng
         dev = eng.device
         sd = eng.sd
         self.out_channels = OrderedDict(out_channels)
-        c_feat = eng.fm[0]
+        c_feat = eng.fm[0] if c_feat is None else int(c_feat)
+        self.unit_feat = bool(eng.unit_feat if unit_feat is None else unit_feat)
         rows_w, rows_b, roles, names = [], [], [], []
         self.row_of = {}
         for task, n in self.out_channels.items():
@@ -1380,7 +1530,7 @@ class Tail:
         self.desc = L.TailDesc(self.n_out, c_feat, self.head_w.data_ptr(), self.head_b.data_ptr(),
                                self.roles.data_ptr(), self.out_slot.data_ptr(), seg[0], seg[1],
                                self.seg_lut.data_ptr(), dist[1], dist[0], float(max_surf_distance),
-                               1 if eng.unit_feat else 0, self.slot_high_res, self.slot_fake, len(self.map_names),
+                               1 if self.unit_feat else 0, self.slot_high_res, self.slot_fake, len(self.map_names),
                                float(self.head_w.abs().max().item()) if self.n_out else 0.0, 0)
 
     def run(self, feat_cl, dims, input_cl=None, want_feat=True, want_seg=True, extra_rows=0, skip_zero_input=False):
@@ -1393,6 +1543,13 @@ class Tail:
         D, H, W = dims
         nvox = D * H * W
         dev = eng.device
+        fn_hidden = None
+        if self.hidden:
+            # hidden head layers: the heads read the last layer's output as it is; the feature map handed back is the
+            # backbone's, normalised.  A tile (skip_zero_input) gives its mask to the last hidden layer
+            mask = input_cl if (skip_zero_input and eng.mask_skip and input_cl is not None and input_cl.numel() == nvox) else None
+            feat_cl, fn_hidden = eng.run_head_layers(self.hidden, feat_cl, dims, mask_img=mask)
+            want_feat_out, want_feat = want_feat, False
         maps_buf = torch.empty((len(self.map_names) + int(extra_rows), D, H, W), dtype=torch.float32, device=dev)
         nseg = self.desc.n_seg
         feat_norm = torch.empty_like(feat_cl) if want_feat else None
@@ -1406,14 +1563,21 @@ class Tail:
                 "tail_heads")
         maps = OrderedDict((n, maps_buf[i]) for i, n in enumerate(self.map_names))
         self.last_buf = maps_buf                      # [n_maps][D,H,W]: the stitcher consumes all rows in one launch
+        if fn_hidden is not None and want_feat_out:
+            feat_norm = fn_hidden
         return maps, feat_norm, seg, label
 
-    def run_raw(self, feat_cl, dims, want_feat=True, rows=False):
+    def run_raw(self, feat_cl, dims, want_feat=True, rows=False, apply_hidden=True):
         """TaskHead.forward only: raw logits (D,H,W,n_out) -- rows=True: (n_out, D*H*W), the training losses' layout --
-        [+ normalised features]."""
+        [+ normalised features].  apply_hidden=False: feat_cl is already the last hidden layer's output (the training
+        step runs the hidden layers itself, for their tape)."""
         eng = self.eng
         D, H, W = dims
-        feat_norm = torch.empty_like(feat_cl) if (want_feat and eng.unit_feat) else None
+        if self.hidden and apply_hidden:
+            hid, fn = eng.run_head_layers(self.hidden, feat_cl, dims)
+            raw, _ = self.run_raw(hid, dims, want_feat=False, rows=rows, apply_hidden=False)
+            return raw, (fn if want_feat else None)
+        feat_norm = torch.empty_like(feat_cl) if (want_feat and self.unit_feat) else None
         if rows:
             raw = torch.empty((self.n_out, D * H * W), dtype=torch.float32, device=eng.device)
             L.check(eng.lib.bfm_tail_raw_rows(L.ptr(feat_cl), D * H * W, C.byref(self.desc), L.ptr(feat_norm), L.ptr(raw),

@@ -388,14 +388,24 @@ class AgeHead:
 
 
 class TaskHead(nn.Module):
-    """TaskHead with task_f_maps=[c]: one 1x1x1 conv + bias per dense task, and the pooled scalar head for a task whose
-    out_channels entry is <= 0 (age; head.py:20-67)."""
+    """TaskHead (head.py:20-67): with task_f_maps = [c0, ..., cn] the hidden layers `layers.{i}.main` = Conv3d(c_i, c_i+1, 3,
+    padding 1, bias) + LeakyReLU(0.2) on the backbone's (normalised) last feature map, then one 1x1x1 conv + bias per dense
+    task over cn channels, and the pooled scalar head for a task whose out_channels entry is <= 0 (age; single-entry
+    task_f_maps only)."""
 
     def __init__(self, args, f_maps_list, out_channels, is_3d=True, out_feat_level=-1, exclude_keys=[], *kwargs):
         super().__init__()
-        if len(f_maps_list) != 1:
-            raise NotImplementedError("hidden head layers (task_f_maps of length > 1) are not on the hot path")
+        self.task_f_maps = [int(v) for v in f_maps_list]
+        if not self.task_f_maps:
+            raise L.BfmError("task_f_maps is empty: it lists at least the backbone's last width")
+        if len(self.task_f_maps) > 1:
+            if not is_3d:
+                raise NotImplementedError("hidden head layers (task_f_maps of length > 1) are 3-D only here")
+            if any(v % 4 for v in self.task_f_maps) or self.task_f_maps[-1] % 8 or self.task_f_maps[-1] > 64:
+                raise L.BfmError("task_f_maps %s: hidden head layers take widths that are multiples of 4, the last one a "
+                                 "multiple of 8 and at most 64 (the fused heads' limit)" % (self.task_f_maps,))
         self.out_feat_level = out_feat_level
+        self.layers = nn.ModuleList([_ConvBlock(ci, co) for ci, co in zip(self.task_f_maps[:-1], self.task_f_maps[1:])])
         self.out_channels = OrderedDict((k, v) for k, v in out_channels.items() if k not in exclude_keys)
         self.out_names = self.out_channels.keys()
         self.c_feat = f_maps_list[-1]
@@ -413,6 +423,9 @@ class TaskHead(nn.Module):
                                  % (name, names))
             if not is_3d:
                 raise NotImplementedError("the pooled scalar head is 3-D only here")
+            if len(self.layers):
+                raise L.BfmError("task_f_maps %s: the pooled scalar head '%s' behind hidden head layers is not built; use a "
+                                 "single-entry task_f_maps with it" % (self.task_f_maps, name))
             size = getattr(args, "size", None)
             if size is None or len(size) != 3:
                 raise L.BfmError("the pooled scalar head '%s' needs train_args.size (3 values)" % name)
@@ -462,7 +475,13 @@ class TaskHead(nn.Module):
     def tail(self, eng):
         key = (id(eng), self._version_key(), self.left_hemis_only, self.max_surf_distance)
         if self._tail is None or self._tail_key != key:
-            self._tail = Tail(eng, self.dense_channels, self.left_hemis_only, self.max_surf_distance)
+            if len(self.layers):
+                # the 1x1x1 heads read the last hidden layer's channels as they are (head.py:54-59)
+                self._tail = Tail(eng, self.dense_channels, self.left_hemis_only, self.max_surf_distance,
+                                  c_feat=self.c_feat, unit_feat=False)
+                self._tail.hidden = eng.head_layers(self.task_f_maps)
+            else:
+                self._tail = Tail(eng, self.dense_channels, self.left_hemis_only, self.max_surf_distance)
             self._tail_key = key
         return self._tail
 
@@ -486,6 +505,9 @@ class TaskHead(nn.Module):
     @L.on_device(lambda self, x, *a, **k: x[self.out_feat_level])
     def forward(self, x, *kwargs):
         """x: list of feature maps; uses x[out_feat_level] as is (already normalised by the backbone)."""
+        if len(self.layers):
+            raise L.BfmError("task_f_maps %s: the hidden head layers run behind the backbone (the joiner, InferenceSession); "
+                             "TaskHead.forward on a bare feature list is not built for them" % (self.task_f_maps,))
         x = x[self.out_feat_level]
         res = []
         for b in range(x.shape[0]):
@@ -835,6 +857,8 @@ def build_model(gen_args, train_args, device="cpu"):
     step (SURVEY 'next' row N2), not to this path -- except for the head-less 'contrastive' task, whose one loss the
     forward surface evaluates (get_criterion)."""
     gen_args, train_args = process_args(gen_args, train_args, task=gen_args.task)
+    if "contrastive" in gen_args.tasks:
+        _single_task_f_maps(train_args, "the head-less contrastive model")
     backbone = build_backbone(train_args, train_args.backbone)
     head = get_head(train_args, train_args.task_f_maps, train_args.out_channels, True, -1)
     head.left_hemis_only = bool(gen_args.generator.left_hemis_only)
@@ -844,6 +868,13 @@ def build_model(gen_args, train_args, device="cpu"):
     criterion = get_criterion(gen_args, train_args, gen_args.tasks, device)
     model.to(device)
     return gen_args, train_args, model, processors, criterion, get_postprocessor
+
+
+def _single_task_f_maps(train_args, what):
+    """The paths whose kernels read the heads straight off the backbone's last feature map refuse hidden head layers."""
+    if len(train_args.task_f_maps) > 1:
+        raise L.BfmError("task_f_maps %s: hidden head layers are built for build_model's network only, not for %s"
+                         % (list(train_args.task_f_maps), what))
 
 
 def _head_settings(head, gen_args):
@@ -857,6 +888,7 @@ def build_conditioned_model(gen_args, train_args, device="cpu"):
     len(train_args.condition.split('+')) condition channels, every head but pathology.  Called as
     model(samples, cond=[...]); criterion as in build_model."""
     gen_args, train_args = process_args(gen_args, train_args, task=gen_args.task)
+    _single_task_f_maps(train_args, "the mask-conditioned model")
     backbone = build_backbone(train_args, train_args.backbone, num_cond=len(train_args.condition.split("+")))
     head = _head_settings(get_head(train_args, train_args.task_f_maps, train_args.out_channels, True, -1, stage=1,
                                    exclude_keys=["pathology"]), gen_args)
@@ -873,6 +905,7 @@ def build_inpaint_model(gen_args, train_args, device="cpu"):
     probability as two channels (outputs 'feat_task' and every other head).  The pathology processors are
     get_processors(gen_args, train_args, ['pathology'], device) -- the reference's own call lacks gen_args."""
     gen_args, train_args = process_args(gen_args, train_args, task=gen_args.task)
+    _single_task_f_maps(train_args, "the two-stage model")
     names = train_args.backbone.split("+")
     if len(names) != 2:
         raise L.BfmError("build_inpaint_model needs a two-stage backbone 'a+b' (got '%s')" % train_args.backbone)

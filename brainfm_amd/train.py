@@ -320,6 +320,7 @@ assert _ADAM_DESC.itemsize == 64
 class TrainStep:
     """Parameters live in the engine (layer .w_raw / .gamma / .beta) and the tail (head_w / head_b); `step` updates
     them in place and drops the packed-weight caches so that the next forward repacks."""
+    hidden = ()                 # the hidden head layers' records (steps without a task head have none)
 
     def __init__(self, engine, tail, loss_names, loss_weights, weights_ce, all_samples, max_surf_distance=3.0,
                  bias_field_log_type="l2", lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, clip_max_norm=0.0,
@@ -331,6 +332,10 @@ class TrainStep:
         if bad:
             raise L.BfmError("losses outside the HIP training path: %s" % bad)
         self.tail = tail
+        # hidden head layers (task_f_maps longer than one; engine._HeadLayer records the tail carries): trained in place
+        self.hidden = list(getattr(tail, "hidden", ()))
+        if self.hidden and age_head is not None:
+            raise L.BfmError("task_f_maps with hidden head layers and the pooled scalar head together are not built")
         self._init_optim(engine, loss_names, loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler)
         self.all_samples = float(all_samples)
         self.max_dist = float(max_surf_distance)
@@ -393,6 +398,9 @@ class TrainStep:
                 p[ly.name + ".groupnorm.weight"] = ly.gamma
                 p[ly.name + ".groupnorm.bias"] = ly.beta
                 p[ly.name + ".conv.weight"] = ly.w_raw
+        for hl in getattr(self, "hidden", ()):                     # registered in front of the 1x1x1 heads (head.py:27-31)
+            p[hl.name + ".weight"] = hl.w_raw
+            p[hl.name + ".bias"] = hl.bias
         for task, (r0, n) in self.tail.row_of.items():
             p["head.final_conv_%s.weight" % task] = self.tail.head_w[r0:r0 + n]
             p["head.final_conv_%s.bias" % task] = self.tail.head_b[r0:r0 + n]
@@ -408,6 +416,9 @@ class TrainStep:
             named = [("head.weight_all", (self.tail.n_out, self.tail.c_feat)), ("head.bias_all", (self.tail.n_out,))]
             if self.age is not None:                               # the pooled head's backward ends before the backbone's
                 named += [("head." + k, tuple(v.shape)) for k, v in self.age.params.items()]
+            for hl in reversed(getattr(self, "hidden", ())):      # backward.backward_head_layer: the bias first
+                named.append((hl.name + ".bias", tuple(hl.bias.shape)))
+                named.append((hl.name + ".weight", tuple(hl.w_raw.shape)))
             for pair in list(reversed(self.eng.dec)) + list(reversed(self.eng.enc)):
                 for ly in reversed(pair):
                     named.append((ly.name + ".conv.weight", tuple(ly.w_raw.shape)))
@@ -727,16 +738,23 @@ class TrainStep:
                              % (tuple(x_cl.shape), x_cl.dtype, dims + (eng.in_channels,)))
         feats, tape = BW.backbone_forward_train(eng, x_cl, dims)
         feat_last = feats[-1][0]
+        head_in, hid_tape = feat_last, None
+        if self.hidden:
+            # F.normalize runs before the hidden layers (unet3d/model.py:207-208, head.py:53-55); the 1x1x1 heads then read
+            # the last layer's output as it is
+            hid_tape = []
+            head_in, _ = eng.run_head_layers(self.hidden, feat_last, dims, tape=hid_tape)
         n_out, cf = tail.n_out, tail.c_feat
         # head outputs as rows of nvox values wherever the one-pass heads backward exists (64 features, <= 96 outputs,
         # <= 64 classes: every shipped head set); BFM_TRAIN_ROWS=0 keeps channels-last
         rows = (os.environ.get("BFM_TRAIN_ROWS", "1") != "0" and cf == 64 and n_out <= 96 and
                 tail.row_of.get("segmentation", (0, 0))[1] <= 64)
-        raw, fn = tail.run_raw(feat_last, dims, want_feat=True, rows=rows)
+        raw, fn = tail.run_raw(head_in, dims, want_feat=True, rows=rows, apply_hidden=False)
         if fn is None:
-            fn = feat_last
+            fn = head_in
         dRaw = torch.zeros_like(raw)
-        return dict(dims=dims, feats=feats, tape=tape, feat_last=feat_last, rows=rows, raw=raw, fn=fn, dRaw=dRaw)
+        return dict(dims=dims, feats=feats, tape=tape, feat_last=feat_last, rows=rows, raw=raw, fn=fn, dRaw=dRaw,
+                    hid_tape=hid_tape)
 
     def _sample_criterion(self, ctx, target, sample, scale):
         """Every loss of the sample: values into the context's fp64 slots, gradients added into its dRaw."""
@@ -796,6 +814,12 @@ class TrainStep:
             if sink is not None:
                 for name in age_grads:
                     sink.done(name)
+        hid_grads = OrderedDict()
+        for hl, x_in, x_bound, y in reversed(ctx.get("hid_tape") or []):
+            # the hidden layers, last to first: dFn is the gradient of the layer's output on the way in, of its input after
+            dX, gr = BW.backward_head_layer(eng, hl, x_in, x_bound, y, dFn.view(dims + (hl.cout,)), dims)
+            hid_grads.update(gr)
+            dFn, cf = dX.reshape(nvox, hl.cin), hl.cin
         if eng.unit_feat:
             dfeat = torch.empty_like(dFn)
             L.check(lib.bfm_normalize_bwd(L.ptr(feat_last), L.ptr(dFn), cf, nvox, 1e-12, L.ptr(dfeat), st), "normalize_bwd")
@@ -807,6 +831,7 @@ class TrainStep:
             g["head.final_conv_%s.bias" % task] = db[r0:r0 + n]
         if age_grads is not None:
             g.update(age_grads)
+        g.update(hid_grads)
         # heads no loss of this sample reached: the reference leaves their .grad None (the all-zero rows above only keep
         # the gradient dictionary's layout fixed for the flat all-reduce); loss_and_grads collects who was reached
         self._touched_heads.update(task for task, (r0, n) in tail.row_of.items()

@@ -1019,6 +1019,23 @@ int bfm_age_mlp_bwd(const float* y2, int nv, const bfm_age_params_t* prm, int n_
                     const float* p, const float* dp_in, double age, float coef, double* loss, const bfm_age_grads_t* grd,
                     float* dy2, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
 
+/* ---- hidden task-head layers (task_f_maps longer than one; head_layers.hip) -------------------------------------------
+ * Trainer/models/head.py:27-31,52-55,152-167: ConvBlock = Conv3d(f[i], f[i+1], 3, padding 1, bias) + LeakyReLU(0.2), no
+ * GroupNorm, between the (normalised, unet3d/model.py:207-208) last feature map and the 1x1x1 heads.  The convolution runs
+ * on the existing kernels with the identity affine (scale 1, shift 0, one bound = max |x|) and slope 1; these add the rest.
+ * bfm_head_bias_lrelu: y[v][c] = lrelu(y[v][c] + bias[c], slope) in place over (nvox, C) channels-last, C % 4 == 0.
+ * mask_image (or NULL; nvox floats): voxels where it is zero are left untouched (a masked convolution leaves boxes of them
+ * unwritten).  bound_out (or NULL; device float, zeroed here) = max |y| over the voxels written: the next layer's bound. */
+int bfm_head_bias_lrelu(float* y, const float* bias, int C, int64_t nvox, float slope, const float* mask_image,
+                        float* bound_out, bfm_stream_t stream);
+/* Its backward (autograd over head.py:165-166): dP = dY * (Y > 0 ? 1 : slope), absmax_out (or NULL; zeroed here) = max |dP|,
+ * dbias[c] = sum_v dP[v][c] through fp64 partials of fixed voxel ranges folded in ascending order (no atomics: the same bits
+ * on every run).  dP may not alias dY.  dW then comes from bfm_conv3x3x3_wgrad_ex and dX from the data-gradient convolution,
+ * both with the identity affine.  workspace >= bfm_head_bias_lrelu_bwd_workspace(C, nvox), 8-byte aligned. */
+size_t bfm_head_bias_lrelu_bwd_workspace(int C, int64_t nvox);
+int bfm_head_bias_lrelu_bwd(const float* dY, const float* Y, int C, int64_t nvox, float slope, float* dP, float* dbias,
+                            float* absmax_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
