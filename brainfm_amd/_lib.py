@@ -108,6 +108,10 @@ SIGNATURES = {
     "bfm_conv3x3x3_upfold_ex": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "bfm_conv3x3x3_upfold_batch_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
     "bfm_conv3x3x3_upfold_batch": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _Z, _I, _P]),
+    "bfm_conv3x3x3_tap_batch_workspace": (_Z, [_I, _I, _I, _I]),
+    "bfm_conv3x3x3_tap_batch": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _Z, _I, _P]),
+    "bfm_tap_sum_rows": (_I, [_I, _I]),
+    "bfm_tap_sum_batch": (_I, [_P, _I, _I, _I, _I, _P, _I, _F, _I, _I, _P, _P, _P]),
     "bfm_moment_rows_bytes": (_Z, [_I, _I]),
     "bfm_conv3x3x3_mfma_rows": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "bfm_conv3x3x3_mfma_ex": (_I, [_P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _P, _I, _P, _I, _I, _F, _I,

@@ -38,6 +38,24 @@ def nearest_index_map(n_in, n_out):
     return np.minimum(idx, n_in - 1).astype(np.int32)
 
 
+def tap_row_table(lo, hi):
+    """(output voxel, tap) -> row of the low-res tensor that a 3x3x3 zero-padded conv over nearest_up(lo -> hi) reads
+    there, -1 where the tap leaves the hi-res volume: int32 [prod(hi)][27], taps kd, kh, kw ascending.  lo == hi is the
+    identity map, a plain conv (conv3d_tap.hip: bfm_tap_sum_batch)."""
+    maps = [nearest_index_map(lo[a], hi[a]).astype(np.int64) for a in range(3)]
+    z, y, x = np.meshgrid(*[np.arange(hi[a]) for a in range(3)], indexing="ij")
+    tab = np.full(tuple(hi) + (27,), -1, dtype=np.int32)
+    for kd in range(3):
+        for kh in range(3):
+            for kw in range(3):
+                zz, yy, xx = z + kd - 1, y + kh - 1, x + kw - 1
+                ok = (zz >= 0) & (zz < hi[0]) & (yy >= 0) & (yy < hi[1]) & (xx >= 0) & (xx < hi[2])
+                row = (maps[0][zz.clip(0, hi[0] - 1)] * lo[1] + maps[1][yy.clip(0, hi[1] - 1)]) * lo[2] \
+                    + maps[2][xx.clip(0, hi[2] - 1)]
+                tab[..., (kd * 3 + kh) * 3 + kw] = np.where(ok, row, -1)
+    return np.ascontiguousarray(tab.reshape(-1, 27))
+
+
 _TUNE_CHOICES = {}          # (device, passes, shape key) -> conv variant that won UNetEngine._autotune in this process
 
 # The conv variants (cfg[6]): 0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino F(2,3), 4 conv_wino4 F(4,3).  Per variant
@@ -168,6 +186,7 @@ class UNetEngine:
     _same_box_cache = None
     _uf_cache = None
     _deep_ok = None
+    _tap_cache = None           # (lo, hi) -> device table of _tap_table
     _head_layers = None         # (task_f_maps, [_HeadLayer]) once a head with hidden layers asked for them (head_layers)
     _unit_bound = None
     _no_heads = None
@@ -398,6 +417,15 @@ class UNetEngine:
             up = L.Upsample(lo[0], lo[1], lo[2], *[t.data_ptr() for t in dev])
             self._up_cache[key] = (up, dev)
         return self._up_cache[key][0]
+
+    def _tap_table(self, lo, hi):
+        """tap_row_table(lo, hi) on the device, built once per (lo, hi) shape."""
+        key = (tuple(lo), tuple(hi))
+        if self._tap_cache is None:
+            self._tap_cache = {}
+        if key not in self._tap_cache:
+            self._tap_cache[key] = torch.from_numpy(tap_row_table(key[0], key[1])).to(self.device)
+        return self._tap_cache[key]
 
     def _workspace(self, nbytes):
         """Scratch of the current lane (tiles of different lanes run concurrently on their own streams)."""
@@ -985,6 +1013,12 @@ class UNetEngine:
     DEEP_VERS_1SRC = (0, 2, 4)
     deep_upfold = os.environ.get("BFM_DEEP_UPFOLD", "1") != "0"          # fold exact 2x upsamples inside the region too
     deep_upfold_min = int(os.environ.get("BFM_DEEP_UPFOLD_MIN", "100"))  # fewest low-res voxels per sample worth it
+    # The smallest levels (2^3, 5 x 2 x 2, 5 x 5 x 2 voxels per sample) as tap-wise GEMMs over the batch's densely packed
+    # rows (conv3d_tap.hip): one source with at most tap_max voxels, or two sources whose low-res tensor has at most
+    # tap_max -- at most half of conv_mfma's 128-row tile filled per sample.  Of the shapes alone, never of S.
+    # BFM_TAP=0: the conv_mfma route.
+    use_tap = os.environ.get("BFM_TAP", "1") != "0"
+    tap_max = 64
     # The tile loop multiplies every output of a tile by (tile input != 0) (scripts/demo_test.py:88-100): the last
     # convolution and the per-voxel heads leave out the voxels that product discards (BFM_MASK_SKIP=0: compute them all).
     mask_skip = os.environ.get("BFM_MASK_SKIP", "1") != "0"
@@ -1065,6 +1099,8 @@ class UNetEngine:
             self._batch_stats(ly, A, ca, B, cb, S, dims, lo_dims, upp, scale, shift, bound)
         else:
             scale, shift, bound = stats
+        if self.use_tap and (lo_dims[0] * lo_dims[1] * lo_dims[2] if B is not None else D * H * W) <= self.tap_max:
+            return self._batch_conv_tap(ly, A, dims, B, lo_dims, scale, shift, bound)
         if (B is not None and self.use_upfold and self.deep_upfold and tuple(dims) == tuple(2 * v for v in lo_dims)
                 and lo_dims[0] * lo_dims[1] * lo_dims[2] >= self.deep_upfold_min):
             return self._batch_conv_upfold(ly, A, dims, B, lo_dims, scale, shift, bound)
@@ -1166,6 +1202,62 @@ class UNetEngine:
         self._bracket(lambda: self._batch_launch(sk, cfg, A, None, None, dims, sc_a, sh_a, bound, out, rows, aff),
                       lambda: (2.0 * 27 * ca * ly.cout * nv * S, 4.0 * S * (nv * ca + 2 * nv * ly.cout),
                                self._tag(ly) + "x%dsk" % S, ca, ly.cout, dims, cfg))
+        if rows is not None:
+            out._bfm_rows = rows
+        return out
+
+    def _batch_conv_tap(self, ly, A, dims, B, lo_dims, scale, shift, bound):
+        """A layer of the batched levels whose (low-res) tensor has at most tap_max voxels per sample, as tap-wise GEMMs:
+        bfm_conv3x3x3_tap_batch multiplies every tap's weights with the S * n_lo densely packed rows of the batch (one pass
+        over the packed weights), bfm_tap_sum_batch gathers the 27 products of every output voxel.  One source: the sum
+        applies LeakyReLU and writes the moment rows.  Two sources: that is the upsampled half, without activation; the
+        skip half then accumulates onto it through conv_mfma as in _batch_conv_upfold."""
+        S = A.shape[0]
+        D, H, W = dims
+        nv = D * H * W
+        ca = A.shape[-1]
+        st = L.stream_ptr()
+        if "mfma" not in ly.packs:
+            self._make_pack(ly, "mfma")
+        ly.touch("mfma")
+        wp, wexp = ly.packs["mfma"]
+        out = torch.empty((S, D, H, W, ly.cout), dtype=torch.float32, device=self.device)
+        if B is None:
+            X, cx, n_lo, kc0, aff = A, ca, nv, 0, 0
+            sc_x, sh_x = scale, shift
+            tab = self._tap_table(dims, dims)
+            rows = self._rows_buf(ly.cout, S, self.lib.bfm_tap_sum_rows, nv, ly.cout)
+        else:
+            X, cx, n_lo, kc0, aff = B, B.shape[-1], lo_dims[0] * lo_dims[1] * lo_dims[2], ca // 16, ly.cin
+            sc_x, sh_x = scale[:, ca:], shift[:, ca:]
+            tab = self._tap_table(lo_dims, dims)
+            rows = None
+        wsb = self.lib.bfm_conv3x3x3_tap_batch_workspace(cx, ly.cout, S, n_lo)
+
+        def _launch_tap():
+            ws = self._workspace(wsb)
+            L.check(self.lib.bfm_conv3x3x3_tap_batch(L.ptr(X), cx, S, n_lo, L.ptr(sc_x), L.ptr(sh_x), L.ptr(bound), ly.groups,
+                                                     L.ptr(wp), wexp, ly.cout, kc0, ly.cin // 16, self.passes, L.ptr(ws),
+                                                     ws.numel(), aff, st), "conv_tap_batch " + ly.name)
+            L.check(self.lib.bfm_tap_sum_batch(L.ptr(ws), cx, ly.cout, S, n_lo, L.ptr(tab), nv, self.slope,
+                                               1 if B is None else 0, 0, L.ptr(out),
+                                               L.ptr(rows[0]) if rows is not None else None, st),
+                    "tap_sum_batch " + ly.name)
+        self._bracket(_launch_tap, lambda: (2.0 * 27 * cx * ly.cout * nv * S,
+                                            4.0 * (S * (n_lo * cx + nv * ly.cout) + 27 * cx * ly.cout),
+                                            self._tag(ly) + "x%dtap" % S, cx, ly.cout, dims, (0,) * 8))
+        if B is not None:
+            # the skip half on conv_mfma itself (what decoders.0.2 runs at these shapes by the committed table): a fixed
+            # choice, so that no shape of this route is ever timed in-process
+            sk = self._skip_layer(ly, ca)
+            sc_a, sh_a = scale[:, :ca], shift[:, :ca]
+            key = (ca, ly.cout, tuple(dims), False, True, 1, "tap")
+            cfg = self._batch_plan(key, (0,))
+            self._pack(sk, True, 0)
+            rows = self._rows_for(ca, ly.cout, dims, cfg, S)
+            self._bracket(lambda: self._batch_launch(sk, cfg, A, None, None, dims, sc_a, sh_a, bound, out, rows, aff),
+                          lambda: (2.0 * 27 * ca * ly.cout * nv * S, 4.0 * S * (nv * ca + 2 * nv * ly.cout),
+                                   self._tag(ly) + "x%dsk" % S, ca, ly.cout, dims, cfg))
         if rows is not None:
             out._bfm_rows = rows
         return out

@@ -341,6 +341,24 @@ int bfm_conv3x3x3_upfold_batch(const float* B, int CB, int S, int d, int h, int 
                                int passes, float* out, void* workspace, size_t workspace_bytes, int affine_stride,
                                bfm_stream_t stream);
 
+/* The smallest deep levels as tap-wise GEMMs on densely packed rows (conv3d_tap.hip).  X [S][n_lo][Cin] fp32 channels-last;
+ * scale / shift [S][Cin] (rows affine_stride floats apart, 0 = Cin), bound [S][G] as for _upfold_batch.  wpacked: the
+ * bfm_pack_conv_weights_mfma pack of a layer with kc_pack * 16 input channels, of which these Cin start at channel
+ * kc_first * 16.  _tap_batch leaves P[tap][K slab][s * n_lo + v][Cout] = W[tap] . y[s][v] in the workspace;
+ * bfm_tap_sum_batch (same Cin, Cout, S, n_lo, same workspace) then writes
+ *   out[s][o][c] = (accumulate ? out : 0) + sum_tap sum_slab P[tap][slab][s * n_lo + table[o * 27 + tap]][c]
+ * (taps and slabs ascending; table entry -1 = term dropped), optionally LeakyReLU(slope), optionally the moment rows of the
+ * stored output: S * bfm_tap_sum_rows(n_hi, Cout) rows, laid out as bfm_moment_rows_bytes says.  A sample's bits do not
+ * depend on S or on its place in the batch: the K slab plan is a function of (Cin, Cout) alone. */
+size_t bfm_conv3x3x3_tap_batch_workspace(int Cin, int Cout, int S, int n_lo);
+int bfm_conv3x3x3_tap_batch(const float* X, int Cin, int S, int n_lo, const float* scale, const float* shift,
+                            const float* bound, int G, const void* wpacked, int wexp, int Cout, int kc_first, int kc_pack,
+                            int passes, void* workspace, size_t workspace_bytes, int affine_stride, bfm_stream_t stream);
+int bfm_tap_sum_rows(int n_hi, int Cout);
+int bfm_tap_sum_batch(const void* workspace, int Cin, int Cout, int S, int n_lo, const int* table /*[n_hi][27], device*/,
+                      int n_hi, float slope, int activation, int accumulate, float* out, void* moment_rows /*or NULL*/,
+                      bfm_stream_t stream);
+
 int bfm_conv3x3x3_mfma(const float* A, int CA, const float* B, int CB, int D, int H, int W,
                        const bfm_upsample_t* up, const float* scale, const float* shift, const float* bound,
                        int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
