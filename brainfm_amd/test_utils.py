@@ -6,13 +6,15 @@
   evaluate_image(inputs, ckp_path, ...)               :289-312  (model cached: fixes quirk Q1 behind the same signature)
   test_tile -> tiled_inference(...)                   scripts/demo_test.py:66-119, in HBM, no NIfTI round trip
   tiled_inference_distributed(...)                    tiles sharded over ranks, RCCL gather to rank 0
+Both tile flows are plan_exchange (host only: owners, batches, slots, buffer sizes) -> _run_batches (one rank's batches on
+its lanes) -> ops.stitch; HipStitchOps is that ops interface, _PerTileOps wraps the gloo tests' per-tile stand-ins into it.
 
 All arithmetic runs in libbrainfm_hip.so (fused tail kernel + stitch kernels).
 """
 import ctypes as C
 import os
 from argparse import Namespace
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -95,6 +97,12 @@ def axis_intervals(n, win, stride):
 def tiling_ranges(shape, stride, win_size):
     xs, ys, zs = (axis_intervals(shape[a], win_size[a], stride[a]) for a in range(3))
     return [[x, y, z] for x in xs for y in ys for z in zs]
+
+
+def tile_window(full_im, rng):
+    """The view of a (N,C,D,H,W) volume that tile `rng` = [(x0,x1),(y0,y1),(z0,z1)] covers."""
+    (x0, x1), (y0, y1), (z0, z1) = rng
+    return full_im[:, :, x0:x1, y0:y1, z0:z1]
 
 
 def count_volume(shape, ranges, device):
@@ -325,7 +333,12 @@ class InferenceSession:
         # tile's convolutions.  Stitching stays on the caller's stream in the reference's tile order.
         self.lanes = max(1, int(os.environ.get("BFM_LANES", "2")))
         self._lane_streams = []
-        self.atlas = None                                  # (MNI (X,Y,Z) fp32 on the device, 12 floats of inv(affine))
+        # what the tile flows keep between volumes, and what invalidates each
+        self.atlas = None              # (MNI (X,Y,Z) fp32 on the device, 12 floats of inv(affine)): set_atlas replaces it
+        self._stitch_ops = None        # HipStitchOps and its device tables, keyed by what they describe: never invalidated
+        self._dist_bufs = {}           # name -> rows / send / own / receive buffer: replaced when its size or device changes
+        self._dist_cnt = {}            # count volume per (shape, stride, window, device), the tiling alone: never invalidated
+        self._agreed_sizes = set()     # tile sizes whose conv variants the ranks agreed on: never invalidated (see drop_graphs)
         if atlas_path is not None:
             self.set_atlas(*_read_volume(atlas_path, False))
 
@@ -342,9 +355,21 @@ class InferenceSession:
             if vol.dim() != 3:
                 raise L.BfmError("atlas must be a 3-D volume, got %s" % (tuple(vol.shape),))
             self.atlas = (vol, (C.c_float * 12)(*[float(v) for v in A32]))
-        self._graphs.clear()                               # captured tile graphs bake the atlas pointer and matrix in
+        self.drop_graphs()                                 # captured tile graphs bake the atlas pointer and matrix in
+
+    def drop_graphs(self):
+        """Forget every captured tile graph, its static buffers and pools (a graph bakes in the atlas, the packed weights'
+        exponents and the conv variants): a shape's next batch runs eagerly, the one after is captured again.  The agreed
+        tile sizes stay: the ranks' common conv choices live in the engine and outlast the graphs captured with them."""
+        self._graphs.clear()
         self._graph_seen.clear()
         self._graph_pool = {}
+
+    @property
+    def stitch_ops(self):
+        if self._stitch_ops is None:
+            self._stitch_ops = HipStitchOps(self)
+        return self._stitch_ops
 
     def lane_streams(self, n):
         while len(self._lane_streams) < n:
@@ -354,10 +379,10 @@ class InferenceSession:
     def stitch_keys(self):
         """The keys tiled inference stitches for this head set, in STITCH_KEYS order."""
         tail = self.model.head.tail(self.engine)
-        names = set(tail.map_names)
-        if self.atlas is not None and {"regx", "regy", "regz"} <= names:
-            names.add("deformed_atlas")
-        return [k for k in STITCH_KEYS if k in names or (k == "label" and tail.desc.n_seg > 0)]
+        names = list(tail.map_names)
+        if self.atlas is not None and {"regx", "regy", "regz"} <= set(names):
+            names.append("deformed_atlas")
+        return stitch_selection(names, tail.desc.n_seg > 0)[0]
 
     @L.on_device(lambda self, *a, **k: self.device)
     def graph_group(self, ims, lane=0):
@@ -371,9 +396,7 @@ class InferenceSession:
         key = (dims, S, lane)
         eng = self.engine
         if eng.weights_epoch != self._graphs_epoch:            # trained in between: graphs hold stale packing exponents
-            self._graphs.clear()
-            self._graph_seen.clear()
-            self._graph_pool = {}
+            self.drop_graphs()
             self._graphs_epoch = eng.weights_epoch
         if key not in self._graph_seen:
             self._graph_seen.add(key)
@@ -453,26 +476,7 @@ class InferenceSession:
             if fnorm is not None:
                 bufs[-1] = fnorm
             out["feat"] = [UNetEngine.as_ncdhw(f) for f in bufs]
-        order = ["T1", "T2", "FLAIR", "CT", "segmentation", "high_res_residual", "high_res", "bias_field", "lp", "lw",
-                 "rp", "rw", "fake_cortical", "regx", "regy", "regz"]
-        def chans(k):
-            # a head with c channels (`losses.uncertainty`: value + sigma) is c adjacent rows of the tail's buffer:
-            # the reference keeps them as one (1,c,D,H,W) tensor (Trainer/models/__init__.py:57-111, joiner.py:50-55)
-            r0, c = tail.channels.get(k, (None, 1))
-            return tail.last_buf[r0:r0 + c][None] if c > 1 else maps[k][None, None]
-
-        for k in order:
-            if k == "segmentation":
-                if seg is not None:
-                    out[k] = seg.permute(3, 0, 1, 2).unsqueeze(0)
-            elif k in maps:
-                out[k] = chans(k)
-        for k, v in maps.items():
-            if k not in out and "#" not in k:
-                out[k] = chans(k)
-        if label is not None:
-            out["label"] = label[None, None]
-        return out, x_cl
+        return _tail_outputs(tail, maps, seg, label, out), x_cl
 
     @torch.no_grad()
     def evaluate(self, inputs, feature_only=True):
@@ -487,6 +491,31 @@ class InferenceSession:
         return out["feat"][-1] if feature_only else out
 
 
+def _tail_outputs(tail, maps, seg, label, out):
+    """The fused tail's results under the reference's output keys, added to `out` (Trainer/models/__init__.py:307-352)."""
+    order = ["T1", "T2", "FLAIR", "CT", "segmentation", "high_res_residual", "high_res", "bias_field", "lp", "lw",
+             "rp", "rw", "fake_cortical", "regx", "regy", "regz"]
+
+    def chans(k):
+        # a head with c channels (`losses.uncertainty`: value + sigma) is c adjacent rows of the tail's buffer:
+        # the reference keeps them as one (1,c,D,H,W) tensor (Trainer/models/__init__.py:57-111, joiner.py:50-55)
+        r0, c = tail.channels.get(k, (None, 1))
+        return tail.last_buf[r0:r0 + c][None] if c > 1 else maps[k][None, None]
+
+    for k in order:
+        if k == "segmentation":
+            if seg is not None:
+                out[k] = seg.permute(3, 0, 1, 2).unsqueeze(0)
+        elif k in maps:
+            out[k] = chans(k)
+    for k, v in maps.items():
+        if k not in out and "#" not in k:
+            out[k] = chans(k)
+    if label is not None:
+        out["label"] = label[None, None]
+    return out
+
+
 _SESSIONS = {}
 
 
@@ -496,22 +525,35 @@ def _resolve_device(device):
     return device
 
 
+def _mtime(path):
+    return os.path.getmtime(path) if path and os.path.exists(path) else None
+
+
+def _default_cfgs(gen_cfg, model_cfg):
+    """(gen_args, train_args) of the module's default configuration files with the two given ones on top."""
+    if default_gen_cfg_file is None or default_train_cfg_file is None:
+        raise ValueError("set brainfm_amd.test_utils.default_gen_cfg_file / default_train_cfg_file "
+                         "(absolute paths of cfgs/generator/default.yaml, cfgs/trainer/default_train.yaml)")
+    return (_cfg.preprocess_cfg([default_gen_cfg_file, gen_cfg], cfg_dir=gen_cfg_dir),
+            _cfg.preprocess_cfg([default_train_cfg_file, default_val_file, model_cfg], cfg_dir=train_cfg_dir))
+
+
+def _cached_session(key, build):
+    """The session kept under `key` (checkpoint paths and times, configurations, device); build() makes it once."""
+    if key not in _SESSIONS:
+        _SESSIONS[key] = build()
+    return _SESSIONS[key]
+
+
 @torch.no_grad()
 def evaluate_image(inputs, ckp_path, feature_only=True, device="cpu", gen_cfg=None, model_cfg=None):
     """utils/test_utils.py:289-312.  inputs: (batch, 1, s, r, c)."""
     device = _resolve_device(device)
     if torch.device(device).type != "cuda":
         raise L.BfmError("evaluate_image runs on a HIP device only; there is no CPU fallback in the product path")
-    mtime = os.path.getmtime(ckp_path) if ckp_path and os.path.exists(ckp_path) else None
-    key = (ckp_path, mtime, gen_cfg, model_cfg, str(device))
-    if key not in _SESSIONS:
-        if default_gen_cfg_file is None or default_train_cfg_file is None:
-            raise ValueError("set brainfm_amd.test_utils.default_gen_cfg_file / default_train_cfg_file "
-                             "(absolute paths of cfgs/generator/default.yaml, cfgs/trainer/default_train.yaml)")
-        gen_args = _cfg.preprocess_cfg([default_gen_cfg_file, gen_cfg], cfg_dir=gen_cfg_dir)
-        train_args = _cfg.preprocess_cfg([default_train_cfg_file, default_val_file, model_cfg], cfg_dir=train_cfg_dir)
-        _SESSIONS[key] = InferenceSession(gen_args, train_args, device, ckp_path=ckp_path)
-    return _SESSIONS[key].evaluate(inputs, feature_only)
+    key = (ckp_path, _mtime(ckp_path), gen_cfg, model_cfg, str(device))
+    build = lambda: InferenceSession(*_default_cfgs(gen_cfg, model_cfg), device, ckp_path=ckp_path)
+    return _cached_session(key, build).evaluate(inputs, feature_only)
 
 
 # ----------------------------------------------------------------------------- tiled whole-volume inference
@@ -574,6 +616,13 @@ def assign_tiles(ranges, world_size):
     return owner
 
 
+def stitch_selection(names, has_label):
+    """Which keys a tile flow stitches and where each one's row is: (keys in STITCH_KEYS order, row of each in `names`
+    -- the fused tail's map buffer -- with -1 for 'label', which comes from the label volume)."""
+    keys = [k for k in STITCH_KEYS if k in names or (k == "label" and has_label)]
+    return keys, [names.index(k) if k != "label" else -1 for k in keys]
+
+
 def _stitch_tile(lib, acc, keys, maps, label, x_cl, rng, shape):
     (x0, x1), (y0, y1), (z0, z1) = rng
     td, th, tw = x1 - x0, y1 - y0, z1 - z0
@@ -621,7 +670,7 @@ def tiled_inference(full_im, session, stride=[80, 80, 80], win_size=[160, 160, 1
     start.record(main)
     for idx, rng in enumerate(ranges):
         (x0, x1), (y0, y1), (z0, z1) = rng
-        im = full_im[:, :, x0:x1, y0:y1, z0:z1]
+        im = tile_window(full_im, rng)
         k = idx % nl
         dims = (x1 - x0, y1 - y0, z1 - z0)
         if nl > 1 and session.has_graph(dims, k):
@@ -641,9 +690,8 @@ def tiled_inference(full_im, session, stride=[80, 80, 80], win_size=[160, 160, 1
         else:
             maps_buf, names, label, x_cl = _run_tile(session, im, raw=True)
         if acc_buf is None:
-            keys = [k_ for k_ in STITCH_KEYS if k_ in names or (k_ == "label" and label is not None)]
-            sel = torch.tensor([names.index(k_) if k_ != "label" else -1 for k_ in keys], dtype=torch.int32,
-                               device=eng.device)
+            keys, sel = stitch_selection(names, label is not None)
+            sel = torch.tensor(sel, dtype=torch.int32, device=eng.device)
             acc_buf = torch.zeros((len(keys),) + shape, dtype=torch.float32, device=eng.device)
         tv = (x1 - x0) * (y1 - y0) * (z1 - z0)
         L.check(lib.bfm_stitch_accumulate_multi(L.ptr(maps_buf), tv, L.ptr(sel), len(keys), L.ptr(label), L.ptr(x_cl),
@@ -660,18 +708,65 @@ def tiled_inference(full_im, session, stride=[80, 80, 80], win_size=[160, 160, 1
 
 def _cached_count_volume(session, shape, ranges, stride, win_size, dev):
     """The count volume depends on the tiling alone: kept on the session (callers read it, nobody writes it)."""
+    if session is None:
+        return count_volume(shape, ranges, dev)
     ckey = ("cnt", tuple(shape), tuple(stride), tuple(win_size), str(dev))
-    cache = session.__dict__.setdefault("_dist_cnt", {})
-    if ckey not in cache:
-        cache[ckey] = count_volume(shape, ranges, dev)
-    return cache[ckey]
+    if ckey not in session._dist_cnt:
+        session._dist_cnt[ckey] = count_volume(shape, ranges, dev)
+    return session._dist_cnt[ckey]
 
 
-def _session_stitch_ops(session):
-    ops = getattr(session, "_stitch_ops", None)               # kept on the session: its device tables are reused
-    if ops is None:
-        ops = session._stitch_ops = HipStitchOps(session)
-    return ops
+ExchangePlan = namedtuple("ExchangePlan", "owner batches_of round_of off_of round_numel own_numel")
+
+
+def plan_exchange(ranges, world, rounds, nlanes, nkeys, width, live):
+    """Where every tile's rows go, from plain numbers alone (every rank computes the same plan).  width[i]: columns of
+    tile i's [nkeys][width] rows; live[i]: whether tile i runs at all (a tile that does not gets slot (0, 0): nothing
+    computed, nothing shipped, nothing read).  Per rank: its live tiles as batches of same-shape tiles (tile_batches:
+    the deep levels of a batch run as one launch per layer), largest batch first, at least `nlanes` of them; tile i sits
+    at offset off_of[i] of the buffer of round round_of[i], round k being the k-th batch of every rank (rounds=False:
+    one round).  Rank 0's own tiles never travel: they are packed into a private buffer per round (own_numel[k]), and a
+    round's padded size round_numel[k] is set by the peers alone; both are at least 1."""
+    tiles = range(len(ranges))
+    owner = assign_tiles(ranges, world)
+    batches_of = [tile_batches(ranges, [i for i in tiles if owner[i] == r and live[i]], min_batches=nlanes)
+                  for r in range(world)]
+    nrounds = max([len(b) for b in batches_of] + [1]) if rounds else 1
+    round_of, off_of = {i: 0 for i in tiles}, {i: 0 for i in tiles}
+    round_numel, own_numel = [1] * nrounds, [1] * nrounds
+    for r, batches in enumerate(batches_of):
+        fill = [0] * nrounds
+        for k, batch in enumerate(batches):
+            kk = k if rounds else 0
+            for i in batch:
+                round_of[i], off_of[i] = kk, fill[kk]
+                fill[kk] += width[i] * nkeys
+        sizes = own_numel if r == 0 else round_numel
+        sizes[:] = [max(a, b) for a, b in zip(sizes, fill)]
+    return ExchangePlan(owner, batches_of, round_of, off_of, round_numel, own_numel)
+
+
+def _run_batches(session, ops, full_im, ranges, batches, slot, width, index, lanes, start, before_capture=None):
+    """Run one rank's `batches` of same-shape tiles, tile i's rows going to slot[i] (a flat view of width[i] columns per
+    key; `index`: the compact form).  lanes: the modelled work per lane so far, updated here (a caller with several
+    rounds goes on balancing): every batch goes to the least loaded lane (ties: the lower one), on that lane's stream once
+    event `start` has passed -- no lane waits for another lane's tiles; an empty list: on the caller's stream.
+    before_capture(): called ahead of a batch whose graph is not captured yet.
+    Returns (keys, [per lane used, the event that says its rows are written])."""
+    keys, done = None, {}
+    for batch in batches:
+        lane = None
+        if lanes:
+            lane = min(range(len(lanes)), key=lambda j: (lanes[j], j))
+            lanes[lane] += sum(tile_time(ranges[i]) for i in batch)
+        ims = [tile_window(full_im, ranges[i]) for i in batch]
+        if before_capture is not None and not session.has_graph(tuple(ims[0].shape[2:]), lane or 0, len(batch)):
+            before_capture()
+        cargs = dict(index=index, tiles_idx=batch, strides=[width[i] for i in batch]) if index is not None else {}
+        keys, _, ev = ops.run_group(ims, [slot[i] for i in batch], lane=lane, after=start, **cargs)
+        if ev is not None:
+            done[lane] = ev
+    return keys, list(done.values())
 
 
 @torch.no_grad()
@@ -681,17 +776,10 @@ def _tiled_inference_lanes(full_im, session, ranges, shape, stride, win_size):
     lane ever waits for another lane's tile, which the per-tile `full[range] +=` on the caller's stream forced through
     the reference's tile order -- tiles go to the lanes largest first onto the less loaded lane, and one launch
     (bfm_stitch_gather_multi) then sums every voxel's tiles in the reference's order and divides by their number: the
-    same bits as the sequential form."""
+    same bits as the sequential form.  The slots are plan_exchange's for one rank and one round."""
     dev = full_im.device
-    ops = _session_stitch_ops(session)
-    nl = session.lanes
-    nkeys = len(session.stitch_keys())
-    offs, total = [], 0
-    for r in ranges:
-        offs.append(total)
-        total += tile_cost(r) * nkeys
-    buf = _exchange_buffer(session, "rows", total, dev)
-    load = [0] * nl
+    ops = session.stitch_ops
+    nkeys = ops.n_keys
     main = torch.cuda.current_stream(dev)
     start = torch.cuda.Event()
     start.record(main)                                         # the input is in place, last volume's rows are consumed
@@ -701,29 +789,19 @@ def _tiled_inference_lanes(full_im, session, ranges, shape, stride, win_size):
     # and do not run a tile without any input at all, as the multi-GPU path does for free
     skip = COMPACT and os.environ.get("BFM_SKIP_EMPTY_TILES", "1") == "all"
     index = ops.index_volume(full_im, ranges, counts=skip) if COMPACT else None
-    live = None
-    if skip and index is not None and index.nnz is not None:
-        live = [i for i in range(len(ranges)) if index.nnz[i] > 0]
-    last, keys = {}, None
-    for batch in tile_batches(ranges, live):                   # same-shape tiles together: the deep levels run batched
-        k = min(range(nl), key=lambda j: (load[j], j))
-        load[k] += sum(tile_time(ranges[i]) for i in batch)
-        ims = [full_im[:, :, ranges[i][0][0]:ranges[i][0][1], ranges[i][1][0]:ranges[i][1][1],
-                       ranges[i][2][0]:ranges[i][2][1]] for i in batch]
-        outs = [buf[offs[i]:offs[i] + tile_cost(ranges[i]) * nkeys] for i in batch]
-        keys, _, done = ops.run_group(ims, outs, lane=k, after=start, index=index, tiles_idx=batch,
-                                      strides=[tile_cost(ranges[i]) for i in batch])
-        if done is not None:
-            last[k] = done
-    for ev in last.values():
+    counted = skip and index is not None and index.nnz is not None
+    live = [n > 0 for n in index.nnz] if counted else [True] * len(ranges)
+    width = [tile_cost(r) for r in ranges]
+    plan = plan_exchange(ranges, 1, False, 1, nkeys, width, live)
+    buf = _exchange_buffer(session, "rows", sum(width) * nkeys, dev)
+    slot = [buf[plan.off_of[i]:plan.off_of[i] + w * nkeys] for i, w in enumerate(width)]
+    keys, done = _run_batches(session, ops, full_im, ranges, plan.batches_of[0], slot, width, index, [0] * session.lanes,
+                              start)
+    for ev in done:
         main.wait_event(ev)
-    srcs = [buf[offs[i]:offs[i] + tile_cost(r) * nkeys].view(nkeys, tile_cost(r)) for i, r in enumerate(ranges)]
-    acc_buf = torch.empty((nkeys,) + tuple(shape), dtype=torch.float32, device=dev)
-    ops.gather_all(acc_buf, srcs, ranges, shape, index=index)
     cnt = _cached_count_volume(session, shape, ranges, stride, win_size, dev)
-    if keys is None:                                           # every tile was empty
-        keys = session.stitch_keys()
-    return OrderedDict((k_, acc_buf[j]) for j, k_ in enumerate(keys)), ranges, cnt
+    acc_buf = ops.stitch([s_.view(nkeys, w) for s_, w in zip(slot, width)], ranges, shape, cnt, index=index)
+    return OrderedDict((k_, acc_buf[j]) for j, k_ in enumerate(keys or ops.keys)), ranges, cnt
 
 
 @torch.no_grad()
@@ -745,8 +823,7 @@ def prepare_tile_graphs(full_im, session, stride=[80, 80, 80], win_size=[160, 16
         if (dims, len(batch)) in done:
             continue
         done.add((dims, len(batch)))
-        ims = [full_im[:, :, ranges[i][0][0]:ranges[i][0][1], ranges[i][1][0]:ranges[i][1][1],
-                       ranges[i][2][0]:ranges[i][2][1]].to(device=session.device, dtype=torch.float32) for i in batch]
+        ims = [tile_window(full_im, ranges[i]).to(device=session.device, dtype=torch.float32) for i in batch]
         for lane in range(session.lanes):
             while not session.has_graph(dims, lane, len(batch)):
                 session.graph_group(ims, lane=lane)
@@ -758,7 +835,7 @@ def _tile_tail(session, feats, x_cl, dims, raw):
     """Fused tail (+ the deformed atlas) of one tile whose backbone features are `feats`."""
     eng = session.engine
     tail = session.model.head.tail(eng)
-    atlas = getattr(session, "atlas", None)
+    atlas = session.atlas
     if atlas is not None and not {"regx", "regy", "regz"} <= set(tail.map_names):
         atlas = None                                           # the reference's loop needs the registration head too
     # every consumer of a tile's maps (stitch / pack kernels, the atlas gather) keeps them only where the tile's input is
@@ -858,6 +935,14 @@ class HipStitchOps:
     def session(self):
         return self._session() if self._session is not None else None
 
+    @property
+    def keys(self):
+        return self.session.stitch_keys()
+
+    @property
+    def n_keys(self):
+        return len(self.keys)
+
     def _identity(self, k, dev):
         if (k, dev) not in self._sel:
             self._sel[(k, dev)] = torch.arange(k, dtype=torch.int32, device=dev)
@@ -945,18 +1030,12 @@ class HipStitchOps:
             self._lane_after[lane] = ev
         return res[0][0], [r[1] for r in res], None
 
-    def run_tile(self, im, out=None, lane=None, after=None):
-        """run_group for one tile: (keys, rows[, event])."""
-        keys, rows, done = self.run_group([im], [out], lane=lane, after=after)
-        return (keys, rows[0], done) if lane is not None else (keys, rows[0])
-
     def _tile_rows(self, outs, out, compact=None):
         maps_buf, names, label, x_cl = outs
-        keys = [k for k in STITCH_KEYS if k in names or (k == "label" and label is not None)]
+        keys, sel = stitch_selection(names, label is not None)
         skey = (tuple(names), label is not None)
         if skey not in self._sel:
-            self._sel[skey] = torch.tensor([names.index(k) if k != "label" else -1 for k in keys], dtype=torch.int32,
-                                           device=x_cl.device)
+            self._sel[skey] = torch.tensor(sel, dtype=torch.int32, device=x_cl.device)
         n = x_cl.numel()
         if compact is not None:
             pos, rs = compact
@@ -1013,15 +1092,59 @@ class HipStitchOps:
         L.check(self.lib.bfm_divide_by_count_multi(L.ptr(acc_buf), L.ptr(cnt), cnt.numel(), acc_buf.shape[0],
                                                    L.stream_ptr()), "divide_multi")
 
+    def stitch(self, srcs, ranges, shape, cnt, index=None):
+        """The stitched [K][D,H,W] volume of all tiles' rows (srcs[i]: tile i's, reference order): gather_all, or with
+        BFM_GATHER_STITCH=0 (read at call time) add_all per tile in that order on a zeroed volume + finalize_all."""
+        alloc = torch.empty if GATHER_STITCH else torch.zeros
+        acc_buf = alloc((srcs[0].shape[0],) + tuple(shape), dtype=torch.float32, device=srcs[0].device)
+        if GATHER_STITCH:
+            self.gather_all(acc_buf, srcs, ranges, shape, index=index)
+            return acc_buf
+        for rng, rows in zip(ranges, srcs):
+            self.add_all(acc_buf, rows, rng, shape)
+        self.finalize_all(acc_buf, cnt)
+        return acc_buf
+
+
+class _PerTileOps:
+    """The ops interface of the tile flows (n_keys, keys, index_volume, run_group, stitch) around per-tile stand-in ops
+    -- objects with `keys`, run_tile(im) -> (keys, rows [K][n]), add(acc, rows_j, rng, shape) and finalize(acc, cnt),
+    as the gloo tests inject them to run the sharding and ordering logic without a GPU.  Dense rows, no lanes."""
+
+    def __init__(self, ops, session=None):
+        self.ops = ops
+        self.keys = list(getattr(ops, "keys", None) or (session.stitch_keys() if session is not None else STITCH_KEYS))
+        self.n_keys = getattr(ops, "n_keys", len(self.keys))
+
+    def index_volume(self, full_im, ranges, counts=False):
+        return None
+
+    def run_group(self, ims, outs, lane=None, after=None):
+        for im, out in zip(ims, outs):
+            keys, rows = self.ops.run_tile(im)
+            if len(keys) != self.n_keys:
+                raise RuntimeError("ops.run_tile returned %d maps, expected %d" % (len(keys), self.n_keys))
+            out[:] = rows.reshape(-1)
+        return keys, outs, None
+
+    def stitch(self, srcs, ranges, shape, cnt, index=None):
+        acc_buf = torch.zeros((self.n_keys,) + tuple(shape), dtype=torch.float32, device=srcs[0].device)
+        for rng, rows in zip(ranges, srcs):
+            for j in range(self.n_keys):
+                self.ops.add(acc_buf[j], rows[j], rng, shape)
+        for j in range(self.n_keys):
+            self.ops.finalize(acc_buf[j], cnt)
+        return acc_buf
+
 
 def _exchange_buffer(session, name, numel, dev):
-    """Send / receive buffers of the multi-GPU exchange, kept on the session between volumes."""
-    bufs = getattr(session, "_dist_bufs", None)
-    if bufs is None:
-        bufs = session._dist_bufs = {}
-    t = bufs.get(name)
+    """Rows / send / receive buffers of the tile flows, kept on the session between volumes (padding is never read: no
+    fill).  Without a session: a fresh zero-filled one."""
+    if session is None:
+        return torch.zeros(numel, dtype=torch.float32, device=dev)
+    t = session._dist_bufs.get(name)
     if t is None or t.numel() != numel or t.device != torch.device(dev):
-        t = bufs[name] = torch.empty(numel, dtype=torch.float32, device=dev)
+        t = session._dist_bufs[name] = torch.empty(numel, dtype=torch.float32, device=dev)
     return t
 
 
@@ -1042,8 +1165,7 @@ def agree_on_conv_variants(session, full_im, ranges, group=None):
             os.environ.get("BFM_DIST_AGREE", "1") == "0":
         return
     sizes = sorted({tuple(b - a for a, b in r) for r in ranges})
-    agreed = session.__dict__.setdefault("_agreed_sizes", set())
-    todo = [s_ for s_ in sizes if s_ not in agreed]
+    todo = [s_ for s_ in sizes if s_ not in session._agreed_sizes]
     if not todo:
         return
     eng = session.engine
@@ -1059,10 +1181,8 @@ def agree_on_conv_variants(session, full_im, ranges, group=None):
     with torch.cuda.device(full_im.device):                   # RCCL stages the pickled table through the current device
         dist.broadcast_object_list(box, src=src, group=group)
     if eng.adopt_conv_choices(box[0]) and session._graphs:
-        session._graphs.clear()
-        session._graph_seen.clear()
-        session._graph_pool = {}
-    agreed.update(todo)
+        session.drop_graphs()
+    session._agreed_sizes.update(todo)
 
 
 def broadcast_volume(full_im, device, group=None, shape=None):
@@ -1109,15 +1229,19 @@ def tiled_inference_distributed(full_im, session, stride=[80, 80, 80], win_size=
     stats: a dict that receives what the exchange moved (bytes per peer and round, and on rank 0 two events that bracket
     what the gathers left exposed after its own tiles).
     Returns (acc, ranges, cnt) on rank 0, (None, ranges, None) elsewhere.
-    ``ops`` (run_tile/add/finalize) defaults to the HIP kernels; the gloo unit tests inject host ops
-    to exercise the sharding / ordering logic without a GPU."""
+    ``ops`` defaults to the session's HipStitchOps; the gloo unit tests inject per-tile host ops (run_tile / add /
+    finalize, wrapped in _PerTileOps) to exercise the sharding / ordering logic without a GPU or a session."""
     import torch.distributed as dist
     rank = dist.get_rank(group)
     world = dist.get_world_size(group)
     if rounds is None:
         rounds = DIST_ROUNDS
+    if ops is None and session is None:
+        raise L.BfmError("tiled_inference_distributed needs a session (or stand-in ops)")
     if ops is None:
-        ops = _session_stitch_ops(session) if session is not None else HipStitchOps(session)
+        ops = session.stitch_ops
+    elif not isinstance(ops, HipStitchOps):                    # stand-in ops take the session's keys at most, then run
+        ops, session = _PerTileOps(ops, session), None         # without it: fresh zeroed buffers, one lane
     if broadcast:
         if rank != 0 and full_im is not None:
             raise L.BfmError("broadcast=True: only rank 0 passes the volume")
@@ -1129,114 +1253,60 @@ def tiled_inference_distributed(full_im, session, stride=[80, 80, 80], win_size=
         raise L.BfmError("tiled_inference_distributed: this rank has no volume (pass broadcast=True on every rank)")
     shape = tuple(full_im.shape[2:])
     ranges = tiling_ranges(shape, stride, win_size)
-    owner = assign_tiles(ranges, world)
     dev = full_im.device
-    direct = hasattr(ops, "add_all")                           # HIP ops write straight into the send buffer
-    nkeys = getattr(ops, "n_keys", None)
-    if nkeys is None and hasattr(ops, "keys"):
-        nkeys = len(ops.keys)
-    if nkeys is None and session is not None:
-        nkeys = len(session.stitch_keys())
-    if nkeys is None:
-        nkeys = len(STITCH_KEYS)
-    # per rank: its tiles as batches of same-shape tiles (tile_batches: the deep levels of a batch run as one launch per
-    # layer), largest batch first; slot[i] = (round, offset in that round's buffer) with round k = the k-th batch of
-    # every rank.  Rank 0's own tiles never travel: they are packed into a private buffer per round, and the round's
-    # (padded) size is set by the peers alone.
-    nlanes = session.lanes if (session is not None and getattr(session, "use_graphs", False)) else 1
+    nkeys = ops.n_keys
+    graphs = session is not None and session.use_graphs
+    nlanes = session.lanes if graphs else 1                    # > 1: this rank's batches run on its lanes' streams
     # compact rows: a tile ships the voxels its mask keeps (known from the volume on every rank before any tile runs:
     # HipStitchOps.index_volume brings the counts to the host, the same on every rank) -- 1/5 of the bytes on a head in
     # a 256^3 box
-    index = None
-    if direct and COMPACT and GATHER_STITCH and dev.type == "cuda" and hasattr(ops, "index_volume"):
-        index = ops.index_volume(full_im, ranges, counts=True)
+    index = ops.index_volume(full_im, ranges, counts=True) if COMPACT and GATHER_STITCH else None
     width = [index.nnz[i] if index is not None else tile_cost(r) for i, r in enumerate(ranges)]   # columns per row
     # a tile whose input is all zero keeps nothing of what it computes (scripts/demo_test.py:88-100) and adds +0 wherever
     # it is stitched: with the counts on the host it is not run at all (BFM_SKIP_EMPTY_TILES=0: run it)
-    live = [index is None or not SKIP_EMPTY or width[i] > 0 for i in range(len(ranges))]
-    batches_of = [tile_batches(ranges, [i for i in range(len(ranges)) if owner[i] == r and live[i]], min_batches=nlanes)
-                  for r in range(world)]
-    nrounds = max([len(b) for b in batches_of] + [1]) if rounds else 1
-    round_of, off_of = {}, {}
-    round_numel = [1] * nrounds
-    own_numel = [1] * nrounds
-    for i in range(len(ranges)):
-        if not live[i]:
-            round_of[i], off_of[i] = 0, 0                      # nothing computed, nothing shipped, nothing read
-    for r in range(world):
-        fill = [0] * nrounds
-        for k, batch in enumerate(batches_of[r]):
-            kk = k if rounds else 0
-            for i in batch:
-                round_of[i], off_of[i] = kk, fill[kk]
-                fill[kk] += width[i] * nkeys
-        for kk in range(nrounds):
-            if r == 0:
-                own_numel[kk] = max(own_numel[kk], fill[kk])
-            else:
-                round_numel[kk] = max(round_numel[kk], fill[kk])
-
-    def _buf(name, numel):
-        if session is not None and direct:
-            return _exchange_buffer(session, name, numel, dev)     # persistent; padding is never read: no fill
-        return torch.zeros(numel, dtype=torch.float32, device=dev)
-
-    if direct and session is not None and dev.type == "cuda":
+    live = [index is None or not SKIP_EMPTY or w > 0 for w in width]
+    plan = plan_exchange(ranges, world, rounds, nlanes, nkeys, width, live)
+    nrounds = len(plan.round_numel)
+    if session is not None:
         agree_on_conv_variants(session, full_im, ranges, group)
     keys = None
     works, gathered, own, pending = [], [], [], []
-    mine = batches_of[rank]
-    lanes = session.lanes if (direct and session is not None and session.use_graphs and dev.type == "cuda") else 1
-    start = None
-    if lanes > 1:
+    start, lane_load = None, []                                # one lane: on the caller's stream
+    if nlanes > 1:
+        lane_load = [0] * nlanes                               # this rank's batches go to its less loaded lane
         start = torch.cuda.Event()
         start.record(torch.cuda.current_stream(dev))           # send buffers are free, the input is in place
-    lane_load = [0] * lanes                                    # this rank's batches go to its less loaded lane
+
+    def settle():                                              # warm-up only: no transfer in flight while a graph is
+        for w in works:                                        # being captured
+            w.wait()
+
     for kk in range(nrounds):
-        sbuf = _buf("send%d" % kk, round_numel[kk])            # on rank 0: the padding the gather asks of its root
+        sbuf = _exchange_buffer(session, "send%d" % kk, plan.round_numel[kk], dev)   # on rank 0: the gather's padding
         dst = sbuf
         if rank == 0:
-            dst = _buf("own%d" % kk, own_numel[kk])
+            dst = _exchange_buffer(session, "own%d" % kk, plan.own_numel[kk], dev)
             own.append(dst)
-        todo = [b_ for k, b_ in enumerate(mine) if (k if rounds else 0) == kk]
-        for batch in todo:
-            ims = [full_im[:, :, ranges[i][0][0]:ranges[i][0][1], ranges[i][1][0]:ranges[i][1][1],
-                           ranges[i][2][0]:ranges[i][2][1]] for i in batch]
-            outs = [dst[off_of[i]:off_of[i] + width[i] * nkeys] for i in batch]
-            cargs = dict(index=index, tiles_idx=batch, strides=[width[i] for i in batch]) if index is not None else {}
-            lane = min(range(lanes), key=lambda j: (lane_load[j], j))
-            lane_load[lane] += sum(tile_time(ranges[i]) for i in batch)
-            if direct and session is not None and session.use_graphs and \
-                    not session.has_graph(tuple(ims[0].shape[2:]), lane, len(batch)):
-                for w in works:                                    # warm-up only: no transfer in flight while a graph
-                    w.wait()                                       # is being captured
-            if direct and lanes > 1:
-                # this rank's batches run on its lanes' streams, independently of each other; the gather of a round waits
-                # for that round's tiles only -- and on rank 0 for none: its receives are posted at once, whatever it is
-                # still computing itself
-                keys, _, done = ops.run_group(ims, outs, lane=lane, after=start, **cargs)
-                if done is not None:
-                    if rank == 0:
-                        pending.append(done)
-                    else:
-                        torch.cuda.current_stream(dev).wait_event(done)
-            elif direct:
-                keys, _, _ = ops.run_group(ims, outs, **cargs)
-            else:
-                for i, im in zip(batch, ims):
-                    keys, rows = ops.run_tile(im)
-                    if len(keys) != nkeys:
-                        raise RuntimeError("ops.run_tile returned %d maps, expected %d" % (len(keys), nkeys))
-                    n = tile_cost(ranges[i]) * nkeys
-                    dst[off_of[i]:off_of[i] + n] = rows.reshape(-1)
-        g = [_buf("recv%d_%d" % (kk, r), round_numel[kk]) for r in range(world)] if rank == 0 else None
+        todo = [b_ for k, b_ in enumerate(plan.batches_of[rank]) if (k if rounds else 0) == kk]
+        slot = {i: dst[plan.off_of[i]:plan.off_of[i] + width[i] * nkeys] for b_ in todo for i in b_}
+        # this rank's batches run on its lanes' streams, independently of each other; the gather of a round waits for that
+        # round's tiles only -- and on rank 0 for none: its receives are posted at once, whatever it is still computing
+        keys_kk, done = _run_batches(session, ops, full_im, ranges, todo, slot, width, index, lane_load, start,
+                                     settle if graphs else None)
+        keys = keys_kk or keys
+        if rank == 0:
+            pending += done
+        for ev in done if rank != 0 else []:                   # a peer's gather waits for its round's rows
+            torch.cuda.current_stream(dev).wait_event(ev)
+        g = [_exchange_buffer(session, "recv%d_%d" % (kk, r), plan.round_numel[kk], dev) for r in range(world)] \
+            if rank == 0 else None
         gathered.append(g)
         works.append(dist.gather(sbuf, g, dst=0, group=group, async_op=True))
     if stats is not None:
         stats["world"] = world
         stats["rounds"] = nrounds
-        stats["round_bytes_per_peer"] = [int(v) * 4 for v in round_numel]
-        stats["bytes_sent_per_peer"] = int(sum(round_numel)) * 4 if world > 1 else 0
+        stats["round_bytes_per_peer"] = [int(v) * 4 for v in plan.round_numel]
+        stats["bytes_sent_per_peer"] = int(sum(plan.round_numel)) * 4 if world > 1 else 0
         stats["compact_rows"] = index is not None
     if rank == 0 and stats is not None and dev.type == "cuda":
         for ev in pending:                                    # rank 0's own tiles are done ...
@@ -1250,37 +1320,12 @@ def tiled_inference_distributed(full_im, session, stride=[80, 80, 80], win_size=
         stats["ev_gathers_done"].record(torch.cuda.current_stream(dev))
     if rank != 0:
         return None, ranges, None
-    if keys is None:
-        keys = (session.stitch_keys() if session is not None else [k for k in STITCH_KEYS])[:nkeys]
     for ev in pending:                                        # rank 0's own tiles (lanes)
         torch.cuda.current_stream(dev).wait_event(ev)
     srcs = []
-    for i, rng in enumerate(ranges):                          # reference tile order
-        nv = width[i]
-        src = own[round_of[i]] if owner[i] == 0 else gathered[round_of[i]][owner[i]]
-        srcs.append(src[off_of[i]:off_of[i] + nv * nkeys].reshape(nkeys, nv))
-    if session is not None and direct:
-        cnt = _cached_count_volume(session, shape, ranges, stride, win_size, dev)
-    else:
-        cnt = count_volume(shape, ranges, dev)
-    if hasattr(ops, "gather_all") and GATHER_STITCH:
-        acc_buf = torch.empty((nkeys,) + shape, dtype=torch.float32, device=dev)
-        if index is not None:
-            ops.gather_all(acc_buf, srcs, ranges, shape, index=index)
-        else:
-            ops.gather_all(acc_buf, srcs, ranges, shape)      # one launch: sum in tile order, / count, write once
-    else:
-        acc_buf = torch.zeros((nkeys,) + shape, dtype=torch.float32, device=dev)
-        for rng, rows in zip(ranges, srcs):
-            if direct:
-                ops.add_all(acc_buf, rows, rng, shape)
-            else:
-                for j in range(nkeys):
-                    ops.add(acc_buf[j], rows[j], rng, shape)
-        if direct:
-            ops.finalize_all(acc_buf, cnt)
-        else:
-            for j in range(nkeys):
-                ops.finalize(acc_buf[j], cnt)
-    acc = OrderedDict((k, acc_buf[j]) for j, k in enumerate(keys))
-    return acc, ranges, cnt
+    for i in range(len(ranges)):                              # reference tile order
+        src = own[plan.round_of[i]] if plan.owner[i] == 0 else gathered[plan.round_of[i]][plan.owner[i]]
+        srcs.append(src[plan.off_of[i]:plan.off_of[i] + width[i] * nkeys].reshape(nkeys, width[i]))
+    cnt = _cached_count_volume(session, shape, ranges, stride, win_size, dev)
+    acc_buf = ops.stitch(srcs, ranges, shape, cnt, index=index)
+    return OrderedDict((k, acc_buf[j]) for j, k in enumerate(keys or ops.keys[:nkeys])), ranges, cnt

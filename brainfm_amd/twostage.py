@@ -1,48 +1,22 @@
 """The pathology-robust two-stage ("inpainting") inference harness of the reference (utils/test_utils.py:316-350 and the
 tile loop of scripts/demo_test.py:66-119 around it), beside test_utils.py, whose configuration globals
-(default_gen_cfg_file, default_train_cfg_file, ...), session cache and tiling / stitch helpers it uses:
+(default_gen_cfg_file, default_train_cfg_file, ...), session cache (_cached_session, _default_cfgs), output assembly
+(_tail_outputs) and tiling / stitch helpers it uses:
 
   TwoStageSession(gen_args, train_args, device, ...)      both models of build_inpaint_model resident
   evaluate_image_twostage(inputs, pathol_ckp_path, task_ckp_path, ...)   :316-350, sessions cached like evaluate_image
   tiled_inference_twostage(full_im, session, stride, win_size)           one GPU, eager
 
 All arithmetic runs in libbrainfm_hip.so."""
-import os
 from collections import OrderedDict
 
 import torch
 
 from . import _lib as L
-from . import cfg as _cfg
 from . import misc as MI
 from . import models as M
 from . import test_utils as TU
 from .engine import UNetEngine
-
-
-def _tail_outputs(tail, maps, seg, label, out):
-    """The fused tail's results under the reference's output keys, added to `out` (Trainer/models/__init__.py:307-352)."""
-    order = ["T1", "T2", "FLAIR", "CT", "segmentation", "high_res_residual", "high_res", "bias_field", "lp", "lw",
-             "rp", "rw", "fake_cortical", "regx", "regy", "regz"]
-
-    def chans(k):
-        # a head with c channels (`losses.uncertainty`: value + sigma) is c adjacent rows of the tail's buffer:
-        # the reference keeps them as one (1,c,D,H,W) tensor (Trainer/models/__init__.py:57-111, joiner.py:50-55)
-        r0, c = tail.channels.get(k, (None, 1))
-        return tail.last_buf[r0:r0 + c][None] if c > 1 else maps[k][None, None]
-
-    for k in order:
-        if k == "segmentation":
-            if seg is not None:
-                out[k] = seg.permute(3, 0, 1, 2).unsqueeze(0)
-        elif k in maps:
-            out[k] = chans(k)
-    for k, v in maps.items():
-        if k not in out and "#" not in k:
-            out[k] = chans(k)
-    if label is not None:
-        out["label"] = label[None, None]
-    return out
 
 
 class TwoStageSession:
@@ -76,8 +50,7 @@ class TwoStageSession:
     def stitch_keys(self):
         """The keys tiled_inference_twostage stitches: STITCH_KEYS + ['pathology'], those the two head sets produce."""
         tail = self.task_model.head.tail(self.task_engine)
-        names = set(tail.map_names) | {"pathology"}
-        return [k for k in TU.STITCH_KEYS + ["pathology"] if k in names or (k == "label" and tail.desc.n_seg > 0)]
+        return TU.stitch_selection(list(tail.map_names), tail.desc.n_seg > 0)[0] + ["pathology"]
 
     def run_stages(self, x_cl, dims, want_feat=True, want_seg=True):
         """Both stages of one sample.  x_cl: (D,H,W,1) contiguous fp32.  Returns (stage 0: (feats, maps, fnorm),
@@ -125,7 +98,7 @@ class TwoStageSession:
             return [UNetEngine.as_ncdhw(f) for f in bufs]
 
         task = OrderedDict(feat_task=feat_list(feats1, fnorm1))
-        _tail_outputs(tail1, maps1, seg, label, task)
+        TU._tail_outputs(tail1, maps1, seg, label, task)
         pathol = OrderedDict(feat_pathol=feat_list(feats0, fnorm0), pathology=maps0["pathology"][None, None])
         out = MI.merge_list_of_dict([task], [pathol])[0]
         if feature_only:
@@ -140,17 +113,11 @@ def evaluate_image_twostage(inputs, pathol_ckp_path, task_ckp_path, feature_only
     device = TU._resolve_device(device)
     if torch.device(device).type != "cuda":
         raise L.BfmError("evaluate_image_twostage runs on a HIP device only; there is no CPU fallback in the product path")
-    mtimes = tuple(os.path.getmtime(p) if p and os.path.exists(p) else None for p in (pathol_ckp_path, task_ckp_path))
-    key = ("twostage", pathol_ckp_path, task_ckp_path, mtimes, gen_cfg, model_cfg, str(device))
-    if key not in TU._SESSIONS:
-        if TU.default_gen_cfg_file is None or TU.default_train_cfg_file is None:
-            raise ValueError("set brainfm_amd.test_utils.default_gen_cfg_file / default_train_cfg_file "
-                             "(absolute paths of cfgs/generator/default.yaml, cfgs/trainer/default_train.yaml)")
-        gen_args = _cfg.preprocess_cfg([TU.default_gen_cfg_file, gen_cfg], cfg_dir=TU.gen_cfg_dir)
-        train_args = _cfg.preprocess_cfg([TU.default_train_cfg_file, TU.default_val_file, model_cfg], cfg_dir=TU.train_cfg_dir)
-        TU._SESSIONS[key] = TwoStageSession(gen_args, train_args, device, pathol_ckp_path=pathol_ckp_path,
-                                         task_ckp_path=task_ckp_path)
-    return TU._SESSIONS[key].evaluate(inputs, feature_only)
+    key = ("twostage", pathol_ckp_path, task_ckp_path, (TU._mtime(pathol_ckp_path), TU._mtime(task_ckp_path)), gen_cfg,
+           model_cfg, str(device))
+    build = lambda: TwoStageSession(*TU._default_cfgs(gen_cfg, model_cfg), device, pathol_ckp_path=pathol_ckp_path,
+                                    task_ckp_path=task_ckp_path)
+    return TU._cached_session(key, build).evaluate(inputs, feature_only)
 
 
 @torch.no_grad()
@@ -173,9 +140,8 @@ def tiled_inference_twostage(full_im, session, stride=[80, 80, 80], win_size=[16
     acc_buf = torch.zeros((len(keys),) + shape, dtype=torch.float32, device=eng.device)
     acc = OrderedDict((k, acc_buf[j]) for j, k in enumerate(keys))
     for rng in ranges:
-        (x0, x1), (y0, y1), (z0, z1) = rng
-        x_cl = eng.to_cl(full_im[:, :, x0:x1, y0:y1, z0:z1])
-        dims = (x1 - x0, y1 - y0, z1 - z0)
+        x_cl = eng.to_cl(TU.tile_window(full_im, rng))
+        dims = tuple(b - a for a, b in rng)
         (_, maps0, _), (_, maps1, _, _, label, _), _ = session.run_stages(x_cl, dims, want_feat=False, want_seg=False)
         maps = dict(maps1)
         maps["pathology"] = maps0["pathology"]

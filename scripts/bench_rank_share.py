@@ -1,6 +1,6 @@
 """What each rank of an N-rank run of the 256^3 volume computes, timed alone on ONE GPU (no transfers): its batches of
-same-shape tiles on its two lanes in the order tiled_inference_distributed runs them, plus -- on rank 0 -- the one-launch
-stitch of all 27 tiles.
+same-shape tiles on its two lanes as tiled_inference_distributed runs them (its plan_exchange and _run_batches, one
+round), plus -- on rank 0 -- the stitch of all 27 tiles.
 A model of the N-GPU step without the exchange: max over ranks.   python scripts/bench_rank_share.py [N=8] [size=256]"""
 import os
 import sys
@@ -20,18 +20,14 @@ sess.use_graphs = True
 full = bench.make_volume(n, dev)
 stride, win = [80] * 3, [160] * 3
 ranges = TU.tiling_ranges((n, n, n), stride, win)
-owner = TU.assign_tiles(ranges, world)
-batches_of = [TU.tile_batches(ranges, [i for i in range(len(ranges)) if owner[i] == r_], min_batches=sess.lanes)
-              for r_ in range(world)]
-ops = TU.HipStitchOps(sess)
-nkeys = len(sess.stitch_keys())
-offs, total = [], 0
-for r in ranges:
-    offs.append(total)
-    total += TU.tile_cost(r) * nkeys
-buf = torch.zeros(total, dtype=torch.float32, device=dev)
-srcs = [buf[offs[i]:offs[i] + TU.tile_cost(r) * nkeys].view(nkeys, TU.tile_cost(r)) for i, r in enumerate(ranges)]
-acc = torch.empty((nkeys, n, n, n), dtype=torch.float32, device=dev)
+ops = sess.stitch_ops
+nkeys = ops.n_keys
+width = [TU.tile_cost(r) for r in ranges]
+batches_of = TU.plan_exchange(ranges, world, False, sess.lanes, nkeys, width, [True] * len(ranges)).batches_of
+offs = [sum(width[:i]) * nkeys for i in range(len(ranges))]          # every tile's slot in one buffer, in tile order
+buf = torch.zeros(sum(width) * nkeys, dtype=torch.float32, device=dev)
+slot = [buf[o:o + w * nkeys] for o, w in zip(offs, width)]
+cnt = TU.count_volume((n, n, n), ranges, dev)
 
 
 def share(rank):
@@ -39,22 +35,11 @@ def share(rank):
     start = torch.cuda.Event()
     start.record(main)
     index = ops.index_volume(full, ranges) if TU.COMPACT else None
-    load, last = [0] * sess.lanes, {}
-    for batch in batches_of[rank]:
-        k = min(range(sess.lanes), key=lambda j: (load[j], j))
-        load[k] += sum(TU.tile_time(ranges[i]) for i in batch)
-        ims = [full[:, :, ranges[i][0][0]:ranges[i][0][1], ranges[i][1][0]:ranges[i][1][1], ranges[i][2][0]:ranges[i][2][1]]
-               for i in batch]
-        outs = [buf[offs[i]:offs[i] + TU.tile_cost(ranges[i]) * nkeys] for i in batch]
-        _, _, done = ops.run_group(ims, outs, lane=k, after=start, index=index, tiles_idx=batch,
-                                   strides=[TU.tile_cost(ranges[i]) for i in batch])
-        if done is not None:
-            last[k] = done
-    for ev in last.values():
+    _, done = TU._run_batches(sess, ops, full, ranges, batches_of[rank], slot, width, index, [0] * sess.lanes, start)
+    for ev in done:
         main.wait_event(ev)
     if rank == 0:
-        ops.gather_all(acc, srcs, ranges, (n, n, n), index=index)
-    return [i for b_ in batches_of[rank] for i in b_]
+        ops.stitch([s_.view(nkeys, w) for s_, w in zip(slot, width)], ranges, (n, n, n), cnt, index=index)
 
 
 worst = 0.0
@@ -65,7 +50,7 @@ for rank in range(world):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for _ in range(5):
-        mine = share(rank)
+        share(rank)
     b.record()
     torch.cuda.synchronize()
     ms = a.elapsed_time(b) / 5
