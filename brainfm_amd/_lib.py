@@ -300,6 +300,15 @@ SIGNATURES = {
     "bfm_head_bias_lrelu": (_I, [_P, _P, _I, _L, _F, _P, _P, _P]),
     "bfm_head_bias_lrelu_bwd_workspace": (_Z, [_I, _L]),
     "bfm_head_bias_lrelu_bwd": (_I, [_P, _P, _I, _L, _F, _P, _P, _P, _P, _Z, _P]),
+    "bfm_eval_pair_stats_workspace": (_Z, []),
+    "bfm_eval_pair_stats": (_I, [_P, _P, _L, _P, _P, _Z, _P]),
+    "bfm_eval_l1_nonzero": (_I, [_P, _P, _I, _L, _P, _P]),
+    "bfm_eval_channel_sums_workspace": (_Z, [_I, _L]),
+    "bfm_eval_channel_sums": (_I, [_P, _P, _I, _L, _P, _P, _Z, _P]),
+    "bfm_eval_label_counts": (_I, [_P, _P, _L, _P, _I, _I, _P, _P]),
+    "bfm_eval_ssim3d_workspace": (_Z, [_I, _I, _I, _I]),
+    "bfm_eval_ssim3d": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(_F), _P, _P, _P, _Z, _P]),
+    "bfm_eval_avgpool2_pair": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

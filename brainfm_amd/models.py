@@ -735,6 +735,31 @@ class SetCriterion(nn.Module):
         return losses
 
 
+def get_evaluator(args, task, device):
+    """Trainer/models/__init__.py:131-158: the metric names of a task set and their Evaluator (brainfm_amd.evaluator).
+    The reference's 'T1' branch under `else` cannot be reached (the first test catches 'T1'); it is kept so that every
+    task set gives the reference's list."""
+    from .evaluator import Evaluator
+    metric_names = []
+    if 'T1' in task or 'T2' in task or 'FLAIR' in task or 'CT' in task:
+        metric_names += ['feat_ssim', 'feat_ms_ssim', 'feat_l1']
+    else:
+        if 'T1' in task:
+            metric_names += ['recon_l1', 'recon_psnr', 'recon_ssim', 'recon_ms_ssim']
+        if 'super_resolution' in task:
+            metric_names += ['sr_l1', 'sr_psnr', 'sr_ssim', 'sr_ms_ssim']
+        if 'bias_field' in task:
+            metric_names += ['bf_normalized_l2', 'bf_corrected_l1']
+        if 'segmentation' in task:
+            metric_names += ['seg_dice']
+        if 'pathology' in task:
+            metric_names += ['pathol_dice']
+
+    assert len(metric_names) > 0
+
+    return Evaluator(args=args, metric_names=metric_names, device=device)
+
+
 def get_criterion(gen_args, train_args, tasks, device, exclude_keys=[]):
     """Trainer/models/__init__.py:162-267 for the task the forward surface evaluates itself: 'contrastive' -> SetCriterion
     when train_args carries what it reads (weights.contrastive, contrastive_temperatures); otherwise None, as for every

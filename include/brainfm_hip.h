@@ -1054,6 +1054,50 @@ size_t bfm_head_bias_lrelu_bwd_workspace(int C, int64_t nvox);
 int bfm_head_bias_lrelu_bwd(const float* dY, const float* Y, int C, int64_t nvox, float slope, float* dP, float* dbias,
                             float* absmax_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
 
+/* ---- the evaluator (Trainer/models/evaluator.py; eval_metrics.hip) ----------------------------------------------------
+ * Volumes are contiguous fp32 (or int32 labels), planes = B * C.  Every workspace and every fp64 / int64 output is 8-byte
+ * aligned device memory.  Sums are fp64 block partials folded in a fixed order (no float atomics: the same bits on every
+ * run); nothing is written when a call is rejected.
+ *
+ * get_l1 / get_psnr / get_normalized_l2 (evaluator.py:100-119) and the min / max of get_ssim / get_ms_ssim (:125-126,
+ * :134-135) from one read of o (output) and t (target): stats[0..9] = sum|o-t|, sum(o-t)^2, sum(o t), sum(o^2), sum(t^2),
+ * min o, max o, min t, max t, count(t != 0); differences and products are formed in fp64.  Min and max propagate NaN as
+ * torch's do.  The scores are host arithmetic on these numbers. */
+size_t bfm_eval_pair_stats_workspace(void);
+int bfm_eval_pair_stats(const float* o, const float* t, int64_t n, double* stats /*[10]*/, void* workspace,
+                        size_t workspace_bytes, bfm_stream_t stream);
+/* get_l1(nonzero_only=True), evaluator.py:106-108: the reference sums over dim 0, the batch, so the result is a volume:
+ * out[i] = sum_b |t[b][i] - o[b][i]| [t[b][i] != 0] / sum_b [t[b][i] != 0] in fp32 (NaN where no sample's target is
+ * non-zero); n = elements per sample. */
+int bfm_eval_l1_nonzero(const float* o, const float* t, int B, int64_t n, float* out, bfm_stream_t stream);
+/* get_dice on probability maps, evaluator.py:96-97: out[p] = {sum(o t), sum(o + t)} over plane p's n_per voxels. */
+size_t bfm_eval_channel_sums_workspace(int planes, int64_t n_per);
+int bfm_eval_channel_sums(const float* o, const float* t, int planes, int64_t n_per, double* out /*[planes][2]*/,
+                          void* workspace, size_t workspace_bytes, bfm_stream_t stream);
+/* get_onehot + get_dice on two label maps (evaluator.py:30-40,96-97,170-172) without the one-hot: with c = lut[label],
+ * counts[l] = |{P: c == l}|, counts[n_labels + l] = |{T: c == l}|, counts[2 n_labels + l] = |{both}|, and
+ * counts[3 n_labels] = how many labels of P and T lie outside [0, nlut) (the reference's LUT indexing raises IndexError
+ * there; a lut entry outside [0, n_labels) counts the same way) -- such voxels enter no class.  counts is zeroed by the call.
+ * Integer LDS histograms and integer global adds: exact in any order.  n_labels <= 256, n <= 2^40 (BFM_E_SHAPE). */
+int bfm_eval_label_counts(const int32_t* P, const int32_t* T, int64_t n, const int32_t* lut, int nlut, int n_labels,
+                          int64_t* counts /*[3 n_labels + 1]*/, bfm_stream_t stream);
+/* pytorch_msssim 1.0's _ssim on (planes, D, H, W) volumes (get_ssim / get_ms_ssim, evaluator.py:121-141; data range 1,
+ * K = (0.01, 0.03)): the 11-tap window win_host (host, fp32, sums to 1) filters X, Y, XX, YY, XY "valid" along every axis
+ * of length >= 11 (a shorter axis is left unfiltered at full length), then
+ *   cs = (2 s12 + C2) / (s1 + s2 + C2),  ssim = (2 m1 m2 + C1) / (m1^2 + m2^2 + C1) * cs,
+ * out[p] = {mean ssim, mean cs} of plane p (fp64 sums of the fp32 maps).  The filtered moments never leave the CU.
+ * norm_dev (or NULL) = {min X, max X, min Y, max Y} on the device: each value is read as (x - min) / (max - min), fp32, a
+ * true division -- a constant volume gives NaN, as the reference does.  H * W < 2^31, planes <= 65535 (BFM_E_SHAPE). */
+size_t bfm_eval_ssim3d_workspace(int planes, int D, int H, int W);
+int bfm_eval_ssim3d(const float* X, const float* Y, int planes, int D, int H, int W, const float* win_host /*[11]*/,
+                    const double* norm_dev /*[4] or NULL*/, double* out /*[planes][2]*/, void* workspace,
+                    size_t workspace_bytes, bfm_stream_t stream);
+/* The pooling between the scales of pytorch_msssim's ms_ssim: F.avg_pool3d(kernel 2, padding n % 2 per axis), padded
+ * zeros counted in the divisor, of X and Y in one launch: outputs (planes, (D+1)/2, (H+1)/2, (W+1)/2).  norm_dev as above
+ * (scale 0 reads the raw volumes). */
+int bfm_eval_avgpool2_pair(const float* X, const float* Y, int planes, int D, int H, int W,
+                           const double* norm_dev /*[4] or NULL*/, float* Xo, float* Yo, bfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
