@@ -6,8 +6,9 @@
 //     grad_l1   mean|d_x o - d_x t| + mean|d_y ..| + mean|d_z ..|    forward differences, last slice zero (GradientLoss)
 //     seg       CE = mean_v( -sum_c log(max(p,1e-5)) * w_c * t_c ),  Dice = sum_c w_c (1 - 2 sum_v p t / max(sum_v (p+t), 1e-5))
 //               with p = softmax(logits)  (SegProcessor, joiner.py:69-77)
-//   Every loss kernel ADDS  coef * dL/d(raw)  into its columns of dRaw ([nvox][n_out], channels-last) and returns the
-//   loss value in fp64; reductions are two-stage with a fixed order.
+//   Every loss kernel ADDS  coef * dL/d(raw)  into its columns of dRaw and returns the loss value in fp64; reductions are
+//   two-stage with a fixed order.  raw / dRaw come channels-last ([nvox][n_out]) or as rows ([n_out] rows of nvox values):
+//   each loss has ONE per-voxel expression, written once, and a kernel per layout around it that keeps its own staging.
 //   heads:   raw = Fn W^T + b,  Fn = F.normalize(feat)  (head.py:52-59, model.py:207)
 //   AdamW:   torch.optim.AdamW semantics (decoupled weight decay), one fused elementwise kernel.
 #include "bfm_common.h"
@@ -41,38 +42,10 @@ __global__ void final_sum_kernel(const double* __restrict__ part, int nb, double
 }
 
 // ----------------------------------------------------------------------------- L1
-// out column `co` of raw vs target [nvox] (optional weight [nvox]); clampv > 0: the prediction is clamp(o, +-clampv)
-// first (DistProcessor), whose gradient is zero where it clamps
-__global__ void __launch_bounds__(256) l1_kernel(const float* __restrict__ raw, int n_out, int co,
-                                                 const float* __restrict__ target, const float* __restrict__ weight,
-                                                 const float* __restrict__ mask_mul, int64_t nvox, float clampv,
-                                                 int l2, float coef, float* __restrict__ dRaw,
-                                                 double* __restrict__ part) {
-    __shared__ double red[256];
-    double acc = 0.0;
-    GRID_STRIDE(v, nvox) {
-        float o = raw[v * n_out + co];
-        bool live = true;
-        if (clampv > 0.f) {
-            if (o > clampv) { o = clampv; live = false; }
-            else if (o < -clampv) { o = -clampv; live = false; }
-        }
-        const float m = mask_mul ? mask_mul[v] : 1.f;        // bias field: both sides are multiplied by the soft mask
-        const float w = weight ? weight[v] : 1.f;
-        const float d = o * m - target[v] * m;
-        acc += (double)((l2 ? d * d : fabsf(d)) * w);
-        const float sg = l2 ? 2.f * d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
-        if (live && dRaw) dRaw[v * n_out + co] += coef * sg * w * m;
-    }
-    acc = block_sum(acc, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// All l1 / l2 entries of one sample in ONE pass over the head outputs: a block stages rows of raw (and of dRaw) for a
-// run of voxels through LDS with coalesced row segments, each thread handles one voxel and walks the entry table
-// (column, target, weight, mask, clamp, l2, coefficient); per-entry sums are folded per block in fp64 in a fixed order.
-// The single-entry kernel above re-reads a 276-byte-strided column of the whole tensor per launch (22 launches, 3.4 ms at
-// 128^3).
+// Every l1 / l2 entry of one sample in ONE pass over the head outputs.  An entry is a column of raw against target [nvox]
+// (optional weight [nvox], optional mask [nvox]: bias field, both sides are multiplied by the soft mask); clampv > 0: the
+// prediction is clamp(o, +-clampv) first (DistProcessor), whose gradient is zero where it clamps.  Per-entry sums are folded
+// per block in fp64 in a fixed order.
 constexpr int L1M_MAX = 32;
 struct L1Entry {
     int col;
@@ -88,6 +61,36 @@ struct L1Table {
     int n;
 };
 
+// entry e at voxel v on the head output o: the loss term goes into acc (fp64), grad = coef * dL/do; returns `live`, false
+// where the clamp holds o (no gradient there)
+__device__ __forceinline__ bool l1_term(const L1Entry& e, int64_t v, float o, double& acc, float& grad) {
+    bool live = true;
+    if (e.clampv > 0.f) {
+        if (o > e.clampv) { o = e.clampv; live = false; }
+        else if (o < -e.clampv) { o = -e.clampv; live = false; }
+    }
+    const float m = e.mask ? e.mask[v] : 1.f;
+    const float w = e.weight ? e.weight[v] : 1.f;
+    const float d = o * m - e.target[v] * m;
+    acc += (double)((e.l2 ? d * d : fabsf(d)) * w);
+    const float sg = e.l2 ? 2.f * d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
+    grad = e.coef * sg * w * m;
+    return live;
+}
+
+// per-entry block sums of the multi kernels (l1 and gradient l1): part [nb][L1M_MAX]
+__device__ __forceinline__ void l1_multi_block_sums(const double (&acc)[L1M_MAX], int n, double* red, double* part) {
+#pragma unroll
+    for (int k = 0; k < L1M_MAX; ++k) {
+        if (k >= n) continue;                                      // wave-uniform
+        const double sk = block_sum(acc[k], red);
+        if (threadIdx.x == 0) part[(int64_t)blockIdx.x * L1M_MAX + k] = sk;
+    }
+}
+
+// channels-last [nvox][n_out]: a block stages rows of raw (and of dRaw) for a run of voxels through LDS with coalesced row
+// segments, each thread handles one voxel and walks the entry table (one 4-byte column out of every 276-byte row
+// otherwise)
 __global__ void __launch_bounds__(256) l1_multi_kernel(const float* __restrict__ raw, int n_out, int64_t nvox, int tile_vox,
                                                        const L1Table tab, float* __restrict__ dRaw,
                                                        double* __restrict__ part /*[nb][L1M_MAX]*/) {
@@ -117,18 +120,8 @@ __global__ void __launch_bounds__(256) l1_multi_kernel(const float* __restrict__
             for (int k = 0; k < L1M_MAX; ++k) {
                 if (k >= tab.n) continue;                          // (a break keeps the loop rolled and acc[] in scratch)
                 const L1Entry& e = tab.e[k];
-                float o = traw[t * ld + e.col];
-                bool live = true;
-                if (e.clampv > 0.f) {
-                    if (o > e.clampv) { o = e.clampv; live = false; }
-                    else if (o < -e.clampv) { o = -e.clampv; live = false; }
-                }
-                const float m = e.mask ? e.mask[v] : 1.f;
-                const float w = e.weight ? e.weight[v] : 1.f;
-                const float d = o * m - e.target[v] * m;
-                acc[k] += (double)((e.l2 ? d * d : fabsf(d)) * w);
-                const float sg = e.l2 ? 2.f * d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
-                if (live) tgrd[t * ld + e.col] += e.coef * sg * w * m;
+                float g;
+                if (l1_term(e, v, traw[t * ld + e.col], acc[k], g)) tgrd[t * ld + e.col] += g;
             }
         }
         __syncthreads();
@@ -139,12 +132,31 @@ __global__ void __launch_bounds__(256) l1_multi_kernel(const float* __restrict__
                 if (g != 0.f) dRaw[vb * n_out + i] += g;
             }
     }
+    l1_multi_block_sums(acc, tab.n, red, part);
+}
+
+// "rows" layout of the head outputs: raw / dRaw as [n_out] rows of nvox values (row pitch rs >= nvox) instead of
+// [nvox][n_out].  What the loss kernels walk is a handful of columns per entry; in rows every access of a wave is one
+// 256-byte segment, nothing goes through LDS and each kernel is one grid-stride loop with the SAME per-voxel expressions as
+// its channels-last twin (tests compare the two layouts bit for bit where the order allows).
+__global__ void __launch_bounds__(256) l1_multi_rows_kernel(const float* __restrict__ raw, int64_t rs, int64_t nvox,
+                                                            const L1Table tab, float* dRaw,
+                                                            double* __restrict__ part /*[nb][L1M_MAX]*/) {
+    __shared__ double red[256];
+    double acc[L1M_MAX];
 #pragma unroll
-    for (int k = 0; k < L1M_MAX; ++k) {
-        if (k >= tab.n) continue;                                  // wave-uniform
-        const double sk = block_sum(acc[k], red);
-        if (t == 0) part[(int64_t)blockIdx.x * L1M_MAX + k] = sk;
+    for (int k = 0; k < L1M_MAX; ++k) acc[k] = 0.0;
+    GRID_STRIDE(v, nvox) {
+#pragma unroll
+        for (int k = 0; k < L1M_MAX; ++k) {
+            if (k >= tab.n) continue;
+            const L1Entry& e = tab.e[k];
+            float g;
+            const bool live = l1_term(e, v, raw[(int64_t)e.col * rs + v], acc[k], g);
+            if (live && dRaw) dRaw[(int64_t)e.col * rs + v] += g;
+        }
     }
+    l1_multi_block_sums(acc, tab.n, red, part);
 }
 
 // one wave per quantity: lane l adds its strided partials in order, then a fixed xor tree (deterministic; one thread
@@ -159,69 +171,62 @@ __global__ void l1_multi_fold_kernel(const double* __restrict__ part, int nb, in
 }
 
 // ----------------------------------------------------------------------------- gradient L1 (GradientLoss 'l1')
-__global__ void __launch_bounds__(256) grad_l1_kernel(const float* __restrict__ raw, int n_out, int co,
-                                                      const float* __restrict__ target, const float* __restrict__ weight,
-                                                      int D, int H, int W, float coef, float* __restrict__ dRaw,
-                                                      double* __restrict__ part) {
-    __shared__ double red[256];
-    const int64_t nvox = (int64_t)D * H * W;
-    double acc = 0.0;
-    GRID_STRIDE(v, nvox) {
-        const int x = (int)(v % W);
-        const int64_t t2 = v / W;
-        const int y = (int)(t2 % H), z = (int)(t2 / H);
-        const float o = raw[v * n_out + co], t = target[v];
-        const float w = weight ? weight[v] : 1.f;
-        float g = 0.f;                                        // d(sum of the three terms)/d(o at v), own contributions
-        // forward differences along the fastest (x), middle (y) and slowest (z) axis; zero on the last slice
-        if (x + 1 < W) {
-            const float d = (raw[(v + 1) * n_out + co] - o) - (target[v + 1] - t);
-            acc += (double)(fabsf(d) * w);
-            g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-        }
-        if (y + 1 < H) {
-            const float d = (raw[(v + W) * n_out + co] - o) - (target[v + W] - t);
-            acc += (double)(fabsf(d) * w);
-            g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-        }
-        if (z + 1 < D) {
-            const int64_t s = (int64_t)H * W;
-            const float d = (raw[(v + s) * n_out + co] - o) - (target[v + s] - t);
-            acc += (double)(fabsf(d) * w);
-            g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-        }
-        // contributions of the differences anchored at the previous voxel along each axis (weight of THAT voxel)
-        if (x > 0) {
-            const float d = (o - raw[(v - 1) * n_out + co]) - (t - target[v - 1]);
-            g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - 1] : 1.f);
-        }
-        if (y > 0) {
-            const float d = (o - raw[(v - W) * n_out + co]) - (t - target[v - W]);
-            g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - W] : 1.f);
-        }
-        if (z > 0) {
-            const int64_t s = (int64_t)H * W;
-            const float d = (o - raw[(v - s) * n_out + co]) - (t - target[v - s]);
-            g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - s] : 1.f);
-        }
-        if (dRaw) dRaw[v * n_out + co] += coef * g;
-    }
-    acc = block_sum(acc, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// Every gradient-L1 entry of a sample in one launch (round 4): the seven rows of raw a voxel's stencil touches are fetched
-// once for all entries instead of once per entry and launch (8 launches x 218 us at 128^3: each read one 4-byte column
-// out of 276-byte rows).  Same expressions per entry as grad_l1_kernel.
+// Every gradient-L1 entry of a sample in one launch: the seven elements of raw a voxel's stencil touches are fetched once
+// for all entries instead of once per entry and launch.
 struct GL1Entry { int col; float coef; const float* target; const float* weight; };
 struct GL1Table { GL1Entry e[L1M_MAX]; int n; };
 
-__global__ void __launch_bounds__(256) grad_l1_multi_kernel(const float* __restrict__ raw, int n_out, const GL1Table tab, int D,
-                                                            int H, int W, float* __restrict__ dRaw,
+// The six-neighbour stencil of one entry at voxel v = (z, y, x): r points at the entry's element of raw at v, the next voxel
+// along x / y / z is sx / sy / sz elements of raw on (target and weight are [nvox]: 1, W, s = H * W).  a = the loss terms
+// anchored at v, g = d(sum of the three terms)/d(o at v).
+__device__ __forceinline__ void grad_l1_term(const float* r, int64_t sx, int64_t sy, int64_t sz, const float* target,
+                                             const float* weight, int64_t v, int x, int y, int z, int D, int H, int W,
+                                             int64_t s, double& a, float& g) {
+    const float o = r[0], t = target[v];
+    const float w = weight ? weight[v] : 1.f;
+    g = 0.f;
+    a = 0.0;
+    // forward differences along the fastest (x), middle (y) and slowest (z) axis; zero on the last slice
+    if (x + 1 < W) {
+        const float d = (r[sx] - o) - (target[v + 1] - t);
+        a += (double)(fabsf(d) * w);
+        g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
+    }
+    if (y + 1 < H) {
+        const float d = (r[sy] - o) - (target[v + W] - t);
+        a += (double)(fabsf(d) * w);
+        g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
+    }
+    if (z + 1 < D) {
+        const float d = (r[sz] - o) - (target[v + s] - t);
+        a += (double)(fabsf(d) * w);
+        g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
+    }
+    // contributions of the differences anchored at the previous voxel along each axis (weight of THAT voxel)
+    if (x > 0) {
+        const float d = (o - r[-sx]) - (t - target[v - 1]);
+        g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - 1] : 1.f);
+    }
+    if (y > 0) {
+        const float d = (o - r[-sy]) - (t - target[v - W]);
+        g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - W] : 1.f);
+    }
+    if (z > 0) {
+        const float d = (o - r[-sz]) - (t - target[v - s]);
+        g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - s] : 1.f);
+    }
+}
+
+// ROWS: element (column c, voxel v) of raw / dRaw at c * cs + v (the x stride is the compile-time 1); otherwise
+// channels-last, at v * vs + c with vs = n_out
+template <bool ROWS>
+__global__ void __launch_bounds__(256) grad_l1_multi_kernel(const float* __restrict__ raw, int64_t cs, int64_t vs,
+                                                            const GL1Table tab, int D, int H, int W, float* __restrict__ dRaw,
                                                             double* __restrict__ part /*[nb][L1M_MAX]*/) {
     __shared__ double red[256];
     const int64_t nvox = (int64_t)D * H * W;
     const int64_t s = (int64_t)H * W;
+    const int64_t sx = ROWS ? 1 : vs, sy = W * sx, sz = s * sx;
     double acc[L1M_MAX];
 #pragma unroll
     for (int k = 0; k < L1M_MAX; ++k) acc[k] = 0.0;
@@ -229,58 +234,90 @@ __global__ void __launch_bounds__(256) grad_l1_multi_kernel(const float* __restr
         const int x = (int)(v % W);
         const int64_t t2 = v / W;
         const int y = (int)(t2 % H), z = (int)(t2 / H);
-        const float* r0 = raw + v * n_out;
 #pragma unroll
         for (int k = 0; k < L1M_MAX; ++k) {
             if (k >= tab.n) continue;
             const GL1Entry& e = tab.e[k];
-            const float* target = e.target;
-            const float* weight = e.weight;
-            const int co = e.col;
-            const float o = r0[co], t = target[v];
-            const float w = weight ? weight[v] : 1.f;
-            float g = 0.f;
-            double a = 0.0;
-            if (x + 1 < W) {
-                const float d = (r0[n_out + co] - o) - (target[v + 1] - t);
-                a += (double)(fabsf(d) * w);
-                g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-            }
-            if (y + 1 < H) {
-                const float d = (r0[(int64_t)W * n_out + co] - o) - (target[v + W] - t);
-                a += (double)(fabsf(d) * w);
-                g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-            }
-            if (z + 1 < D) {
-                const float d = (r0[s * n_out + co] - o) - (target[v + s] - t);
-                a += (double)(fabsf(d) * w);
-                g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-            }
-            if (x > 0) {
-                const float d = (o - r0[-(int64_t)n_out + co]) - (t - target[v - 1]);
-                g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - 1] : 1.f);
-            }
-            if (y > 0) {
-                const float d = (o - r0[-(int64_t)W * n_out + co]) - (t - target[v - W]);
-                g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - W] : 1.f);
-            }
-            if (z > 0) {
-                const float d = (o - r0[-s * n_out + co]) - (t - target[v - s]);
-                g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - s] : 1.f);
-            }
+            const int64_t at = ROWS ? (int64_t)e.col * cs + v : v * vs + e.col;
+            float g;
+            double a;
+            grad_l1_term(raw + at, sx, sy, sz, e.target, e.weight, v, x, y, z, D, H, W, s, a, g);
             acc[k] += a;
-            if (dRaw) dRaw[v * n_out + co] += e.coef * g;
+            if (dRaw) dRaw[at] += e.coef * g;
         }
     }
+    l1_multi_block_sums(acc, tab.n, red, part);
+}
+// ----------------------------------------------------------------------------- segmentation: CE + Dice on softmax
+// Three kernel families share the per-voxel expressions below: the LDS-tiled channels-last kernels (ns <= 61: every label
+// set of the reference), the rows kernels (ns <= 64) and the untiled channels-last kernels (ns > 61).
+
+// A loop over the classes.  LIM > 0: unrolled over LIM classes with a c < ns guard, so that per-class values indexed by c
+// stay in registers (rows kernels); LIM == 0: ns rolled iterations.
+template <int LIM, class F>
+__device__ __forceinline__ void for_classes(int ns, F f) {
+    if constexpr (LIM > 0) {
 #pragma unroll
-    for (int k = 0; k < L1M_MAX; ++k) {
-        if (k >= tab.n) continue;                                  // wave-uniform
-        const double sk = block_sum(acc[k], red);
-        if (threadIdx.x == 0) part[(int64_t)blockIdx.x * L1M_MAX + k] = sk;
+        for (int c = 0; c < LIM; ++c)
+            if (c < ns) f(c);
+    } else {
+        for (int c = 0; c < ns; ++c) f(c);
     }
 }
 
-// ----------------------------------------------------------------------------- segmentation: CE + Dice on softmax
+// Softmax + CE of one voxel, in three steps the kernels run over their own copy of the ns logits (memory, LDS or a register
+// array): the largest logit m and inv = 1 / sum_c exp(logit_c - m); then per class the probability and the CE term the
+// kernel subtracts from its fp64 sum in class order.  (The per-class loop stays in the kernels: wrapped in a function
+// together with its store, it costs seg_fwd_rows_kernel<32> six registers and a wave.)
+template <int LIM>
+__device__ __forceinline__ void softmax_max_inv(int ns, const float* logit, float& m, float& inv) {
+    m = -INFINITY;
+    for_classes<LIM>(ns, [&](int c) { m = fmaxf(m, logit[c]); });
+    float sum = 0.f;
+    for_classes<LIM>(ns, [&](int c) { sum += expf(logit[c] - m); });
+    inv = 1.f / sum;
+}
+__device__ __forceinline__ float softmax_prob(float logit, float m, float inv) { return expf(logit - m) * inv; }
+__device__ __forceinline__ double ce_term(float p, float wc, float tc) { return (double)(logf(fmaxf(p, 1e-5f)) * wc * tc); }
+
+// per-class sums of a block: thread (j, c) = (t / ns, t % ns) brings its sums a = sum p*t and b = sum (p+t) over the voxel
+// lanes j, j + nj, ...; they are added over j in order and leave in the block's row of part ([1 + 2 ns], slots 1..)
+__device__ __forceinline__ void seg_class_sums_fold(double a, double b, int ns, int nj, double* s_pt, double* s_ps,
+                                                    double* part) {
+    const int t = threadIdx.x;
+    s_pt[t] = a;
+    s_ps[t] = b;
+    __syncthreads();
+    if (t < ns) {
+        double sa = 0.0, sb = 0.0;
+        for (int k = 0; k < nj; ++k) { sa += s_pt[k * ns + t]; sb += s_ps[k * ns + t]; }
+        part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + t] = sa;
+        part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + ns + t] = sb;
+    }
+}
+
+// class constants of the backward (tiled and rows kernels): with the folded sums num = sum p*t and den = sum (p+t) of a
+// class, d(coef_ce CE + coef_dice Dice)/dp = t * k1 + k0 - ka * t / p
+__device__ __forceinline__ void seg_class_constants(int ns, float coef_ce, float coef_dice, const float* wce,
+                                                    const float* wdice, const double* sums, float* ka, float* k1, float* k0) {
+    for (int c = threadIdx.x; c < ns; c += 256) {
+        ka[c] = coef_ce * wce[c];
+        const double num = sums[1 + c], den = sums[1 + ns + c];
+        const double k = (double)coef_dice * (double)wdice[c];
+        k1[c] = den > 1e-5 ? (float)(-2.0 * k / den) : 0.f;
+        k0[c] = den > 1e-5 ? (float)(2.0 * k * num / (den * den)) : 0.f;
+    }
+}
+
+// dL/dp of one class at one voxel, and the step through the softmax Jacobian given dot = sum_c dL/dp_c * p_c
+__device__ __forceinline__ float seg_dl_dp(float pc, float tc, float ka, float k1, float k0) {
+    float g = tc * k1 + k0;
+    if (pc > 1e-5f) g -= ka * tc / pc;                        // clamp(min=1e-5) kills the gradient below it
+    return g;
+}
+__device__ __forceinline__ float seg_dl_dlogit(float pc, float g, float dot) { return pc * (g - dot); }
+
+// ---- untiled channels-last, ns > 61: one voxel per thread straight from memory, with a stride of n_out floats per lane.
 // pass 1: probabilities P [nvox][ns] (written out) and per-block partials of CE      part: [nb][1 + 2*ns], slot 0
 __global__ void __launch_bounds__(256) seg_fwd_kernel(const float* __restrict__ raw, int n_out, int c0, int ns,
                                                       const float* __restrict__ target /*[ns][nvox] one-hot / soft (NCDHW)*/,
@@ -290,15 +327,12 @@ __global__ void __launch_bounds__(256) seg_fwd_kernel(const float* __restrict__ 
     double ce = 0.0;
     GRID_STRIDE(v, nvox) {
         const float* r = raw + v * n_out + c0;
-        float m = -INFINITY;
-        for (int c = 0; c < ns; ++c) m = fmaxf(m, r[c]);
-        float sum = 0.f;
-        for (int c = 0; c < ns; ++c) sum += expf(r[c] - m);
-        const float inv = 1.f / sum;
+        float m, inv;
+        softmax_max_inv<0>(ns, r, m, inv);
         for (int c = 0; c < ns; ++c) {
-            const float p = expf(r[c] - m) * inv;
+            const float p = softmax_prob(r[c], m, inv);
             P[v * ns + c] = p;
-            ce -= (double)(logf(fmaxf(p, 1e-5f)) * wce[c] * target[(int64_t)c * nvox + v]);
+            ce -= ce_term(p, wce[c], target[(int64_t)c * nvox + v]);
         }
     }
     ce = block_sum(ce, red);
@@ -320,15 +354,7 @@ __global__ void __launch_bounds__(256) seg_class_sums_kernel(const float* __rest
             a += (double)(p * tc);
             b += (double)(p + tc);
         }
-    s_pt[t] = a;
-    s_ps[t] = b;
-    __syncthreads();
-    if (t < ns) {
-        double sa = 0.0, sb = 0.0;
-        for (int k = 0; k < nj; ++k) { sa += s_pt[k * ns + t]; sb += s_ps[k * ns + t]; }
-        part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + t] = sa;
-        part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + ns + t] = sb;
-    }
+    seg_class_sums_fold(a, b, ns, nj, s_pt, s_ps, part);
 }
 
 // fold the per-block partials: out[0] = CE sum, out[1..ns] = sum p*t, out[1+ns..] = sum (p+t)
@@ -341,7 +367,10 @@ __global__ void seg_fold_kernel(const double* __restrict__ part, int nb, int ns,
     if (l == 0) out[k] = s_;
 }
 
-// pass 2: d(w_ce*CE_mean + w_dice*Dice)/d(logits) through the softmax, added into dRaw
+// pass 2: d(w_ce*CE_mean + w_dice*Dice)/d(logits) through the softmax, added into dRaw.  Kept apart from seg_dl_dp and the
+// class constants: this kernel forms the Dice term per voxel as (float)(-2 (t den - num) / den^2) in fp64, the tiled and
+// rows kernels as t * k1 + k0 from per-class fp32 constants.  The two round differently, and the results of this kernel for
+// ns > 61 are to stay the bits they are.
 __global__ void seg_bwd_kernel(const float* __restrict__ P, const float* __restrict__ target, int ns,
                                const float* __restrict__ wce, const float* __restrict__ wdice,
                                const double* __restrict__ sums, int64_t nvox, float coef_ce /* weight/(nvox) */,
@@ -370,12 +399,11 @@ __global__ void seg_bwd_kernel(const float* __restrict__ P, const float* __restr
     }
 }
 
-// LDS-tiled versions for ns <= 61 (every label set of the reference): a block stages the logits / probabilities of 256
-// voxels with coalesced row segments, each thread then works on its own voxel's row in LDS (odd stride: no bank
-// conflicts), and the results leave as coalesced rows again.  The per-thread versions above touch memory with a stride of
-// n_out (69) floats per lane: 5.4 + 7.3 ms at 128^3.
+// ---- LDS-tiled channels-last, ns <= 61: a block stages the logits / probabilities of 256 voxels with coalesced row
+// segments, each thread then works on its own voxel's row in LDS (odd stride: no bank conflicts), and the results leave as
+// coalesced rows again (the untiled kernels above: 5.4 + 7.3 ms at 128^3).
 // SUMS: the per-class sums of seg_class_sums_kernel ride along -- thread (j, c) adds p * t and p + t of the tile's voxels
-// j, j + nj, ... from the probabilities it has in LDS (round 4: the separate pass re-read P and the target, 0.95 ms at 128^3)
+// j, j + nj, ... from the probabilities it has in LDS (the separate pass re-read P and the target, 0.95 ms at 128^3)
 template <bool SUMS>
 __global__ void __launch_bounds__(256) seg_fwd_tile_kernel(const float* __restrict__ raw, int n_out, int c0, int ns,
                                                            const float* __restrict__ target, const float* __restrict__ wce,
@@ -400,15 +428,12 @@ __global__ void __launch_bounds__(256) seg_fwd_tile_kernel(const float* __restri
         __syncthreads();
         if (t < nv) {
             float* r = tile + t * ld;
-            float m = -INFINITY;
-            for (int c = 0; c < ns; ++c) m = fmaxf(m, r[c]);
-            float sum = 0.f;
-            for (int c = 0; c < ns; ++c) sum += expf(r[c] - m);
-            const float inv = 1.f / sum;
+            float m, inv;
+            softmax_max_inv<0>(ns, r, m, inv);
             for (int c = 0; c < ns; ++c) {
-                const float pr = expf(r[c] - m) * inv;
-                r[c] = pr;
-                ce -= (double)(logf(fmaxf(pr, 1e-5f)) * wce[c] * target[(int64_t)c * nvox + vb + t]);
+                const float p = softmax_prob(r[c], m, inv);
+                r[c] = p;
+                ce -= ce_term(p, wce[c], target[(int64_t)c * nvox + vb + t]);
             }
         }
         __syncthreads();
@@ -425,17 +450,7 @@ __global__ void __launch_bounds__(256) seg_fwd_tile_kernel(const float* __restri
     }
     ce = block_sum(ce, red);
     if (threadIdx.x == 0) part[(int64_t)blockIdx.x * (1 + 2 * ns)] = ce;
-    if (SUMS) {
-        s_pt[t] = sa;
-        s_ps[t] = sb;
-        __syncthreads();
-        if (t < ns) {
-            double a = 0.0, b = 0.0;
-            for (int k = 0; k < nj; ++k) { a += s_pt[k * ns + t]; b += s_ps[k * ns + t]; }
-            part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + t] = a;
-            part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + ns + t] = b;
-        }
-    }
+    if (SUMS) seg_class_sums_fold(sa, sb, ns, nj, s_pt, s_ps, part);
 }
 
 __global__ void __launch_bounds__(256) seg_bwd_tile_kernel(const float* __restrict__ P, const float* __restrict__ target, int ns,
@@ -445,16 +460,10 @@ __global__ void __launch_bounds__(256) seg_bwd_tile_kernel(const float* __restri
     extern __shared__ float tile[];                          // [256][ld] + 3 * ns class constants
     const int ld = ns | 1;
     const int t = threadIdx.x;
-    float* ka = tile + 256 * ld;                             // coef_ce * wce
-    float* k1 = ka + ns;                                     // dDice/dp = t * k1 + k0
+    float* ka = tile + 256 * ld;
+    float* k1 = ka + ns;
     float* k0 = k1 + ns;
-    for (int c = t; c < ns; c += 256) {
-        ka[c] = coef_ce * wce[c];
-        const double num = sums[1 + c], den = sums[1 + ns + c];
-        const double k = (double)coef_dice * (double)wdice[c];
-        k1[c] = den > 1e-5 ? (float)(-2.0 * k / den) : 0.f;
-        k0[c] = den > 1e-5 ? (float)(2.0 * k * num / (den * den)) : 0.f;
-    }
+    seg_class_constants(ns, coef_ce, coef_dice, wce, wdice, sums, ka, k1, k0);
     const int64_t ntile = bfm_cdiv64(nvox, 256);
     for (int64_t tb = blockIdx.x; tb < ntile; tb += gridDim.x) {
         const int64_t vb = tb * 256;
@@ -467,18 +476,12 @@ __global__ void __launch_bounds__(256) seg_bwd_tile_kernel(const float* __restri
         __syncthreads();
         if (t < nv) {
             float* r = tile + t * ld;
+            const float* tv = target + vb + t;
             float dot = 0.f;
+            for (int c = 0; c < ns; ++c) dot += seg_dl_dp(r[c], tv[(int64_t)c * nvox], ka[c], k1[c], k0[c]) * r[c];
             for (int c = 0; c < ns; ++c) {
-                const float pc = r[c], tc = target[(int64_t)c * nvox + vb + t];
-                float g = tc * k1[c] + k0[c];
-                if (pc > 1e-5f) g -= ka[c] * tc / pc;         // clamp(min=1e-5) kills the gradient below it
-                dot += g * pc;
-            }
-            for (int c = 0; c < ns; ++c) {
-                const float pc = r[c], tc = target[(int64_t)c * nvox + vb + t];
-                float g = tc * k1[c] + k0[c];
-                if (pc > 1e-5f) g -= ka[c] * tc / pc;
-                r[c] = pc * (g - dot);                        // softmax Jacobian
+                const float pc = r[c];
+                r[c] = seg_dl_dlogit(pc, seg_dl_dp(pc, tv[(int64_t)c * nvox], ka[c], k1[c], k0[c]), dot);
             }
         }
         __syncthreads();
@@ -489,6 +492,85 @@ __global__ void __launch_bounds__(256) seg_bwd_tile_kernel(const float* __restri
     }
 }
 
+// ---- rows: softmax + CE of one voxel per thread, the logits of its ns <= LIM classes in registers; P leaves as [ns][nvox]
+// rows
+template <int LIM>
+__global__ void __launch_bounds__(256) seg_fwd_rows_kernel(const float* __restrict__ raw, int64_t rs, int c0, int ns,
+                                                           const float* __restrict__ target, const float* __restrict__ wce,
+                                                           int64_t nvox_, float* __restrict__ P, double* __restrict__ part) {
+    __shared__ double red[256];
+    double ce = 0.0;
+    int64_t nvox = nvox_;
+    GRID_STRIDE(v, nvox_) {
+        asm volatile("" : "+s"(nvox));
+        // (opaque per iteration: hoisted out of the voxel loop, the LIM row addresses take 2 LIM scalar registers and spill)
+        asm volatile("" : "+s"(rs));
+        const float* r = raw + (int64_t)c0 * rs + v;
+        float sv[LIM];
+#pragma unroll
+        for (int c = 0; c < LIM; ++c) sv[c] = c < ns ? r[(int64_t)c * rs] : -INFINITY;
+        float m, inv;
+        softmax_max_inv<LIM>(ns, sv, m, inv);
+#pragma unroll
+        for (int c = 0; c < LIM; ++c) {
+            if (c < ns) {
+                const float p = softmax_prob(sv[c], m, inv);
+                P[(int64_t)c * nvox + v] = p;
+                ce -= ce_term(p, wce[c], target[(int64_t)c * nvox + v]);
+            }
+        }
+    }
+    ce = block_sum(ce, red);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.x * (1 + 2 * ns)] = ce;
+}
+
+// class sums of one (voxel chunk, class): both operands are rows
+__global__ void __launch_bounds__(256) seg_class_sums_rows_kernel(const float* __restrict__ P, const float* __restrict__ target,
+                                                                  int ns, int64_t nvox, int64_t vox_per_block,
+                                                                  double* __restrict__ part) {
+    __shared__ double red[256];
+    const int c = blockIdx.y;
+    const int64_t v0 = (int64_t)blockIdx.x * vox_per_block, v1 = min(nvox, v0 + vox_per_block);
+    const float* p = P + (int64_t)c * nvox;
+    const float* t = target + (int64_t)c * nvox;
+    double a = 0.0, b = 0.0;
+    for (int64_t v = v0 + threadIdx.x; v < v1; v += 256) {
+        const float pv = p[v], tc = t[v];
+        a += (double)(pv * tc);
+        b += (double)(pv + tc);
+    }
+    a = block_sum(a, red);
+    b = block_sum(b, red);
+    if (threadIdx.x == 0) {
+        part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + c] = a;
+        part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + ns + c] = b;
+    }
+}
+
+template <int LIM>
+__global__ void __launch_bounds__(256) seg_bwd_rows_kernel(const float* __restrict__ P, const float* __restrict__ target, int ns,
+                                                           const float* __restrict__ wce, const float* __restrict__ wdice,
+                                                           const double* __restrict__ sums, int64_t nvox_, float coef_ce,
+                                                           float coef_dice, int64_t rs, int c0, float* __restrict__ dRaw) {
+    __shared__ float ka[LIM], k1[LIM], k0[LIM];
+    seg_class_constants(ns, coef_ce, coef_dice, wce, wdice, sums, ka, k1, k0);
+    __syncthreads();
+    int64_t nvox = nvox_;
+    GRID_STRIDE(v, nvox_) {
+        asm volatile("" : "+s"(nvox), "+s"(rs));              // see seg_fwd_rows_kernel
+        float pv[LIM], gv[LIM];
+        float dot = 0.f;
+        for_classes<LIM>(ns, [&](int c) {
+            const float pc = P[(int64_t)c * nvox + v];
+            const float g = seg_dl_dp(pc, target[(int64_t)c * nvox + v], ka[c], k1[c], k0[c]);
+            dot += g * pc;
+            pv[c] = pc;
+            gv[c] = g;
+        });
+        float* d = dRaw + (int64_t)c0 * rs + v;
+        for_classes<LIM>(ns, [&](int c) { d[(int64_t)c * rs] += seg_dl_dlogit(pv[c], gv[c], dot); });
+    }
+}
 // ----------------------------------------------------------------------------- task heads backward
 // dFn[v][c] = sum_o dRaw[v][o] * W[o][c];   weights in LDS
 __global__ void __launch_bounds__(256) head_dfeat_kernel(const float* __restrict__ dRaw, const float* __restrict__ Wt,
@@ -734,206 +816,6 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(const bfm_adam_tensor_
     }
 }
 
-
-// ============================================================================ "rows" layout of the head outputs (round 4)
-// raw / dRaw as [n_out] rows of nvox values (row pitch rs >= nvox) instead of [nvox][n_out]: what the loss kernels walk is
-// a handful of columns per entry, which in the channels-last form costs one 4-byte element out of every 276-byte voxel row
-// (the LDS-tiled kernels above recover coalescing by staging whole rows, at 1.4-1.6 ms per pass at 128^3).  In rows every
-// access of a wave is one 256-byte segment, nothing goes through LDS and each kernel is one grid-stride loop with the SAME
-// per-voxel expressions as its channels-last twin (tests compare the two layouts bit for bit where the order allows).
-__global__ void __launch_bounds__(256) l1_multi_rows_kernel(const float* __restrict__ raw, int64_t rs, int64_t nvox,
-                                                            const L1Table tab, float* dRaw,
-                                                            double* __restrict__ part /*[nb][L1M_MAX]*/) {
-    __shared__ double red[256];
-    double acc[L1M_MAX];
-#pragma unroll
-    for (int k = 0; k < L1M_MAX; ++k) acc[k] = 0.0;
-    GRID_STRIDE(v, nvox) {
-#pragma unroll
-        for (int k = 0; k < L1M_MAX; ++k) {
-            if (k >= tab.n) continue;
-            const L1Entry& e = tab.e[k];
-            float o = raw[(int64_t)e.col * rs + v];
-            bool live = true;
-            if (e.clampv > 0.f) {
-                if (o > e.clampv) { o = e.clampv; live = false; }
-                else if (o < -e.clampv) { o = -e.clampv; live = false; }
-            }
-            const float m = e.mask ? e.mask[v] : 1.f;
-            const float w = e.weight ? e.weight[v] : 1.f;
-            const float d = o * m - e.target[v] * m;
-            acc[k] += (double)((e.l2 ? d * d : fabsf(d)) * w);
-            const float sg = e.l2 ? 2.f * d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
-            if (live && dRaw) dRaw[(int64_t)e.col * rs + v] += e.coef * sg * w * m;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < L1M_MAX; ++k) {
-        if (k >= tab.n) continue;
-        const double sk = block_sum(acc[k], red);
-        if (threadIdx.x == 0) part[(int64_t)blockIdx.x * L1M_MAX + k] = sk;
-    }
-}
-
-__global__ void __launch_bounds__(256) grad_l1_multi_rows_kernel(const float* __restrict__ raw, int64_t rs, const GL1Table tab,
-                                                                 int D, int H, int W, float* __restrict__ dRaw,
-                                                                 double* __restrict__ part /*[nb][L1M_MAX]*/) {
-    __shared__ double red[256];
-    const int64_t nvox = (int64_t)D * H * W;
-    const int64_t s = (int64_t)H * W;
-    double acc[L1M_MAX];
-#pragma unroll
-    for (int k = 0; k < L1M_MAX; ++k) acc[k] = 0.0;
-    GRID_STRIDE(v, nvox) {
-        const int x = (int)(v % W);
-        const int64_t t2 = v / W;
-        const int y = (int)(t2 % H), z = (int)(t2 / H);
-#pragma unroll
-        for (int k = 0; k < L1M_MAX; ++k) {
-            if (k >= tab.n) continue;
-            const GL1Entry& e = tab.e[k];
-            const float* target = e.target;
-            const float* weight = e.weight;
-            const float* r0 = raw + (int64_t)e.col * rs + v;
-            const float o = r0[0], t = target[v];
-            const float w = weight ? weight[v] : 1.f;
-            float g = 0.f;
-            double a = 0.0;
-            if (x + 1 < W) {
-                const float d = (r0[1] - o) - (target[v + 1] - t);
-                a += (double)(fabsf(d) * w);
-                g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-            }
-            if (y + 1 < H) {
-                const float d = (r0[W] - o) - (target[v + W] - t);
-                a += (double)(fabsf(d) * w);
-                g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-            }
-            if (z + 1 < D) {
-                const float d = (r0[s] - o) - (target[v + s] - t);
-                a += (double)(fabsf(d) * w);
-                g -= (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * w;
-            }
-            if (x > 0) {
-                const float d = (o - r0[-1]) - (t - target[v - 1]);
-                g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - 1] : 1.f);
-            }
-            if (y > 0) {
-                const float d = (o - r0[-W]) - (t - target[v - W]);
-                g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - W] : 1.f);
-            }
-            if (z > 0) {
-                const float d = (o - r0[-s]) - (t - target[v - s]);
-                g += (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * (weight ? weight[v - s] : 1.f);
-            }
-            acc[k] += a;
-            if (dRaw) dRaw[(int64_t)e.col * rs + v] += e.coef * g;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < L1M_MAX; ++k) {
-        if (k >= tab.n) continue;
-        const double sk = block_sum(acc[k], red);
-        if (threadIdx.x == 0) part[(int64_t)blockIdx.x * L1M_MAX + k] = sk;
-    }
-}
-
-// softmax + CE of one voxel per thread, the logits of its ns <= LIM classes in registers; P leaves as [ns][nvox] rows
-template <int LIM>
-__global__ void __launch_bounds__(256) seg_fwd_rows_kernel(const float* __restrict__ raw, int64_t rs, int c0, int ns,
-                                                           const float* __restrict__ target, const float* __restrict__ wce,
-                                                           int64_t nvox_, float* __restrict__ P, double* __restrict__ part) {
-    __shared__ double red[256];
-    double ce = 0.0;
-    int64_t nvox = nvox_;
-    GRID_STRIDE(v, nvox_) {
-        asm volatile("" : "+s"(nvox));
-        // (opaque per iteration: hoisted out of the voxel loop, the LIM row addresses take 2 LIM scalar registers and spill)
-        asm volatile("" : "+s"(rs));
-        const float* r = raw + (int64_t)c0 * rs + v;
-        float sv[LIM];
-#pragma unroll
-        for (int c = 0; c < LIM; ++c) sv[c] = c < ns ? r[(int64_t)c * rs] : -INFINITY;
-        float m = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < LIM; ++c) if (c < ns) m = fmaxf(m, sv[c]);
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < LIM; ++c) if (c < ns) sum += expf(sv[c] - m);
-        const float inv = 1.f / sum;
-#pragma unroll
-        for (int c = 0; c < LIM; ++c) {
-            if (c < ns) {
-                const float pr = expf(sv[c] - m) * inv;
-                P[(int64_t)c * nvox + v] = pr;
-                ce -= (double)(logf(fmaxf(pr, 1e-5f)) * wce[c] * target[(int64_t)c * nvox + v]);
-            }
-        }
-    }
-    ce = block_sum(ce, red);
-    if (threadIdx.x == 0) part[(int64_t)blockIdx.x * (1 + 2 * ns)] = ce;
-}
-
-// class sums of one (voxel chunk, class): both operands are rows
-__global__ void __launch_bounds__(256) seg_class_sums_rows_kernel(const float* __restrict__ P, const float* __restrict__ target,
-                                                                  int ns, int64_t nvox, int64_t vox_per_block,
-                                                                  double* __restrict__ part) {
-    __shared__ double red[256];
-    const int c = blockIdx.y;
-    const int64_t v0 = (int64_t)blockIdx.x * vox_per_block, v1 = min(nvox, v0 + vox_per_block);
-    const float* p = P + (int64_t)c * nvox;
-    const float* t = target + (int64_t)c * nvox;
-    double a = 0.0, b = 0.0;
-    for (int64_t v = v0 + threadIdx.x; v < v1; v += 256) {
-        const float pv = p[v], tc = t[v];
-        a += (double)(pv * tc);
-        b += (double)(pv + tc);
-    }
-    a = block_sum(a, red);
-    b = block_sum(b, red);
-    if (threadIdx.x == 0) {
-        part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + c] = a;
-        part[(int64_t)blockIdx.x * (1 + 2 * ns) + 1 + ns + c] = b;
-    }
-}
-
-template <int LIM>
-__global__ void __launch_bounds__(256) seg_bwd_rows_kernel(const float* __restrict__ P, const float* __restrict__ target, int ns,
-                                                           const float* __restrict__ wce, const float* __restrict__ wdice,
-                                                           const double* __restrict__ sums, int64_t nvox_, float coef_ce,
-                                                           float coef_dice, int64_t rs, int c0, float* __restrict__ dRaw) {
-    __shared__ float ka[LIM], k1[LIM], k0[LIM];
-    for (int c = threadIdx.x; c < ns; c += 256) {
-        ka[c] = coef_ce * wce[c];
-        const double num = sums[1 + c], den = sums[1 + ns + c];
-        const double k = (double)coef_dice * (double)wdice[c];
-        k1[c] = den > 1e-5 ? (float)(-2.0 * k / den) : 0.f;
-        k0[c] = den > 1e-5 ? (float)(2.0 * k * num / (den * den)) : 0.f;
-    }
-    __syncthreads();
-    int64_t nvox = nvox_;
-    GRID_STRIDE(v, nvox_) {
-        asm volatile("" : "+s"(nvox), "+s"(rs));              // see seg_fwd_rows_kernel
-        float pv[LIM], gv[LIM];
-        float dot = 0.f;
-#pragma unroll
-        for (int c = 0; c < LIM; ++c) {
-            if (c < ns) {
-                const float pc = P[(int64_t)c * nvox + v], tc = target[(int64_t)c * nvox + v];
-                float g = tc * k1[c] + k0[c];
-                if (pc > 1e-5f) g -= ka[c] * tc / pc;         // clamp(min=1e-5) kills the gradient below it
-                dot += g * pc;
-                pv[c] = pc;
-                gv[c] = g;
-            }
-        }
-        float* d = dRaw + (int64_t)c0 * rs + v;
-#pragma unroll
-        for (int c = 0; c < LIM; ++c)
-            if (c < ns) d[(int64_t)c * rs] += pv[c] * (gv[c] - dot);                     // softmax Jacobian
-    }
-}
-
 // ----------------------------------------------------------------------------- pathology head (round 6)
 // criterion.py:193-212 loss_pathol_ce / loss_pathol_dice on p = sigmoid(raw) (PatholProcessor, joiner.py:79-87), one channel:
 //   ce = mean_v( -log(max(p, 1e-5)) * t ),   dice = 1 - 2 sum(p t) / max(sum(p + t), 1e-5)
@@ -1003,28 +885,26 @@ __global__ void __launch_bounds__(256) pathol_bwd_kernel(const float* __restrict
 
 extern "C" size_t bfm_loss_workspace(int ns) { return (size_t)RB * (1 + 2 * (ns > 0 ? ns : 0)) * sizeof(double) + 4096; }
 
-extern "C" int bfm_loss_l1(const float* raw, int n_out, int co, const float* target, const float* weight,
-                           const float* mask_mul, int64_t nvox, float clampv, int l2, float coef, float* dRaw,
-                           double* loss_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
-    if (!raw || !target || !loss_out || !workspace || nvox <= 0 || co < 0 || co >= n_out) return BFM_E_ARG;
-    if (workspace_bytes < bfm_loss_workspace(0)) return BFM_E_WORKSPACE;
-    double* part = static_cast<double*>(workspace);
-    const int nb = grid_for(nvox, RB);
-    hipLaunchKernelGGL(l1_kernel, dim3(nb), dim3(256), 0, bfm_s(stream), raw, n_out, co, target, weight, mask_mul, nvox,
-                       clampv, l2, coef / (float)nvox, dRaw, part);
-    hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, bfm_s(stream), part, nb, 1.0 / (double)nvox, loss_out);
-    return bfm_launch_status();
+// Which layout the strides of raw / dRaw describe (element (column c, voxel v) at c * col_stride + v * voxel_stride): each
+// loss entry below takes the pair and picks its kernel
+enum class Layout { bad, rows, channels_last };
+static Layout layout_of(int64_t col_stride, int64_t voxel_stride, int n_out, int64_t nvox) {
+    if (voxel_stride == 1 && col_stride >= nvox) return Layout::rows;
+    if (col_stride == 1 && voxel_stride == n_out) return Layout::channels_last;
+    return Layout::bad;
 }
 
 extern "C" size_t bfm_loss_l1_multi_workspace(void) { return (size_t)RB * L1M_MAX * sizeof(double) + 256; }
 
-extern "C" int bfm_loss_l1_multi(const float* raw, int n_out, int64_t nvox, int n, const int32_t* cols, const int32_t* l2,
-                                 const float* clampv, const float* coef, const float* const* targets,
-                                 const float* const* weights, const float* const* masks, float* dRaw, double* loss_out,
-                                 void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+extern "C" int bfm_loss_l1_multi(const float* raw, int64_t col_stride, int64_t voxel_stride, int n_out, int64_t nvox, int n,
+                                 const int32_t* cols, const int32_t* l2, const float* clampv, const float* coef,
+                                 const float* const* targets, const float* const* weights, const float* const* masks,
+                                 float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
     if (!raw || nvox <= 0 || n_out <= 0 || n <= 0 || n > L1M_MAX || !cols || !l2 || !clampv || !coef || !targets ||
         !loss_out || !workspace)
         return BFM_E_ARG;
+    const Layout lay = layout_of(col_stride, voxel_stride, n_out, nvox);
+    if (lay == Layout::bad) return BFM_E_ARG;
     if (workspace_bytes < bfm_loss_l1_multi_workspace()) return BFM_E_WORKSPACE;
     L1Table tab{};
     tab.n = n;
@@ -1033,43 +913,37 @@ extern "C" int bfm_loss_l1_multi(const float* raw, int n_out, int64_t nvox, int 
         tab.e[k] = L1Entry{cols[k], l2[k], clampv[k], coef[k] / (float)nvox, targets[k], weights ? weights[k] : nullptr,
                            masks ? masks[k] : nullptr};
     }
-    const int ld = n_out | 1;
-    int tile_vox = (int)((60 * 1024) / (2 * sizeof(float) * ld));
-    if (tile_vox > 256) tile_vox = 256;
-    tile_vox &= ~31;
-    if (tile_vox < 32) return BFM_E_SHAPE;
     double* part = static_cast<double*>(workspace);
-    const int nb = (int)std::min<int64_t>(RB, bfm_cdiv64(nvox, tile_vox));
     hipStream_t st = bfm_s(stream);
-    hipLaunchKernelGGL(l1_multi_kernel, dim3(nb), dim3(256), (size_t)2 * tile_vox * ld * sizeof(float), st, raw, n_out, nvox,
-                       tile_vox, tab, dRaw, part);
+    int nb;
+    if (lay == Layout::rows) {
+        nb = grid_for(nvox, RB);
+        hipLaunchKernelGGL(l1_multi_rows_kernel, dim3(nb), dim3(256), 0, st, raw, col_stride, nvox, tab, dRaw, part);
+    } else {
+        const int ld = n_out | 1;
+        int tile_vox = (int)((60 * 1024) / (2 * sizeof(float) * ld));
+        if (tile_vox > 256) tile_vox = 256;
+        tile_vox &= ~31;
+        if (tile_vox < 32) return BFM_E_SHAPE;
+        nb = (int)std::min<int64_t>(RB, bfm_cdiv64(nvox, tile_vox));
+        hipLaunchKernelGGL(l1_multi_kernel, dim3(nb), dim3(256), (size_t)2 * tile_vox * ld * sizeof(float), st, raw, n_out, nvox,
+                           tile_vox, tab, dRaw, part);
+    }
     hipLaunchKernelGGL(l1_multi_fold_kernel, dim3(n), dim3(64), 0, st, part, nb, n, 1.0 / (double)nvox, loss_out);
     return bfm_launch_status();
 }
 
-extern "C" int bfm_loss_grad_l1(const float* raw, int n_out, int co, const float* target, const float* weight, int D,
-                                int H, int W, float coef, float* dRaw, double* loss_out, void* workspace,
-                                size_t workspace_bytes, bfm_stream_t stream) {
-    if (!raw || !target || !loss_out || !workspace || D <= 0 || H <= 0 || W <= 0 || co < 0 || co >= n_out)
+extern "C" int bfm_loss_grad_l1_multi(const float* raw, int64_t col_stride, int64_t voxel_stride, int n_out, int n,
+                                      const int32_t* cols, const float* coef, const float* const* targets,
+                                      const float* const* weights, int D, int H, int W, float* dRaw, double* loss_out,
+                                      void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+    if (!raw || !cols || !coef || !targets || !loss_out || !workspace || n <= 0 || n > L1M_MAX || D <= 0 || H <= 0 || W <= 0 ||
+        n_out <= 0)
         return BFM_E_ARG;
-    if (workspace_bytes < bfm_loss_workspace(0)) return BFM_E_WORKSPACE;
-    double* part = static_cast<double*>(workspace);
     const int64_t nvox = (int64_t)D * H * W;
-    const int nb = grid_for(nvox, RB);
-    hipLaunchKernelGGL(grad_l1_kernel, dim3(nb), dim3(256), 0, bfm_s(stream), raw, n_out, co, target, weight, D, H, W,
-                       coef / (float)nvox, dRaw, part);
-    hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, bfm_s(stream), part, nb, 1.0 / (double)nvox, loss_out);
-    return bfm_launch_status();
-}
-
-extern "C" int bfm_loss_grad_l1_multi(const float* raw, int n_out, int n, const int32_t* cols, const float* coef,
-                                      const float* const* targets, const float* const* weights, int D, int H, int W,
-                                      float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes,
-                                      bfm_stream_t stream) {
-    if (!raw || !cols || !coef || !targets || !loss_out || !workspace || n <= 0 || n > L1M_MAX || D <= 0 || H <= 0 || W <= 0)
-        return BFM_E_ARG;
+    const Layout lay = layout_of(col_stride, voxel_stride, n_out, nvox);
+    if (lay == Layout::bad) return BFM_E_ARG;
     if (workspace_bytes < bfm_loss_l1_multi_workspace()) return BFM_E_WORKSPACE;
-    const int64_t nvox = (int64_t)D * H * W;
     GL1Table tab{};
     tab.n = n;
     for (int k = 0; k < n; ++k) {
@@ -1080,43 +954,71 @@ extern "C" int bfm_loss_grad_l1_multi(const float* raw, int n_out, int n, const 
     }
     double* part = static_cast<double*>(workspace);
     const int nb = grid_for(nvox, RB);
-    hipLaunchKernelGGL(grad_l1_multi_kernel, dim3(nb), dim3(256), 0, bfm_s(stream), raw, n_out, tab, D, H, W, dRaw, part);
-    hipLaunchKernelGGL(l1_multi_fold_kernel, dim3(n), dim3(64), 0, bfm_s(stream), part, nb, n, 1.0 / (double)nvox, loss_out);
+    hipStream_t st = bfm_s(stream);
+    if (lay == Layout::rows)
+        hipLaunchKernelGGL(grad_l1_multi_kernel<true>, dim3(nb), dim3(256), 0, st, raw, col_stride, voxel_stride, tab, D, H, W,
+                           dRaw, part);
+    else
+        hipLaunchKernelGGL(grad_l1_multi_kernel<false>, dim3(nb), dim3(256), 0, st, raw, col_stride, voxel_stride, tab, D, H, W,
+                           dRaw, part);
+    hipLaunchKernelGGL(l1_multi_fold_kernel, dim3(n), dim3(64), 0, st, part, nb, n, 1.0 / (double)nvox, loss_out);
     return bfm_launch_status();
 }
 
-// loss_out[0] = CE (mean over voxels), loss_out[1] = Dice; P = softmax probabilities [nvox][ns] (scratch / output)
-extern "C" int bfm_loss_seg(const float* raw, int n_out, int c0, int ns, const float* target, const float* wce,
-                            const float* wdice, int64_t nvox, float coef_ce, float coef_dice, float* P, float* dRaw,
-                            double* loss_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+// loss_out[0] = CE (sum over voxels), loss_out[1..] = the class sums; P = softmax probabilities (scratch / output), in the
+// layout of raw: [nvox][ns] channels-last, [ns] rows of nvox in rows
+extern "C" int bfm_loss_seg(const float* raw, int64_t col_stride, int64_t voxel_stride, int n_out, int c0, int ns,
+                            const float* target, const float* wce, const float* wdice, int64_t nvox, float coef_ce,
+                            float coef_dice, float* P, float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes,
+                            bfm_stream_t stream) {
     if (!raw || !target || !wce || !wdice || !P || !loss_out || !workspace || nvox <= 0 || ns <= 0 || c0 < 0 ||
         c0 + ns > n_out)
         return BFM_E_ARG;
+    const Layout lay = layout_of(col_stride, voxel_stride, n_out, nvox);
+    if (lay == Layout::bad) return BFM_E_ARG;
+    if (lay == Layout::rows && ns > 64) return BFM_E_SHAPE;      // the logits of a voxel live in registers
     if (workspace_bytes < bfm_loss_workspace(ns)) return BFM_E_WORKSPACE;
     double* part = static_cast<double*>(workspace);
+    double* sums = part + (size_t)RB * (1 + 2 * ns);             // [1 + 2 ns]
     const int nb = grid_for(nvox, RB);
     hipStream_t st = bfm_s(stream);
     const int64_t vpb = bfm_cdiv64(nvox, nb);
-    if (ns > 256 || bfm_cdiv64(nvox, vpb) > nb) return BFM_E_SHAPE;
-    const bool tiled = ns <= 61;                                 // 256 rows of (ns | 1) floats + constants within 64 KB
-    const size_t tile_bytes = (size_t)(256 * (ns | 1) + 3 * ns) * sizeof(float);
-    if (tiled) {
-        hipLaunchKernelGGL(seg_fwd_tile_kernel<true>, dim3(nb), dim3(256), tile_bytes, st, raw, n_out, c0, ns, target, wce, nvox, P,
-                           part);
-    } else {
-        hipLaunchKernelGGL(seg_fwd_kernel, dim3(nb), dim3(256), 0, st, raw, n_out, c0, ns, target, wce, nvox, P, part);
-        // blocks past the last voxel chunk still write zeros: the fold below reads all nb rows
-        hipLaunchKernelGGL(seg_class_sums_kernel, dim3(nb), dim3(256), 0, st, P, target, ns, nvox, vpb, part);
-    }
-    double* sums = part + (size_t)RB * (1 + 2 * ns);             // [1 + 2 ns]
-    hipLaunchKernelGGL(seg_fold_kernel, dim3(1 + 2 * ns), dim3(64), 0, st, part, nb, ns, sums);
-    if (dRaw) {
-        if (tiled)
-            hipLaunchKernelGGL(seg_bwd_tile_kernel, dim3(grid_for(nvox, 2048)), dim3(256), tile_bytes, st, P, target, ns, wce, wdice, sums,
-                               nvox, coef_ce / (float)nvox, coef_dice, n_out, c0, dRaw);
+    const float cce = coef_ce / (float)nvox;
+    auto fold = [&] { hipLaunchKernelGGL(seg_fold_kernel, dim3(1 + 2 * ns), dim3(64), 0, st, part, nb, ns, sums); };
+    if (lay == Layout::rows) {
+        const int64_t rs = col_stride;
+        if (ns <= 32)
+            hipLaunchKernelGGL(seg_fwd_rows_kernel<32>, dim3(nb), dim3(256), 0, st, raw, rs, c0, ns, target, wce, nvox, P, part);
         else
-            hipLaunchKernelGGL(seg_bwd_kernel, dim3(grid_for(nvox)), dim3(256), 0, st, P, target, ns, wce, wdice, sums, nvox,
-                               coef_ce / (float)nvox, coef_dice, n_out, c0, dRaw);
+            hipLaunchKernelGGL(seg_fwd_rows_kernel<64>, dim3(nb), dim3(256), 0, st, raw, rs, c0, ns, target, wce, nvox, P, part);
+        // blocks past the last voxel chunk still write zeros: the fold reads all nb rows
+        hipLaunchKernelGGL(seg_class_sums_rows_kernel, dim3(nb, ns), dim3(256), 0, st, P, target, ns, nvox, vpb, part);
+        fold();
+        if (dRaw && ns <= 32)
+            hipLaunchKernelGGL(seg_bwd_rows_kernel<32>, dim3(grid_for(nvox, 2048)), dim3(256), 0, st, P, target, ns, wce, wdice,
+                               sums, nvox, cce, coef_dice, rs, c0, dRaw);
+        else if (dRaw)
+            hipLaunchKernelGGL(seg_bwd_rows_kernel<64>, dim3(grid_for(nvox, 2048)), dim3(256), 0, st, P, target, ns, wce, wdice,
+                               sums, nvox, cce, coef_dice, rs, c0, dRaw);
+    } else {
+        if (ns > 256 || bfm_cdiv64(nvox, vpb) > nb) return BFM_E_SHAPE;
+        const bool tiled = ns <= 61;                             // 256 rows of (ns | 1) floats + constants within 64 KB
+        const size_t tile_bytes = (size_t)(256 * (ns | 1) + 3 * ns) * sizeof(float);
+        if (tiled) {
+            hipLaunchKernelGGL(seg_fwd_tile_kernel<true>, dim3(nb), dim3(256), tile_bytes, st, raw, n_out, c0, ns, target, wce, nvox,
+                               P, part);
+        } else {
+            hipLaunchKernelGGL(seg_fwd_kernel, dim3(nb), dim3(256), 0, st, raw, n_out, c0, ns, target, wce, nvox, P, part);
+            // blocks past the last voxel chunk still write zeros: the fold reads all nb rows
+            hipLaunchKernelGGL(seg_class_sums_kernel, dim3(nb), dim3(256), 0, st, P, target, ns, nvox, vpb, part);
+        }
+        fold();
+        if (dRaw && tiled)
+            hipLaunchKernelGGL(seg_bwd_tile_kernel, dim3(grid_for(nvox, 2048)), dim3(256), tile_bytes, st, P, target, ns, wce, wdice,
+                               sums, nvox, cce, coef_dice, n_out, c0, dRaw);
+        else if (dRaw)
+            hipLaunchKernelGGL(seg_bwd_kernel, dim3(grid_for(nvox)), dim3(256), 0, st, P, target, ns, wce, wdice, sums, nvox, cce,
+                               coef_dice, n_out, c0, dRaw);
     }
     // loss values are finished on the host from `sums` (CE mean and the Dice sum need wdice): copy them out
     (void)hipMemcpyAsync(loss_out, sums, (size_t)(1 + 2 * ns) * sizeof(double), hipMemcpyDeviceToDevice, st);
@@ -1307,91 +1209,6 @@ extern "C" int bfm_head_bwd_rows(const float* dRaw_rows, int64_t row_stride, con
                                  size_t workspace_bytes, bfm_stream_t stream) {
     if (row_stride < nvox) return BFM_E_ARG;
     return head_bwd_launch(dRaw_rows, row_stride, Fn, head_w, n_out, C, nvox, dW, db, dFn, workspace, workspace_bytes, stream);
-}
-
-// ---- rows layout of the head outputs: same arguments as the channels-last entries with (raw, n_out) -> (rows, pitch)
-extern "C" int bfm_loss_l1_multi_rows(const float* raw_rows, int64_t row_stride, int n_out, int64_t nvox, int n,
-                                      const int32_t* cols, const int32_t* l2, const float* clampv, const float* coef,
-                                      const float* const* targets, const float* const* weights, const float* const* masks,
-                                      float* dRaw_rows, double* loss_out, void* workspace, size_t workspace_bytes,
-                                      bfm_stream_t stream) {
-    if (!raw_rows || nvox <= 0 || row_stride < nvox || n_out <= 0 || n <= 0 || n > L1M_MAX || !cols || !l2 || !clampv ||
-        !coef || !targets || !loss_out || !workspace)
-        return BFM_E_ARG;
-    if (workspace_bytes < bfm_loss_l1_multi_workspace()) return BFM_E_WORKSPACE;
-    L1Table tab{};
-    tab.n = n;
-    for (int k = 0; k < n; ++k) {
-        if (cols[k] < 0 || cols[k] >= n_out || !targets[k]) return BFM_E_ARG;
-        tab.e[k] = L1Entry{cols[k], l2[k], clampv[k], coef[k] / (float)nvox, targets[k], weights ? weights[k] : nullptr,
-                           masks ? masks[k] : nullptr};
-    }
-    double* part = static_cast<double*>(workspace);
-    const int nb = grid_for(nvox, RB);
-    hipStream_t st = bfm_s(stream);
-    hipLaunchKernelGGL(l1_multi_rows_kernel, dim3(nb), dim3(256), 0, st, raw_rows, row_stride, nvox, tab, dRaw_rows, part);
-    hipLaunchKernelGGL(l1_multi_fold_kernel, dim3(n), dim3(64), 0, st, part, nb, n, 1.0 / (double)nvox, loss_out);
-    return bfm_launch_status();
-}
-
-extern "C" int bfm_loss_grad_l1_multi_rows(const float* raw_rows, int64_t row_stride, int n_out, int n, const int32_t* cols,
-                                           const float* coef, const float* const* targets, const float* const* weights,
-                                           int D, int H, int W, float* dRaw_rows, double* loss_out, void* workspace,
-                                           size_t workspace_bytes, bfm_stream_t stream) {
-    if (!raw_rows || !cols || !coef || !targets || !loss_out || !workspace || n <= 0 || n > L1M_MAX || D <= 0 || H <= 0 ||
-        W <= 0 || n_out <= 0)
-        return BFM_E_ARG;
-    if (workspace_bytes < bfm_loss_l1_multi_workspace()) return BFM_E_WORKSPACE;
-    const int64_t nvox = (int64_t)D * H * W;
-    if (row_stride < nvox) return BFM_E_ARG;
-    GL1Table tab{};
-    tab.n = n;
-    for (int k = 0; k < n; ++k) {
-        if (cols[k] < 0 || cols[k] >= n_out || !targets[k]) return BFM_E_ARG;
-        for (int j = 0; j < k; ++j)
-            if (cols[j] == cols[k]) return BFM_E_ARG;               // two entries on one column would race on dRaw
-        tab.e[k] = GL1Entry{cols[k], coef[k] / (float)nvox, targets[k], weights ? weights[k] : nullptr};
-    }
-    double* part = static_cast<double*>(workspace);
-    const int nb = grid_for(nvox, RB);
-    hipLaunchKernelGGL(grad_l1_multi_rows_kernel, dim3(nb), dim3(256), 0, bfm_s(stream), raw_rows, row_stride, tab, D, H, W,
-                       dRaw_rows, part);
-    hipLaunchKernelGGL(l1_multi_fold_kernel, dim3(n), dim3(64), 0, bfm_s(stream), part, nb, n, 1.0 / (double)nvox, loss_out);
-    return bfm_launch_status();
-}
-
-// P = softmax probabilities as [ns] rows of nvox (scratch / output); ns <= 64
-extern "C" int bfm_loss_seg_rows(const float* raw_rows, int64_t row_stride, int n_out, int c0, int ns, const float* target,
-                                 const float* wce, const float* wdice, int64_t nvox, float coef_ce, float coef_dice,
-                                 float* P, float* dRaw_rows, double* loss_out, void* workspace, size_t workspace_bytes,
-                                 bfm_stream_t stream) {
-    if (!raw_rows || !target || !wce || !wdice || !P || !loss_out || !workspace || nvox <= 0 || row_stride < nvox ||
-        ns <= 0 || c0 < 0 || c0 + ns > n_out)
-        return BFM_E_ARG;
-    if (ns > 64) return BFM_E_SHAPE;
-    if (workspace_bytes < bfm_loss_workspace(ns)) return BFM_E_WORKSPACE;
-    double* part = static_cast<double*>(workspace);
-    const int nb = grid_for(nvox, RB);
-    hipStream_t st = bfm_s(stream);
-    const int64_t vpb = bfm_cdiv64(nvox, nb);
-    if (ns <= 32)
-        hipLaunchKernelGGL(seg_fwd_rows_kernel<32>, dim3(nb), dim3(256), 0, st, raw_rows, row_stride, c0, ns, target, wce, nvox, P, part);
-    else
-        hipLaunchKernelGGL(seg_fwd_rows_kernel<64>, dim3(nb), dim3(256), 0, st, raw_rows, row_stride, c0, ns, target, wce, nvox, P, part);
-    // blocks past the last voxel chunk still write zeros: the fold below reads all nb rows
-    hipLaunchKernelGGL(seg_class_sums_rows_kernel, dim3(nb, ns), dim3(256), 0, st, P, target, ns, nvox, vpb, part);
-    double* sums = part + (size_t)RB * (1 + 2 * ns);             // [1 + 2 ns]
-    hipLaunchKernelGGL(seg_fold_kernel, dim3(1 + 2 * ns), dim3(64), 0, st, part, nb, ns, sums);
-    if (dRaw_rows) {
-        if (ns <= 32)
-            hipLaunchKernelGGL(seg_bwd_rows_kernel<32>, dim3(grid_for(nvox, 2048)), dim3(256), 0, st, P, target, ns, wce, wdice, sums,
-                               nvox, coef_ce / (float)nvox, coef_dice, row_stride, c0, dRaw_rows);
-        else
-            hipLaunchKernelGGL(seg_bwd_rows_kernel<64>, dim3(grid_for(nvox, 2048)), dim3(256), 0, st, P, target, ns, wce, wdice, sums,
-                               nvox, coef_ce / (float)nvox, coef_dice, row_stride, c0, dRaw_rows);
-    }
-    (void)hipMemcpyAsync(loss_out, sums, (size_t)(1 + 2 * ns) * sizeof(double), hipMemcpyDeviceToDevice, st);
-    return bfm_launch_status();
 }
 
 extern "C" int bfm_normalize_bwd(const float* feat, const float* dFn, int C, int64_t nvox, float eps, float* dfeat,

@@ -4,7 +4,7 @@ Mirrors the reference's iteration -- Trainer/engine.py:96-147:
 
     outputs, _ = model(samples)                       -> backward.backbone_forward_train + Tail.run_raw   (per sample)
     outputs = processor(outputs, ...)                 -> softmax / clamp folded into the loss kernels
-    loss_dict = criterion(outputs, target, samples)   -> bfm_loss_l1 / bfm_loss_grad_l1 / bfm_loss_seg
+    loss_dict = criterion(outputs, target, samples)   -> bfm_loss_l1_multi / bfm_loss_grad_l1_multi / bfm_loss_seg / ...
     losses = sum(loss_dict[k] * weight_dict[k])
     scaler.scale(losses).backward()                   -> bfm_head_bwd, bfm_normalize_bwd, backward.backbone_backward
     scaler.unscale_(optimizer); clip_gradients(...)   -> bfm_grad_sumsq (+ non-finite flag), per-parameter coefficient
@@ -25,6 +25,7 @@ import ctypes as C
 import math
 import os
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -513,6 +514,37 @@ class TrainStep:
             raise L.BfmError("target of shape %s does not match the volume %s" % (tuple(x.shape), tuple(shape_tail)))
         return x
 
+    def _coef(self, name, scale):
+        """What multiplies d loss_<name> / d raw: loss scale * weight / all_samples (0 without a weight)."""
+        return scale * self.loss_weights.get("loss_" + name, 0.0) / self.all_samples
+
+    def _issue_entries(self, entries, launch, what, vals, keep, distinct_cols=False):
+        """Issue per-column loss entries (slot, col, target, weight, mask, clamp, l2, coef) in groups of at most 32, in order.
+        launch(n, a, stage) calls the export on the group's ctypes arrays a.cols / l2 / clamp / coef / tg / wt / mk and the
+        device pointer of an fp64 staging row, whose n values then go to the entries' slots of `vals`.
+        distinct_cols: an entry whose column is already in the group waits for the next launch."""
+        pending = list(entries)
+        while pending:
+            batch, rest, seen = [], [], set()
+            for e in pending:
+                if len(batch) == 32 or (distinct_cols and e[1] in seen):
+                    rest.append(e)
+                else:
+                    seen.add(e[1])
+                    batch.append(e)
+            pending = rest
+            n = len(batch)
+            ptrs = lambda j: (C.c_void_p * n)(*[(e[j].data_ptr() if e[j] is not None else None) for e in batch])  # noqa: E731
+            a = SimpleNamespace(
+                cols=(C.c_int32 * n)(*[e[1] for e in batch]), tg=ptrs(2), wt=ptrs(3), mk=ptrs(4),
+                clamp=(C.c_float * n)(*[e[5] for e in batch]), l2=(C.c_int32 * n)(*[e[6] for e in batch]),
+                coef=(C.c_float * n)(*[e[7] for e in batch]))
+            keep.extend(e[j] for j in (2, 3, 4) for e in batch)
+            stage = torch.empty(n, dtype=torch.float64, device=self.dev)
+            L.check(launch(n, a, L.ptr(stage)), what)
+            idx = torch.tensor([e[0] for e in batch], dtype=torch.int64, device=self.dev)
+            vals.index_copy_(0, idx, stage)
+
     def _sample_losses(self, raw, dims, target, sample, dRaw, vals, scale, rows=False):
         """Launch every loss of one sample; values land in `vals` (device fp64, one slot list per loss name).
         rows: raw / dRaw are (n_out, nvox) rows instead of channels-last (nvox, n_out)."""
@@ -520,11 +552,15 @@ class TrainStep:
         D, H, W = dims
         nvox = D * H * W
         n_out = self.tail.n_out
+        # element (column c, voxel v) of raw and dRaw at c * cs + v * vs: all a loss entry needs to know of the layout
+        cs, vs = (raw.stride(0), 1) if rows else (1, n_out)
+        pr, pd = L.ptr(raw), L.ptr(dRaw)
         ws, wsn = L.ptr(self._ws), self._ws.numel()
+        wsm, wsmn = L.ptr(self._ws_multi), self._ws_multi.numel()
         slots = {}
         k = 0
-        dense = []                                        # (slot index, col, target, weight, mask, clamp, l2, coef): one launch
-        grads_l1 = []                                     # (slot index, col, target, weight, coef): the gradient-L1 entries, one launch
+        dense = []                                        # l1 / l2 entries (slot, col, target, weight, mask, clamp, l2, coef)
+        grads_l1 = []                                     # gradient-L1 entries, the same tuple (no mask, clamp or l2)
         keep = []                                         # tensors the deferred launch reads
         active = set()                                    # head rows some loss of this sample differentiates
         pathol_done = False
@@ -535,21 +571,15 @@ class TrainStep:
             k += n
             return C.c_void_p(vals.data_ptr() + 8 * (k - n))
 
-        def seg_loss(r0, ns, tgt, c_ce, c_dice):
-            P = torch.empty(nvox * ns, dtype=torch.float32, device=self.dev)     # [nvox][ns], rows: [ns][nvox]
-            if rows:
-                L.check(lib.bfm_loss_seg_rows(L.ptr(raw), nvox, n_out, r0, ns, L.ptr(tgt), L.ptr(self.wce), L.ptr(self.wce),
-                                              nvox, c_ce, c_dice, L.ptr(P), L.ptr(dRaw), slot("seg", 1 + 2 * ns), ws, wsn, st),
-                        "loss_seg_rows")
-            else:
-                L.check(lib.bfm_loss_seg(L.ptr(raw), n_out, r0, ns, L.ptr(tgt), L.ptr(self.wce), L.ptr(self.wce), nvox,
-                                         c_ce, c_dice, L.ptr(P), L.ptr(dRaw), slot("seg", 1 + 2 * ns), ws, wsn, st), "loss_seg")
+        def entry(name, co, tgt, wt=None, mask=None, clampv=0.0, l2=0, coef=0.0):
+            slot(name)
+            active.add(co)
+            (grads_l1 if name.endswith("_grad") else dense).append((k - 1, co, tgt, wt, mask, clampv, l2, coef))
 
         for name in self.loss_names:
-            coef = scale * self.loss_weights.get("loss_" + name, 0.0) / self.all_samples
+            coef = self._coef(name, scale)
             if name in IMAGE_KEYS or (name.endswith("_grad") and name[:-5] in IMAGE_KEYS) or name in ("SR", "SR_grad"):
-                is_grad = name.endswith("_grad")
-                key = name[:-5] if is_grad else name
+                key = name[:-5] if name.endswith("_grad") else name
                 if key == "SR":
                     head, tgt, wt = "high_res_residual", sample.get("high_res_residual"), None
                 else:
@@ -557,15 +587,7 @@ class TrainStep:
                     wt = (1.0 - self._t(target[key + "_DM"], dims)) if (key + "_DM") in target else None
                 if tgt is None or head not in self.tail.row_of:
                     continue                                          # criterion.py:274-281: shape mismatch -> 0
-                tgt = self._t(tgt, dims)
-                co = self._col(head)
-                active.add(co)
-                if is_grad:
-                    slot(name)
-                    grads_l1.append((k - 1, co, tgt, wt, coef))
-                else:
-                    slot(name)
-                    dense.append((k - 1, co, tgt, wt, None, 0.0, 0, coef))
+                entry(name, self._col(head), self._t(tgt, dims), wt, coef=coef)
             elif name in ("distance", "surface", "registration", "registration_grad"):
                 # criterion.py:175-185: loss_image / loss_image_grad of the whole multi-channel map (surface: 8 channels,
                 # Trainer/models/__init__.py:103-106; its head has no processor, so no clamp)
@@ -577,25 +599,17 @@ class TrainStep:
                 if tgt.shape[0] != nch:
                     continue
                 for j in range(nch):
-                    co = self._col(head, j)
-                    active.add(co)
-                    if name == "registration_grad":
-                        slot(name)
-                        grads_l1.append((k - 1, co, tgt[j], None, coef / nch))
-                    else:
-                        clampv = self.max_dist if head == "distance" else 0.0
-                        slot(name)
-                        dense.append((k - 1, co, tgt[j], None, None, clampv, 0, coef / nch))
+                    entry(name, self._col(head, j), tgt[j], clampv=self.max_dist if name == "distance" else 0.0,
+                          coef=coef / nch)
             elif name in REG_REGULARISERS:
                 # criterion.py:187-191: SmoothnessLoss('l2') / HessianLoss('l2') of the raw registration output (no processor,
                 # no target); value and coef * d/d(raw) in one launch pair, added into the registration rows of dRaw
                 r0, nch = self.tail.row_of["registration"]
                 active.update(range(r0, r0 + nch))
-                off, cs, vs = (r0 * raw.stride(0), raw.stride(0), 1) if rows else (r0, 1, n_out)
                 wsr = torch.empty(lib.bfm_loss_reg_workspace(nch, D, H, W), dtype=torch.uint8, device=self.dev)
                 keep.append(wsr)
                 fn = lib.bfm_loss_reg_smooth if name == "registration_smooth" else lib.bfm_loss_reg_hessian
-                L.check(fn(L.ptr(raw), off, cs, vs, nch, D, H, W, coef, L.ptr(dRaw), slot(name), L.ptr(wsr), wsr.numel(), st),
+                L.check(fn(pr, r0 * cs, cs, vs, nch, D, H, W, coef, pd, slot(name), L.ptr(wsr), wsr.numel(), st),
                         "loss_" + name)
             elif name in ("pathol_ce", "pathol_dice"):
                 # criterion.py:193-212 on sigmoid(raw) (PatholProcessor): both names of a sample in ONE bfm_loss_pathol call,
@@ -610,87 +624,38 @@ class TrainStep:
                     continue
                 co = self._col("pathology")
                 active.add(co)
-                cf = {n_: scale * self.loss_weights.get("loss_" + n_, 0.0) / self.all_samples
-                      for n_ in ("pathol_ce", "pathol_dice") if n_ in self.loss_names}
-                p_ce = slot("pathol_ce") if "pathol_ce" in cf else None
-                p_di = slot("pathol_dice") if "pathol_dice" in cf else None
+                on = [n_ for n_ in ("pathol_ce", "pathol_dice") if n_ in self.loss_names]
+                p_ce, p_di = (slot(n_) if n_ in on else None for n_ in ("pathol_ce", "pathol_dice"))
+                c_ce, c_di = (self._coef(n_, scale) if n_ in on else 0.0 for n_ in ("pathol_ce", "pathol_dice"))
                 wsp = torch.empty(lib.bfm_loss_pathol_workspace(), dtype=torch.uint8, device=self.dev)
                 keep.extend([tgt, wsp])
-                L.check(lib.bfm_loss_pathol(L.ptr(raw), co * raw.stride(0) if rows else co, 1 if rows else n_out, L.ptr(tgt),
-                                            nvox, cf.get("pathol_ce", 0.0), cf.get("pathol_dice", 0.0), L.ptr(dRaw), p_ce, p_di,
-                                            L.ptr(wsp), wsp.numel(), st), "loss_pathol")
+                L.check(lib.bfm_loss_pathol(pr, co * cs, vs, L.ptr(tgt), nvox, c_ce, c_di, pd, p_ce, p_di, L.ptr(wsp),
+                                            wsp.numel(), st), "loss_pathol")
             elif name == "bias_field_log":
                 if "bias_field_log" not in sample or "bias_field_log" not in self.tail.row_of:
                     continue
                 mask = 1.0 - self._t(target["segmentation"], dims).reshape(-1, D, H, W)[0]
-                tgt = self._t(sample["bias_field_log"], dims)
-                slot(name)
-                active.add(self._col("bias_field_log"))
-                dense.append((k - 1, self._col("bias_field_log"), tgt, None, mask, 0.0, self.bias_l2, coef))
-            elif name == "seg_ce":
-                # CE and Dice share the softmax: one launch covers both names
+                entry(name, self._col("bias_field_log"), self._t(sample["bias_field_log"], dims), mask=mask, l2=self.bias_l2,
+                      coef=coef)
+            elif name in ("seg_ce", "seg_dice"):
+                # CE and Dice share the softmax: one launch covers both names, at seg_ce's place in the order where it is on
+                if name == "seg_dice" and "seg_ce" in self.loss_names:
+                    continue
                 r0, ns = self.tail.row_of["segmentation"]
                 active.update(range(r0, r0 + ns))
                 tgt = self._t(target["segmentation"], dims).reshape(ns, D, H, W)
-                c_dice = (scale * self.loss_weights.get("loss_seg_dice", 0.0) / self.all_samples
-                          if "seg_dice" in self.loss_names else 0.0)
-                seg_loss(r0, ns, tgt, coef, c_dice)
-            elif name == "seg_dice":
-                if "seg_ce" not in self.loss_names:
-                    r0, ns = self.tail.row_of["segmentation"]
-                    active.update(range(r0, r0 + ns))
-                    tgt = self._t(target["segmentation"], dims).reshape(ns, D, H, W)
-                    seg_loss(r0, ns, tgt, 0.0, coef)
-        # every l1 / l2 entry in batches of 32 per launch (one pass over raw each); results go to a staging row and from
-        # there to their slots
-        for b0 in range(0, len(dense), 32):
-            batch = dense[b0:b0 + 32]
-            n = len(batch)
-            cols = (C.c_int32 * n)(*[e[1] for e in batch])
-            l2s = (C.c_int32 * n)(*[e[6] for e in batch])
-            clamps = (C.c_float * n)(*[e[5] for e in batch])
-            coefs = (C.c_float * n)(*[e[7] for e in batch])
-            tg = (C.c_void_p * n)(*[e[2].data_ptr() for e in batch])
-            wt = (C.c_void_p * n)(*[(e[3].data_ptr() if e[3] is not None else None) for e in batch])
-            mk = (C.c_void_p * n)(*[(e[4].data_ptr() if e[4] is not None else None) for e in batch])
-            keep.extend([e[2] for e in batch] + [e[3] for e in batch] + [e[4] for e in batch])
-            stage = torch.empty(n, dtype=torch.float64, device=self.dev)
-            wsm = self._ws_multi
-            if rows:
-                L.check(lib.bfm_loss_l1_multi_rows(L.ptr(raw), nvox, n_out, nvox, n, cols, l2s, clamps, coefs, tg, wt, mk,
-                                                   L.ptr(dRaw), L.ptr(stage), L.ptr(wsm), wsm.numel(), st), "loss_l1_multi_rows")
-            else:
-                L.check(lib.bfm_loss_l1_multi(L.ptr(raw), n_out, nvox, n, cols, l2s, clamps, coefs, tg, wt, mk, L.ptr(dRaw),
-                                              L.ptr(stage), L.ptr(wsm), wsm.numel(), st), "loss_l1_multi")
-            idx = torch.tensor([e[0] for e in batch], dtype=torch.int64, device=self.dev)
-            vals.index_copy_(0, idx, stage)
-        # every gradient-L1 entry in one launch (distinct columns per launch: two entries on one column go to two launches)
-        pending = list(grads_l1)
-        while pending:
-            batch, rest, seen = [], [], set()
-            for e in pending:
-                if e[1] in seen or len(batch) == 32:
-                    rest.append(e)
-                else:
-                    seen.add(e[1])
-                    batch.append(e)
-            pending = rest
-            n = len(batch)
-            cols = (C.c_int32 * n)(*[e[1] for e in batch])
-            coefs = (C.c_float * n)(*[e[4] for e in batch])
-            tg = (C.c_void_p * n)(*[e[2].data_ptr() for e in batch])
-            wt = (C.c_void_p * n)(*[(e[3].data_ptr() if e[3] is not None else None) for e in batch])
-            keep.extend([e[2] for e in batch] + [e[3] for e in batch])
-            stage = torch.empty(n, dtype=torch.float64, device=self.dev)
-            wsm = self._ws_multi
-            if rows:
-                L.check(lib.bfm_loss_grad_l1_multi_rows(L.ptr(raw), nvox, n_out, n, cols, coefs, tg, wt, D, H, W, L.ptr(dRaw),
-                                                        L.ptr(stage), L.ptr(wsm), wsm.numel(), st), "loss_grad_l1_multi_rows")
-            else:
-                L.check(lib.bfm_loss_grad_l1_multi(L.ptr(raw), n_out, n, cols, coefs, tg, wt, D, H, W, L.ptr(dRaw), L.ptr(stage),
-                                                   L.ptr(wsm), wsm.numel(), st), "loss_grad_l1_multi")
-            idx = torch.tensor([e[0] for e in batch], dtype=torch.int64, device=self.dev)
-            vals.index_copy_(0, idx, stage)
+                c_ce, c_di = (self._coef(n_, scale) if n_ in self.loss_names else 0.0 for n_ in ("seg_ce", "seg_dice"))
+                P = torch.empty(nvox * ns, dtype=torch.float32, device=self.dev)     # in the layout of raw
+                L.check(lib.bfm_loss_seg(pr, cs, vs, n_out, r0, ns, L.ptr(tgt), L.ptr(self.wce), L.ptr(self.wce), nvox, c_ce,
+                                         c_di, L.ptr(P), pd, slot("seg", 1 + 2 * ns), ws, wsn, st), "loss_seg")
+        # every l1 / l2 entry in one pass over raw per 32, then every gradient-L1 entry (distinct columns per launch: two
+        # entries on one column would race on dRaw)
+        self._issue_entries(dense, lambda n, a, stage: lib.bfm_loss_l1_multi(
+            pr, cs, vs, n_out, nvox, n, a.cols, a.l2, a.clamp, a.coef, a.tg, a.wt, a.mk, pd, stage, wsm, wsmn, st),
+            "loss_l1_multi", vals, keep)
+        self._issue_entries(grads_l1, lambda n, a, stage: lib.bfm_loss_grad_l1_multi(
+            pr, cs, vs, n_out, n, a.cols, a.coef, a.tg, a.wt, D, H, W, pd, stage, wsm, wsmn, st),
+            "loss_grad_l1_multi", vals, keep, distinct_cols=True)
         self._keep = keep
         self._active_rows = active
         return slots, k
@@ -798,7 +763,7 @@ class TrainStep:
             # criterion.py loss_age; its pooled gradient joins dFn after the dense heads' and before normalize_bwd
             age_t = self._age_target(target)
             on = "age" in self.loss_names and age_t is not None
-            coef = scale * self.loss_weights.get("loss_age", 0.0) / self.all_samples if on else 0.0
+            coef = self._coef("age", scale) if on else 0.0
             loss_ptr = None
             if on:
                 slots["age"] = [(k_used, 1)]

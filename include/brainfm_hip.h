@@ -864,35 +864,39 @@ int bfm_transpose_mirror_weights(const float* w_oidhw, int Cout, int Cin, int Ci
  * Replaces, for the supervised heads, Trainer/models/criterion.py:111-124,178-186,215-294 + losses.py:10-74 (loss values
  * and, through autograd, their gradients), head.py:52-59 + model.py:207 (1x1x1 heads over F.normalize'd features),
  * torch.optim.AdamW and the clip/unscale reductions of Trainer/engine.py:128-147.
- * raw / dRaw are the channels-last head outputs [nvox][n_out] of bfm_tail (raw mode); targets and weights keep the
- * reference's NCDHW layout (one channel = nvox contiguous floats; seg target [ns][nvox]). Every loss ADDS
+ * raw / dRaw are the head outputs in one of two layouts, told by the strides every loss entry takes: element (column c,
+ * voxel v) at raw[c * col_stride + v * voxel_stride] and the same for dRaw.
+ *   channels-last [nvox][n_out] (bfm_tail, raw mode):                  col_stride == 1,     voxel_stride == n_out
+ *   rows, [n_out] rows of nvox values (bfm_tail_raw_rows; row pitch):  col_stride >= nvox,  voxel_stride == 1
+ * Any other pair is BFM_E_ARG.  criterion.py walks one channel of the outputs per loss (outputs[key][:, c], NCDHW in the
+ * reference): in rows every access is a contiguous run and the kernels need no LDS staging; the per-voxel expressions are
+ * the same code in both layouts (same bits per voxel; the fp64 sums differ by their fold order).  Targets and weights keep
+ * the reference's NCDHW layout (one channel = nvox contiguous floats; seg target [ns][nvox]).  Every loss ADDS
  * coef * dL/draw into its columns of dRaw (NULL: value only) and writes the loss value(s) in fp64 (device memory).
- *   l1       mean(|o*m - t*m| * w); o clamped to +-clampv first when clampv > 0 (DistProcessor); weight, mask_mul optional
+ *   l1       mean(|o*m - t*m| * w), l2 flag: mean((o*m - t*m)^2 * w) (bias_field_log_type 'l2'); o clamped to +-clampv first
+ *            when clampv > 0 (DistProcessor, no gradient where it clamps); weight w, mask m optional
  *   grad_l1  mean|dx(o) - dx(t)|w + mean|dy ..|w + mean|dz ..|w, forward differences, zero on the last slice
  *   seg      p = softmax(raw[c0:c0+ns]);  loss_out[0] = sum_v CE_v, loss_out[1..ns] = sum_v p t, loss_out[1+ns..] =
- *            sum_v (p+t); gradient of coef_ce * mean_v CE + coef_dice * Dice. P [nvox][ns] receives the probabilities. */
+ *            sum_v (p+t); gradient of coef_ce * mean_v CE + coef_dice * Dice.  P receives the probabilities in the layout of
+ *            raw: [nvox][ns], or [ns] rows of nvox.  Rows: ns <= 64 (BFM_E_SHAPE above). */
 size_t bfm_loss_workspace(int ns);
-int bfm_loss_l1(const float* raw, int n_out, int co, const float* target, const float* weight, const float* mask_mul,
-                int64_t nvox, float clampv, int l2 /* 1: mean squared error (bias_field_log_type 'l2') */, float coef,
-                float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
 /* n <= 32 l1 / l2 entries of one sample in one pass over raw (host arrays of n columns, l2 flags, clamps, coefficients and
  * device pointers; weights / masks arrays or their elements may be NULL); loss_out [n] (device, fp64 means) */
 size_t bfm_loss_l1_multi_workspace(void);
-int bfm_loss_l1_multi(const float* raw, int n_out, int64_t nvox, int n, const int32_t* cols, const int32_t* l2,
-                      const float* clampv, const float* coef, const float* const* targets, const float* const* weights,
-                      const float* const* masks, float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes,
-                      bfm_stream_t stream);
-int bfm_loss_grad_l1(const float* raw, int n_out, int co, const float* target, const float* weight, int D, int H, int W,
-                     float coef, float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes,
-                     bfm_stream_t stream);
-/* every gradient-L1 entry of a sample in one launch: entry k is bfm_loss_grad_l1 on column cols[k] (distinct columns) with
- * coef[k], targets[k], weights[k] (or NULL); loss_out[k] as there.  n <= 32; workspace: bfm_loss_l1_multi_workspace(). */
-int bfm_loss_grad_l1_multi(const float* raw, int n_out, int n, const int32_t* cols, const float* coef,
-                           const float* const* targets, const float* const* weights, int D, int H, int W, float* dRaw,
-                           double* loss_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
-int bfm_loss_seg(const float* raw, int n_out, int c0, int ns, const float* target, const float* wce, const float* wdice,
-                 int64_t nvox, float coef_ce, float coef_dice, float* P, float* dRaw, double* loss_out /*[1+2ns]*/,
-                 void* workspace, size_t workspace_bytes, bfm_stream_t stream);
+int bfm_loss_l1_multi(const float* raw, int64_t col_stride, int64_t voxel_stride, int n_out, int64_t nvox, int n,
+                      const int32_t* cols, const int32_t* l2, const float* clampv, const float* coef,
+                      const float* const* targets, const float* const* weights, const float* const* masks, float* dRaw,
+                      double* loss_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
+/* every gradient-L1 entry of a sample in one launch: entry k is grad_l1 of column cols[k] against targets[k] [D][H][W] with
+ * the optional voxel weight weights[k] (the weight of the voxel a difference is anchored at) and coefficient coef[k];
+ * loss_out[k] (device, fp64) = the sum of the three means.  The columns of one call are distinct (two entries on one
+ * column would race on dRaw: BFM_E_ARG).  n <= 32; workspace: bfm_loss_l1_multi_workspace(). */
+int bfm_loss_grad_l1_multi(const float* raw, int64_t col_stride, int64_t voxel_stride, int n_out, int n, const int32_t* cols,
+                           const float* coef, const float* const* targets, const float* const* weights, int D, int H, int W,
+                           float* dRaw, double* loss_out, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
+int bfm_loss_seg(const float* raw, int64_t col_stride, int64_t voxel_stride, int n_out, int c0, int ns, const float* target,
+                 const float* wce, const float* wdice, int64_t nvox, float coef_ce, float coef_dice, float* P, float* dRaw,
+                 double* loss_out /*[1+2ns]*/, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
 /* Trainer/models/criterion.py:193-212 loss_pathol_ce / loss_pathol_dice on p = sigmoid(raw) (PatholProcessor,
  * Trainer/models/joiner.py:79-87), the one-channel pathology head: ce = mean_v(-log(max(p, 1e-5)) t), dice = 1 - 2 sum(p t) /
  * max(sum(p + t), 1e-5).  The head output of voxel v is raw[col_offset + v * voxel_stride] (channels-last: column, n_out;
@@ -939,25 +943,11 @@ int bfm_loss_contrastive(const float* featP, const float* featQ, int C, int64_t 
 size_t bfm_head_bwd_workspace(int n_out, int C, int64_t nvox);
 int bfm_head_bwd(const float* dRaw, const float* Fn, const float* head_w, int n_out, int C, int64_t nvox, float* dW,
                  float* db, float* dFn, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
-/* ---- the same five steps with the head outputs as [n_out] ROWS of nvox values (row pitch row_stride >= nvox) instead of
- * channels-last [nvox][n_out].  criterion.py walks one channel of the outputs per loss (outputs[key][:, c], NCDHW in the
- * reference): in rows every access is a contiguous run, the kernels need no LDS staging and the per-voxel expressions are
- * those of the channels-last entries above.  P of bfm_loss_seg_rows is [ns][nvox]; ns <= 64.  bfm_tail_raw_rows is
- * TaskHead.forward alone (head.py:52-59) writing that layout; bfm_head_bwd_rows needs C == 64 and n_out <= 96. */
+/* ---- the head outputs as [n_out] ROWS of nvox values (row pitch row_stride >= nvox) instead of channels-last
+ * [nvox][n_out]: bfm_tail_raw_rows is TaskHead.forward alone (head.py:52-59) writing that layout, the loss entries above
+ * read it by their strides, and bfm_head_bwd_rows (C == 64 and n_out <= 96) is bfm_head_bwd on dRaw in rows. */
 int bfm_tail_raw_rows(const float* feat, int64_t nvox, const bfm_tail_desc_t* desc, float* feat_norm, float* raw_rows,
                       int64_t row_stride, bfm_stream_t stream);
-int bfm_loss_l1_multi_rows(const float* raw_rows, int64_t row_stride, int n_out, int64_t nvox, int n, const int32_t* cols,
-                           const int32_t* l2, const float* clampv, const float* coef, const float* const* targets,
-                           const float* const* weights, const float* const* masks, float* dRaw_rows, double* loss_out,
-                           void* workspace, size_t workspace_bytes, bfm_stream_t stream);
-int bfm_loss_grad_l1_multi_rows(const float* raw_rows, int64_t row_stride, int n_out, int n, const int32_t* cols,
-                                const float* coef, const float* const* targets, const float* const* weights, int D, int H,
-                                int W, float* dRaw_rows, double* loss_out, void* workspace, size_t workspace_bytes,
-                                bfm_stream_t stream);
-int bfm_loss_seg_rows(const float* raw_rows, int64_t row_stride, int n_out, int c0, int ns, const float* target,
-                      const float* wce, const float* wdice, int64_t nvox, float coef_ce, float coef_dice, float* P,
-                      float* dRaw_rows, double* loss_out /*[1+2ns]*/, void* workspace, size_t workspace_bytes,
-                      bfm_stream_t stream);
 int bfm_head_bwd_rows(const float* dRaw_rows, int64_t row_stride, const float* Fn, const float* head_w, int n_out, int C,
                       int64_t nvox, float* dW, float* db, float* dFn, void* workspace, size_t workspace_bytes,
                       bfm_stream_t stream);

@@ -396,8 +396,8 @@ def test_heads_backward_fused_pass_vs_float64(n_out, nvox):
 
 
 def test_rows_layout_of_the_head_outputs_equals_channels_last():
-    """Round 4: the training step keeps the head outputs as [n_out] rows of nvox values (bfm_tail_raw_rows, bfm_loss_*_rows,
-    bfm_head_bwd_rows).  Per voxel the rows kernels evaluate the channels-last kernels' expressions: logits, probabilities
+    """Round 4: the training step keeps the head outputs as [n_out] rows of nvox values (bfm_tail_raw_rows, the loss entries
+    by their strides, bfm_head_bwd_rows).  Per voxel the rows kernels evaluate the channels-last kernels' expressions: logits, probabilities
     and d/d(raw) must be the SAME BITS (transposed), the fp64 loss sums agree to rounding of a different fold order."""
     import ctypes as C
     from brainfm_amd import _lib as L
@@ -429,6 +429,251 @@ def test_rows_layout_of_the_head_outputs_equals_channels_last():
     for k in la:
         assert abs(la[k] - lb[k]) <= 1e-12 * max(1.0, abs(la[k])), (k, la[k], lb[k])
     assert torch.equal(da, db), float((da - db).abs().max())
+
+
+# ---- the three loss exports at the edges the golden case does not reach ---------------------------------------------
+_EDGE_DIMS = ((5, 6, 7), (9, 7, 5))       # fewer voxels than one 256-thread block or tile; a ragged last tile
+_EDGE_N_OUT = 69                           # the width of the shipped head set
+
+
+def _both_layouts(raw):
+    """(tag, head outputs on the device, col_stride, voxel_stride, view of such a tensor as (nvox, n_out))."""
+    nvox, n_out = raw.shape
+    return (("cl", raw.to(_dev()), 1, n_out, lambda t: t),
+            ("rows", raw.t().contiguous().to(_dev()), nvox, 1, lambda t: t.t()))
+
+
+def _close_to_f64(tag, got, ref):
+    """The existing tolerances of test_losses_match_oracle_on_random_heads for values (vs float64)."""
+    for k, (g, v) in enumerate(zip(got, ref)):
+        print("VALUE %-28s %2d  hip %.12g  ref64 %.12g" % (tag, k, g, v))
+        assert abs(g - v) <= 2e-6 * max(abs(v), 1e-3), (tag, k, g, v)
+
+
+def _grad_close_to_f64(tag, dRaw, ref, g32=None):
+    """... and for gradients: 1e-5 * max|ref|, which no entry may exceed at these sizes.  g32: the fp32 torch evaluation of
+    the same loss; the seed's check is that IT has no entry past the tolerance (no residual that rounds across zero and
+    flips a sign gradient)."""
+    tol = 1e-5 * np.abs(ref).max()
+    if g32 is not None:
+        assert np.abs(g32 - ref).max() <= tol, ("seed: the fp32 torch evaluation itself flips a sign", tag)
+    err = np.abs(dRaw.cpu().numpy().astype(np.float64) - ref)
+    print("GRAD  %-28s max err %.3e  tol %.3e  max|ref| %.3e" % (tag, err.max(), tol, np.abs(ref).max()))
+    assert err.max() <= tol, (tag, int((err > tol).sum()), err.max(), tol)
+
+
+def _seg_ref(raw, c0, ns, tgt, wce, dims, c_ce, c_dice, dtype):
+    """(ce, dice), d(c_ce ce + c_dice dice)/d(raw): torch autograd of the restated criterion's seg terms in `dtype`."""
+    r = raw.detach().to(dtype, copy=True).requires_grad_(True)
+    out = T.processors({"segmentation": r[:, c0:c0 + ns].t().reshape((1, ns) + dims)})
+    ld = T.sample_losses(out, {"segmentation": tgt.to(dtype).reshape((1, ns) + dims)}, {}, ["seg_ce", "seg_dice"],
+                         wce.to(dtype))
+    (c_ce * ld["loss_seg_ce"] + c_dice * ld["loss_seg_dice"]).backward()
+    return (float(ld["loss_seg_ce"].detach()), float(ld["loss_seg_dice"].detach())), r.grad.double().numpy()
+
+
+def _seg_case(dims, ns, seed):
+    g = torch.Generator().manual_seed(seed)
+    nvox = dims[0] * dims[1] * dims[2]
+    raw = torch.randn((nvox, _EDGE_N_OUT), generator=g) * 1.5
+    tgt = torch.nn.functional.one_hot(torch.randint(0, ns, (nvox,), generator=g), ns).t().float().contiguous()
+    wce = (0.5 + torch.rand(ns, generator=g)) / ns
+    return raw, tgt, wce
+
+
+def _call_seg(lib, L, r, cs, vs, c0, ns, tgt, wce, nvox, c_ce, c_dice):
+    dev = _dev()
+    P = torch.full((nvox * ns,), float("nan"), device=dev)
+    dRaw = torch.zeros_like(r)
+    out = torch.zeros(1 + 2 * ns, dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.bfm_loss_workspace(ns), dtype=torch.uint8, device=dev)
+    rc = lib.bfm_loss_seg(L.ptr(r), cs, vs, _EDGE_N_OUT, c0, ns, L.ptr(tgt), L.ptr(wce), L.ptr(wce), nvox, c_ce, c_dice,
+                          L.ptr(P), L.ptr(dRaw), L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr())
+    return rc, P, dRaw, out.cpu()
+
+
+@pytest.mark.parametrize("dims", _EDGE_DIMS)
+def test_seg_export_at_class_count_and_size_edges(dims):
+    """bfm_loss_seg by its strides, ns in {1, 32, 33, 61, 62, 64} classes at column 3 of 69 on volumes smaller than one tile
+    and with a ragged last tile: 32 / 33 switch the rows kernels' register arrays, 61 / 62 the tiled and the untiled
+    channels-last kernels, 64 is the rows limit (65: BFM_E_SHAPE).  Where both layouts run the shared per-voxel code
+    (ns <= 61), P and dRaw are the same bits transposed and the sums agree to 1e-12; every case is compared with float64
+    autograd of the restated criterion.  ns <= 61: the tolerances of test_losses_match_oracle_on_random_heads.  ns in
+    {62, 64}: 8 x the distance of an fp32 torch evaluation of the same expression from float64, floor 1e-6 (the rule of
+    tests/test_gpu_evaluator.py).  Measured on these inputs, the fp32 distance is at most 3.1e-8 on a value (relative to
+    max(1, |value|)): the floor decides there; on a gradient, as a share of max|gradient|, it is 1.6e-7 / 1.7e-7
+    (5 x 6 x 7, ns 62 / 64) and 2.2e-7 / 7.2e-8 (9 x 7 x 5), which allows 1.3e-6, 1.4e-6, 1.7e-6 and the floor."""
+    from brainfm_amd import _lib as L
+    lib = L.load()
+    nvox = dims[0] * dims[1] * dims[2]
+    c0, c_ce, c_dice = 3, 0.7, 1.3
+    for ns in (1, 32, 33, 61, 62, 64):
+        raw, tgt, wce = _seg_case(dims, ns, 100 + ns)
+        tgt_d, wce_d = tgt.to(_dev()), wce.to(_dev())
+        (ce64, dice64), g64 = _seg_ref(raw, c0, ns, tgt, wce, dims, c_ce, c_dice, torch.float64)
+        (ce32, dice32), g32 = _seg_ref(raw, c0, ns, tgt, wce, dims, c_ce, c_dice, torch.float32)     # the yardstick for ns > 61
+        res = {}
+        for tag, r, cs, vs, as_cl in _both_layouts(raw):
+            rc, P, dRaw, out = _call_seg(lib, L, r, cs, vs, c0, ns, tgt_d, wce_d, nvox, c_ce, c_dice)
+            assert rc == 0, (tag, ns, rc)
+            num, den = out[1:1 + ns], out[1 + ns:]
+            vals = (float(out[0]) / nvox, float((wce.double() * (1.0 - 2.0 * num / torch.clamp(den, min=1e-5))).sum()))
+            res[tag] = (P.reshape(nvox, ns) if tag == "cl" else P.reshape(ns, nvox).t(), as_cl(dRaw), out)
+            name = "seg %s ns=%d %s" % (dims, ns, tag)
+            if ns <= 61:
+                _close_to_f64(name, vals, (ce64, dice64))
+                _grad_close_to_f64(name, as_cl(dRaw), g64)
+            else:
+                for got, v64, v32 in zip(vals, (ce64, dice64), (ce32, dice32)):
+                    scale = max(1.0, abs(v64))
+                    print("VALUE %-28s hip-ref64 %.3e  ref32-ref64 %.3e" % (name, abs(got - v64) / scale, abs(v32 - v64) / scale))
+                    assert abs(got - v64) / scale <= max(1e-6, 8.0 * abs(v32 - v64) / scale), (name, got, v64, v32)
+                scale = np.abs(g64).max()
+                dist = np.abs(as_cl(dRaw).cpu().numpy().astype(np.float64) - g64).max() / scale
+                yard = np.abs(g32 - g64).max() / scale
+                print("GRAD  %-28s hip-ref64 %.3e  ref32-ref64 %.3e" % (name, dist, yard))
+                assert dist <= max(1e-6, 8.0 * yard), (name, dist, yard)
+        (Pa, da, oa), (Pb, db, ob) = res["cl"], res["rows"]
+        if ns <= 61:
+            assert torch.equal(Pa, Pb) and torch.equal(da, db), (dims, ns)
+            assert bool(((oa - ob).abs() <= 1e-12 * torch.clamp(oa.abs(), min=1.0)).all()), (dims, ns)
+    raw, tgt, wce = _seg_case(dims, 65, 165)
+    _, r, cs, vs, _ = _both_layouts(raw)[1]
+    assert _call_seg(lib, L, r, cs, vs, c0, 65, tgt.to(_dev()), wce.to(_dev()), nvox, c_ce, c_dice)[0] == -2   # BFM_E_SHAPE
+    _, r, _, _, _ = _both_layouts(raw)[0]
+    assert _call_seg(lib, L, r, 2, 2, c0, 32, tgt.to(_dev()), wce.to(_dev()), nvox, c_ce, c_dice)[0] == -1    # BFM_E_ARG
+
+
+def _l1_ref(raw, entries, dtype):
+    """Per-entry values and d(sum coef * value)/d(raw) of l1 / l2 entries (col, target, weight, mask, clamp, l2, coef)."""
+    r = raw.detach().to(dtype, copy=True).requires_grad_(True)
+    vals = []
+    for col, t, w, m, cl, l2, _ in entries:
+        o = r[:, col]
+        if cl > 0:
+            o = torch.clamp(o, -cl, cl)
+        m = 1.0 if m is None else m.to(dtype)
+        d = o * m - t.to(dtype) * m
+        vals.append(torch.mean((d * d if l2 else d.abs()) * (1.0 if w is None else w.to(dtype))))
+    sum(e[-1] * v for e, v in zip(entries, vals)).backward()
+    return [float(v.detach()) for v in vals], r.grad.double().numpy()
+
+
+def _gl1_ref(raw, entries, dims, dtype):
+    """The same for gradient-L1 entries (col, target, weight, coef)."""
+    r = raw.detach().to(dtype, copy=True).requires_grad_(True)
+    vals = [T.grad_l1(r[:, col].reshape(dims), t.to(dtype).reshape(dims), 1.0 if w is None else w.to(dtype).reshape(dims))
+            for col, t, w, _ in entries]
+    sum(e[-1] * v for e, v in zip(entries, vals)).backward()
+    return [float(v.detach()) for v in vals], r.grad.double().numpy()
+
+
+def _issue(entries, launch, vals, distinct_cols=False):
+    """Through TrainStep's batching helper (it reads the device of its step and nothing else); returns the launch sizes."""
+    import types
+    from brainfm_amd import train as TR
+    sizes = []
+
+    def counted(n, a, stage):
+        sizes.append(n)
+        return launch(n, a, stage)
+    TR.TrainStep._issue_entries(types.SimpleNamespace(dev=_dev()), entries, counted, "loss entries", vals, [],
+                                distinct_cols=distinct_cols)
+    return sizes
+
+
+@pytest.mark.parametrize("dims", _EDGE_DIMS)
+def test_l1_multi_export_two_launches_both_layouts(dims):
+    """bfm_loss_l1_multi by its strides: 33 entries over 69 columns (32 + 1: two launches through the batching helper), l1 and
+    l2, a clamp, a voxel weight and a mask mixed.  The two layouts run one per-voxel function: dRaw is the same bits, the
+    values agree to 1e-12; both are compared with float64 autograd at the tolerances of
+    test_losses_match_oracle_on_random_heads, no gradient entry past 1e-5 * max|ref|.  The seed's check: an fp32 torch
+    evaluation of the same losses has no such entry either (_grad_close_to_f64), so no |.| residual rounds across zero."""
+    import ctypes as C
+    from brainfm_amd import _lib as L
+    lib = L.load()
+    dev = _dev()
+    nvox = dims[0] * dims[1] * dims[2]
+    g = torch.Generator().manual_seed(31)
+    raw = torch.randn((nvox, _EDGE_N_OUT), generator=g) * 1.5
+    entries = []
+    for k, col in enumerate(torch.randperm(_EDGE_N_OUT, generator=g)[:33].tolist()):
+        entries.append((col, torch.randn(nvox, generator=g), torch.rand(nvox, generator=g) if k % 4 == 1 else None,
+                        torch.rand(nvox, generator=g) if k % 5 == 2 else None, 1.0 if k % 3 == 0 else 0.0, int(k % 7 == 3),
+                        0.25 + 0.05 * k))
+    v64, g64 = _l1_ref(raw, entries, torch.float64)
+    _, g32 = _l1_ref(raw, entries, torch.float32)
+    on_dev = [tuple(x.to(dev) if isinstance(x, torch.Tensor) else x for x in e) for e in entries]
+    ws = torch.empty(lib.bfm_loss_l1_multi_workspace(), dtype=torch.uint8, device=dev)
+    res = []
+    for tag, r, cs, vs, as_cl in _both_layouts(raw):
+        dRaw = torch.zeros_like(r)
+        vals = torch.zeros(33, dtype=torch.float64, device=dev)
+        sizes = _issue([(k,) + e for k, e in enumerate(on_dev)], lambda n, a, stage: lib.bfm_loss_l1_multi(
+            L.ptr(r), cs, vs, _EDGE_N_OUT, nvox, n, a.cols, a.l2, a.clamp, a.coef, a.tg, a.wt, a.mk, L.ptr(dRaw), stage,
+            L.ptr(ws), ws.numel(), L.stream_ptr()), vals)
+        assert sizes == [32, 1]
+        _close_to_f64("l1 %s %s" % (dims, tag), vals.cpu().tolist(), v64)
+        _grad_close_to_f64("l1 %s %s" % (dims, tag), as_cl(dRaw), g64, g32)
+        res.append((vals.cpu(), as_cl(dRaw)))
+    (va, da), (vb, db) = res
+    assert torch.equal(da, db)
+    assert bool(((va - vb).abs() <= 1e-12 * torch.clamp(va.abs(), min=1.0)).all())
+    # strides that are neither layout
+    stage = torch.zeros(1, dtype=torch.float64, device=dev)
+    rc = lib.bfm_loss_l1_multi(L.ptr(raw.to(dev)), 2, 2, _EDGE_N_OUT, nvox, 1, (C.c_int32 * 1)(0), (C.c_int32 * 1)(0),
+                               (C.c_float * 1)(0.0), (C.c_float * 1)(1.0), (C.c_void_p * 1)(on_dev[0][1].data_ptr()), None,
+                               None, None, L.ptr(stage), L.ptr(ws), ws.numel(), L.stream_ptr())
+    assert rc == -1                                                                                   # BFM_E_ARG
+
+
+@pytest.mark.parametrize("dims", _EDGE_DIMS)
+def test_grad_l1_multi_export_same_column_pair_both_layouts(dims):
+    """bfm_loss_grad_l1_multi by its strides: five entries on distinct columns (two with a voxel weight) and two more on ONE
+    column.  The export refuses the pair in one call (BFM_E_ARG: they would race on dRaw); the batching helper sends the
+    second of the pair in a launch of its own.  Both layouts are instantiations of one kernel around one stencil: dRaw is the
+    same bits, the values agree to 1e-12, and both match float64 autograd at the tolerances of
+    test_losses_match_oracle_on_random_heads with no gradient entry past 1e-5 * max|ref|.  The seed's check is
+    _grad_close_to_f64's: the fp32 torch evaluation has no such entry either."""
+    import ctypes as C
+    from brainfm_amd import _lib as L
+    lib = L.load()
+    dev = _dev()
+    D, H, W = dims
+    nvox = D * H * W
+    g = torch.Generator().manual_seed(47)
+    raw = torch.randn((nvox, _EDGE_N_OUT), generator=g) * 1.5
+    entries = [(col, torch.randn(nvox, generator=g), torch.rand(nvox, generator=g) if k % 3 == 1 else None, 0.5 + 0.1 * k)
+               for k, col in enumerate((0, 17, 40, 68, 5, 23, 23))]
+    v64, g64 = _gl1_ref(raw, entries, dims, torch.float64)
+    _, g32 = _gl1_ref(raw, entries, dims, torch.float32)
+    on_dev = [tuple(x.to(dev) if isinstance(x, torch.Tensor) else x for x in e) for e in entries]
+    ws = torch.empty(lib.bfm_loss_l1_multi_workspace(), dtype=torch.uint8, device=dev)
+    res = []
+    for tag, r, cs, vs, as_cl in _both_layouts(raw):
+        dRaw = torch.zeros_like(r)
+        vals = torch.zeros(7, dtype=torch.float64, device=dev)
+
+        def launch(n, a, stage, r=r, cs=cs, vs=vs, dRaw=dRaw):
+            return lib.bfm_loss_grad_l1_multi(L.ptr(r), cs, vs, _EDGE_N_OUT, n, a.cols, a.coef, a.tg, a.wt, D, H, W,
+                                              L.ptr(dRaw), stage, L.ptr(ws), ws.numel(), L.stream_ptr())
+        sizes = _issue([(k, col, t, w, None, 0.0, 0, coef) for k, (col, t, w, coef) in enumerate(on_dev)], launch, vals,
+                       distinct_cols=True)
+        assert sizes == [6, 1]
+        _close_to_f64("grad_l1 %s %s" % (dims, tag), vals.cpu().tolist(), v64)
+        _grad_close_to_f64("grad_l1 %s %s" % (dims, tag), as_cl(dRaw), g64, g32)
+        res.append((vals.cpu(), as_cl(dRaw)))
+        # the pair in one call, and strides that are neither layout
+        stage = torch.zeros(2, dtype=torch.float64, device=dev)
+        cols, coefs = (C.c_int32 * 2)(23, 23), (C.c_float * 2)(1.0, 1.0)
+        tg = (C.c_void_p * 2)(on_dev[5][1].data_ptr(), on_dev[6][1].data_ptr())
+        for cs_, vs_ in ((cs, vs), (2, 2)):
+            cols[1] = 23 if (cs_, vs_) == (cs, vs) else 24
+            assert lib.bfm_loss_grad_l1_multi(L.ptr(r), cs_, vs_, _EDGE_N_OUT, 2, cols, coefs, tg, None, D, H, W, None,
+                                              L.ptr(stage), L.ptr(ws), ws.numel(), L.stream_ptr()) == -1   # BFM_E_ARG
+    (va, da), (vb, db) = res
+    assert torch.equal(da, db)
+    assert bool(((va - vb).abs() <= 1e-12 * torch.clamp(va.abs(), min=1.0)).all())
 
 
 def _split_f16(x):
