@@ -146,7 +146,7 @@ SIGNATURES = {
     "bfm_mean_lastdim": (_I, [_P, _L, _I, _P, _P]),
     "bfm_pack_conv_weights_wino_bytes": (_Z, [_I, _I, _I]),
     "bfm_pack_conv_weights_wino": (_I, [_P, _I, _I, _F, _I, _P, C.POINTER(_I), _P]),
-    "bfm_bspline3_prefilter_axis": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P, _F, _F, _F, _P]),
+    "bfm_bspline3_prefilter_axis": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P, _F, _F, _F, _I, _P]),
     "bfm_bspline3_resample_axis": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "bfm_conv3x3x3_wino_rows": (_I, [_I, _I, _I, _I]),
     "bfm_conv3x3x3_wino_ex": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _P]),
@@ -169,6 +169,9 @@ SIGNATURES = {
     "bfm_maxpool2_batch": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "bfm_grid_push3d_linear": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _P, _P]),
     "bfm_grid_grad3d_linear": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _P, _P]),
+    "bfm_grid_pull3d_spline": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
+    "bfm_grid_push3d_spline": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
+    "bfm_grid_grad3d_spline": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
     "bfm_gn_stats_train": (_I, [_P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "bfm_lrelu_bwd": (_I, [_P, _P, _L, _F, _P, _P]),
     "bfm_lrelu_bwd_ex": (_I, [_P, _P, _L, _F, _P, _P, _P]),

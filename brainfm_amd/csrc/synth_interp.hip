@@ -12,6 +12,7 @@
 // which is what makes the fp32 results bit-identical to the CPU path.
 #include "bfm_common.h"
 #include "gather3d.h"
+#include "interp_bounds.h"
 #include <cstdlib>
 
 namespace {
@@ -440,57 +441,7 @@ __global__ void __launch_bounds__(256) conv1d_axis(const float* __restrict__ in,
     }
 }
 
-// ---- interpol bounds (utils/interpol/bounds.py:24-89)
-__device__ __forceinline__ int imod(int a, int m) { int r = a % m; return r < 0 ? r + m : r; }
-
-__device__ __forceinline__ int bound_index(int i, int n, int b) {
-    switch (b) {
-        case 0: case 1: return min(max(i, 0), n - 1);
-        case 3: case 5: {
-            const int n2 = n * 2;
-            i = i < 0 ? n2 - 1 - imod(-i - 1, n2) : imod(i, n2);
-            return i >= n ? n2 - 1 - i : i;
-        }
-        case 2: {
-            if (n == 1) return 0;
-            const int n2 = (n - 1) * 2;
-            i = imod(abs(i), n2);
-            return i >= n ? n2 - i : i;
-        }
-        case 4: {
-            const int n2 = 2 * (n + 1);
-            i = i < 0 ? -i - 2 : i;
-            i = imod(i, n2);
-            i = i > n ? n2 - 2 - i : i;
-            i = i == -1 ? 0 : i;
-            return i == n ? n - 1 : i;
-        }
-        case 6: return imod(i, n);
-        default: return i;
-    }
-}
-
-__device__ __forceinline__ int bound_sign(int i, int n, int b) {
-    switch (b) {
-        case 4: {
-            if (n == 1) return 1;
-            const int n2 = 2 * (n + 1);
-            i = i < 0 ? n - 1 - i : i;
-            i = imod(i, n2);
-            int x = i == 0 ? 0 : 1;
-            x = (imod(i, n + 1) == n) ? 0 : x;
-            i = i / (n + 1);
-            return (i & 1) ? -x : x;
-        }
-        case 5: {
-            i = i < 0 ? n - 1 - i : i;
-            i = i / n;
-            return (i & 1) ? -1 : 1;
-        }
-        case 0: return (i < 0 || i >= n) ? 0 : 1;
-        default: return 1;
-    }
-}
+// interpol bounds (bound_index / bound_sign): interp_bounds.h, shared with spline_grid.hip
 
 __global__ void grid_pull3d(const float* __restrict__ inp, int Bi, int C, int nx, int ny, int nz,
                             const float* __restrict__ grid, int Bg, int64_t nout, int bx, int by, int bz, int extrap,

@@ -1,6 +1,8 @@
-"""Host-side mirror of the part of ``utils/interpol`` (vendored torch-interpol) that is on the hot
-path: ``grid_pull`` with linear interpolation -> ``iso1.pull3d`` (utils/interpol/api.py:137-200,
-autograd.py:125-152, pushpull.py:35-66, iso1.py:28-133, bounds.py:24-89, jit_utils.py:241-255).
+"""Host-side mirror of ``utils/interpol`` (vendored torch-interpol): ``grid_pull`` / ``grid_push`` / ``grid_count`` /
+``grid_grad`` for spline orders 0 to 3, any order per axis, in 3-D (utils/interpol/api.py:137-335, autograd.py:125-245,
+pushpull.py:35-282).  All-linear calls run ``iso1`` (iso1.py:28-387) on the kernels of synth_interp.hip; every other
+combination runs the generic path (nd.py:30-290, splines.py:30-103, bounds.py:24-89) on spline_grid.hip.  ``prefilter``
+goes through ``spline_coeff_nd`` (coeff.py:254-344), which is differentiable (autograd.py:276-300).
 
 grid_pull / grid_push are differentiable to first order through grid_push / grid_grad; grid_grad itself
 is forward only.
@@ -14,7 +16,35 @@ from . import _lib as L
 _BOUND = dict(zero=0, zeros=0, replicate=1, nearest=1, repeat=1, border=1, dct1=2, mirror=2, dct2=3, reflect=3,
               reflection=3, neumann=3, dst1=4, antimirror=4, dst2=5, antireflect=5, dirichlet=5, dft=6, wrap=6,
               circular=6)
-_INTER = {"nearest": 0, "linear": 1, 0: 0, 1: 1}
+_SPLINE_ORDER = {"nearest": 0, "zeroth": 0, "linear": 1, "first": 1, "quadratic": 2, "second": 2, "cubic": 3, "third": 3,
+                 "fourth": 4, "fifth": 5, "sixth": 6, "seventh": 7}
+_LINEAR = (1, 1, 1)
+
+
+def _order_list(interpolation, high_names=True):
+    """autograd.py:77-122 inter_to_nitorch + jit_utils.pad_list_int: names or integers, one per axis, padded with the
+    last entry.  Orders 4 to 7 exist in the reference and are not implemented here.  high_names=False (grid_pull / push /
+    count / grad): orders 2 and 3 are taken as integers only -- their names ('quadratic', 'cubic', ...) keep raising
+    NotImplementedError there, the behaviour those functions are pinned to; 'nearest' and 'linear' are taken."""
+    orders = list(interpolation) if isinstance(interpolation, (list, tuple)) else [interpolation]
+    out = []
+    for o in orders:
+        if isinstance(o, str):
+            if o.lower() not in _SPLINE_ORDER:
+                raise ValueError("Unknown interpolation order {}".format(o))
+            if not high_names and 2 <= _SPLINE_ORDER[o.lower()] <= 3:
+                raise NotImplementedError("interpolation order '%s' by name is not implemented for pull / push / count / "
+                                          "grad: pass the integer %d" % (o, _SPLINE_ORDER[o.lower()]))
+            o = _SPLINE_ORDER[o.lower()]
+        o = int(o)
+        if not 0 <= o <= 7:
+            raise ValueError("Unknown interpolation order {}".format(o))
+        if o > 3:
+            raise NotImplementedError("interpolation order %d is not implemented (orders 0 to 3 are)" % o)
+        out.append(o)
+    while len(out) < 3:
+        out.append(out[-1])
+    return tuple(out[:3])
 
 
 def _bound_list(bound):
@@ -47,75 +77,88 @@ def _prep(input, grid, dim=3):
 
 
 def _opts(interpolation, bound, extrapolate):
-    orders = interpolation if isinstance(interpolation, (list, tuple)) else [interpolation]
-    if any(_INTER.get(o, o) != 1 for o in orders):
-        raise NotImplementedError("only first-order (linear) interpolation is implemented for pull/push/grad")
     ext = {False: 0, True: 1, "no": 0, "yes": 1, "hist": 2}.get(extrapolate, extrapolate)
-    return (C.c_int * 3)(*_bound_list(bound)), int(ext)
+    return (C.c_int * 3)(*_bound_list(bound)), _order_list(interpolation, high_names=False), int(ext)
 
 
-def _pull_raw(x, g, b, ext):
+def _pull_raw(x, g, b, o, ext):
     B, Cc = x.shape[0], x.shape[1]
     gs = tuple(g.shape[1:4])
     out = torch.empty((B, Cc) + gs, dtype=torch.float32, device=x.device)
-    L.check(L.load().bfm_grid_pull3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
-                                            gs[1], gs[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_pull3d_linear")
+    if o == _LINEAR:
+        L.check(L.load().bfm_grid_pull3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
+                                                gs[1], gs[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_pull3d_linear")
+    else:
+        L.check(L.load().bfm_grid_pull3d_spline(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
+                                                gs[1], gs[2], b, (C.c_int * 3)(*o), ext, L.ptr(out), L.stream_ptr()),
+                "grid_pull3d_spline")
     return out
 
 
-def _push_raw(x, g, shape, b, ext):
+def _push_raw(x, g, shape, b, o, ext):
     B, Cc = x.shape[0], x.shape[1]
     out = torch.zeros((B, Cc) + tuple(shape), dtype=torch.float32, device=x.device)
-    L.check(L.load().bfm_grid_push3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, shape[0],
-                                            shape[1], shape[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_push3d_linear")
+    if o == _LINEAR:
+        L.check(L.load().bfm_grid_push3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, shape[0],
+                                                shape[1], shape[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_push3d_linear")
+    else:
+        L.check(L.load().bfm_grid_push3d_spline(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, shape[0],
+                                                shape[1], shape[2], b, (C.c_int * 3)(*o), ext, L.ptr(out), L.stream_ptr()),
+                "grid_push3d_spline")
     return out
 
 
-def _grad_raw(x, g, b, ext):
+def _grad_raw(x, g, b, o, ext):
     B, Cc = x.shape[0], x.shape[1]
     gs = tuple(g.shape[1:4])
     out = torch.empty((B, Cc) + gs + (3,), dtype=torch.float32, device=x.device)
-    L.check(L.load().bfm_grid_grad3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
-                                            gs[1], gs[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_grad3d_linear")
+    if o == _LINEAR:
+        L.check(L.load().bfm_grid_grad3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
+                                                gs[1], gs[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_grad3d_linear")
+    else:
+        L.check(L.load().bfm_grid_grad3d_spline(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
+                                                gs[1], gs[2], b, (C.c_int * 3)(*o), ext, L.ptr(out), L.stream_ptr()),
+                "grid_grad3d_spline")
     return out
 
 
 class _GridPull(torch.autograd.Function):
-    """autograd.py:125-152 + pushpull.py:262-285: d/dinput = push(grad), d/dgrid = sum_c grad * grid_grad(input)."""
+    """autograd.py:125-152 + pushpull.py:237-258: d/dinput = push(grad), d/dgrid = sum_c grad * grid_grad(input) (zero at
+    order 0, where grid_grad is)."""
 
     @staticmethod
-    def forward(ctx, x, g, b, ext):
-        ctx.opt = (b, ext)
+    def forward(ctx, x, g, b, o, ext):
+        ctx.opt = (b, o, ext)
         ctx.save_for_backward(x, g)
-        return _pull_raw(x, g, b, ext)
+        return _pull_raw(x, g, b, o, ext)
 
     @staticmethod
     def backward(ctx, grad):
         x, g = ctx.saved_tensors
-        b, ext = ctx.opt
+        b, o, ext = ctx.opt
         grad = grad.contiguous().to(torch.float32)
-        gi = _push_raw(grad, g, x.shape[2:], b, ext) if ctx.needs_input_grad[0] else None
-        gg = (_grad_raw(x, g, b, ext) * grad.unsqueeze(-1)).sum(dim=1) if ctx.needs_input_grad[1] else None
-        return gi, gg, None, None
+        gi = _push_raw(grad, g, x.shape[2:], b, o, ext) if ctx.needs_input_grad[0] else None
+        gg = (_grad_raw(x, g, b, o, ext) * grad.unsqueeze(-1)).sum(dim=1) if ctx.needs_input_grad[1] else None
+        return gi, gg, None, None, None
 
 
 class _GridPush(torch.autograd.Function):
-    """autograd.py:155-190 + pushpull.py:288-310: d/dinput = pull(grad), d/dgrid = sum_c input * grid_grad(grad)."""
+    """autograd.py:155-190 + pushpull.py:262-282: d/dinput = pull(grad), d/dgrid = sum_c input * grid_grad(grad)."""
 
     @staticmethod
-    def forward(ctx, x, g, shape, b, ext):
-        ctx.opt = (b, ext)
+    def forward(ctx, x, g, shape, b, o, ext):
+        ctx.opt = (b, o, ext)
         ctx.save_for_backward(x, g)
-        return _push_raw(x, g, shape, b, ext)
+        return _push_raw(x, g, shape, b, o, ext)
 
     @staticmethod
     def backward(ctx, grad):
         x, g = ctx.saved_tensors
-        b, ext = ctx.opt
+        b, o, ext = ctx.opt
         grad = grad.contiguous().to(torch.float32)
-        gi = _pull_raw(grad, g, b, ext) if ctx.needs_input_grad[0] else None
-        gg = (_grad_raw(grad, g, b, ext) * x.unsqueeze(-1)).sum(dim=1) if ctx.needs_input_grad[1] else None
-        return gi, gg, None, None, None
+        gi = _pull_raw(grad, g, b, o, ext) if ctx.needs_input_grad[0] else None
+        gg = (_grad_raw(grad, g, b, o, ext) * x.unsqueeze(-1)).sum(dim=1) if ctx.needs_input_grad[1] else None
+        return gi, gg, None, None, None, None
 
 
 def _require_cuda(t, what):
@@ -123,22 +166,41 @@ def _require_cuda(t, what):
         raise L.BfmError("%s runs on a HIP device only; there is no CPU fallback in the product path" % what)
 
 
+def _needs_prefilter(prefilter, o, b, shape):
+    """Orders 0 and 1: the prefilter is the identity.  Raises for an axis it would have to filter under 'dst1' / 'dst2'."""
+    if not prefilter or all(k < 2 for k in o):
+        return False
+    _check_prefilter_bounds(o, b, shape)
+    return True
+
+
+def _check_prefilter_bounds(orders, bounds, shape):
+    for o, b, n in zip(orders, bounds, shape):
+        if o > 1 and n > 1 and b not in _PREFILTER_FAMILY:
+            raise NotImplementedError("spline prefilter: no 'dst1' / 'dst2' boundary conditions (the reference has none)")
+
+
 def grid_push(input, grid, shape=None, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):
-    """api.py:203-275: splat `input` (..., [channel], *spatial) at the coordinates `grid` (..., *spatial, 3) into a
-    volume of `shape` (default: the input's spatial shape).  Differentiable w.r.t. input and grid."""
+    """api.py:203-250: splat `input` (..., [channel], *spatial) at the coordinates `grid` (..., *spatial, 3) into a
+    volume of `shape` (default: the input's spatial shape).  Differentiable w.r.t. input and grid.  `prefilter` filters
+    the result, as the reference does."""
+    b, o, ext = _opts(interpolation, bound, extrapolate)
+    shape = tuple(int(v) for v in (shape if shape is not None else input.shape[-3:]))
+    prefilter = _needs_prefilter(prefilter, o, list(b), shape)
     _require_cuda(input, "grid_push")
-    b, ext = _opts(interpolation, bound, extrapolate)
     x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid)
     if in_spatial != grid_spatial:
         raise ValueError("Input and grid should have the same spatial shape")
-    shape = tuple(int(v) for v in (shape if shape is not None else in_spatial))
-    out = _GridPush.apply(x, g, shape, b, ext)
+    out = _GridPush.apply(x, g, shape, b, o, ext)
+    if prefilter:
+        out = spline_coeff_nd(out, interpolation=list(o), bound=bound, dim=3, inplace=True)
     out_channel = [channel] if channel else ([1] if batch else [])
     return out.reshape(*batch, *out_channel, *shape)
 
 
 def grid_count(grid, shape=None, interpolation="linear", bound="zero", extrapolate=False):
-    """api.py:278-340: push of an image of ones (the Jacobian-free 'count' image)."""
+    """api.py:253-287: push of an image of ones (the Jacobian-free 'count' image)."""
+    _opts(interpolation, bound, extrapolate)
     _require_cuda(grid, "grid_count")
     gs = tuple(grid.shape[-4:-1])
     ones = torch.ones(tuple(grid.shape[:-4]) + (1,) + gs, dtype=torch.float32, device=grid.device)
@@ -147,89 +209,82 @@ def grid_count(grid, shape=None, interpolation="linear", bound="zero", extrapola
 
 
 def grid_grad(input, grid, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):
-    """api.py:343-412: spatial gradient of the interpolated image at `grid`: (..., [channel], *spatial_out, 3).
+    """api.py:290-332: spatial gradient of the interpolated image at `grid`: (..., [channel], *spatial_out, 3).
     Forward only (its own backward needs pushgrad / hess, not implemented)."""
+    b, o, ext = _opts(interpolation, bound, extrapolate)
+    prefilter = _needs_prefilter(prefilter, o, list(b), input.shape[-3:])
     _require_cuda(input, "grid_grad")
-    b, ext = _opts(interpolation, bound, extrapolate)
-    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input.detach(), grid.detach())
-    out = _grad_raw(x, g, b, ext)
+    input = input.detach()
+    if prefilter:
+        input = spline_coeff_nd(input, interpolation=list(o), bound=bound, dim=3)
+    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid.detach())
+    out = _grad_raw(x, g, b, o, ext)
     out_channel = [channel] if channel else ([1] if batch else [])
     return out.reshape(*batch, *out_channel, *grid_spatial, 3)
 
 
 def grid_pull(input, grid, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):
-    """Sample `input` at the voxel coordinates in `grid`.
+    """Sample `input` at the voxel coordinates in `grid` (api.py:137-200; an integer image is sampled as values, not label by label).
 
     input: (..., [channel], *spatial) ; grid: (..., *spatial_out, 3).  Returns (..., [channel], *spatial_out).
-    Computes in fp32 like the reference's custom_fwd(cast_inputs=torch.float32)."""
-    orders = interpolation if isinstance(interpolation, (list, tuple)) else [interpolation]
-    if any(_INTER.get(o, o) != 1 for o in orders):
-        raise NotImplementedError("only first-order (linear) interpolation is on the hot path")
-    if prefilter:
-        pass                      # order 1: the spline prefilter is the identity
+    Computes in fp32 like the reference's custom_fwd(cast_inputs=torch.float32).  `prefilter` turns the image into
+    spline coefficients first, so that the result interpolates it."""
+    b, o, ext = _opts(interpolation, bound, extrapolate)
     if grid.shape[-1] != 3:
         raise NotImplementedError("only 3-D grids are on the hot path")
+    prefilter = _needs_prefilter(prefilter, o, list(b), input.shape[-3:])
     if input.device.type != "cuda":
         raise L.BfmError("grid_pull runs on a HIP device only; there is no CPU fallback in the product path")
-    b, ext = _opts(interpolation, bound, extrapolate)
+    if prefilter:
+        input = spline_coeff_nd(input, interpolation=list(o), bound=bound, dim=3)
     x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid)
-    out = _GridPull.apply(x, g, b, ext)                          # differentiable w.r.t. input and grid (first order)
+    out = _GridPull.apply(x, g, b, o, ext)                       # differentiable w.r.t. input and grid (first order)
     out_channel = [channel] if channel else ([1] if batch else [])
     return out.reshape(*batch, *out_channel, *grid_spatial)
 
 
 # ----------------------------------------------------------------------------- resize (SURVEY N4: bspline_zooming)
-_SPLINE_BOUND = {"nearest": 1, "replicate": 1, "repeat": 1, "border": 1, "dct2": 3, "reflect": 3, "reflection": 3,
-                 "neumann": 3, 1: 1, 3: 3}
-
-
 _PREFILTER_CACHE = {}
+_PREFILTER_FAMILY = {1: 0, 3: 0, 0: 1, 2: 1, 6: 2}               # coeff.py:229-251: DCT-II, DCT-I, DFT conditions
+_POLE = {2: 8.0 ** 0.5 - 3.0, 3: 3.0 ** 0.5 - 2.0}                # coeff.py:35-42
 
 
-def _prefilter_scalars_dev(n, dev):
-    """_prefilter_scalars with the fp32 table already on the device, cached per (n, device)."""
-    key = (int(n), str(dev))
+def _prefilter_scalars_dev(n, dev, order=3, family=0):
+    """_prefilter_scalars with the fp32 table already on the device, cached per (n, device, order, family)."""
+    key = (int(n), str(dev), order, family)
     if key not in _PREFILTER_CACHE:
-        z, gain, pole_last, init_scale, final_scale, w = _prefilter_scalars(n)
-        _PREFILTER_CACHE[key] = (z, gain, pole_last, init_scale, final_scale, w.to(dev) if n > 2 else None)
+        sc = _prefilter_scalars(n, order, family)
+        _PREFILTER_CACHE[key] = sc[:5] + (sc[5].to(dev) if sc[5] is not None and n > 2 else None, sc[6])
     return _PREFILTER_CACHE[key]
 
 
-def _prefilter_scalars(n):
-    """The host scalars of coeff.py's cubic DCT-II prefilter for a line of n samples (:55-60, :141-175, :218-226)."""
+def _prefilter_scalars(n, order=3, family=0):
+    """The host scalars of coeff.py's one-pole prefilter (orders 2 and 3) for a line of n samples: (pole, gain,
+    pole_last, init_scale, final_scale, fp32 table or None, max_iter).  family 0: DCT-II (:55-60, :141-175, :216-224);
+    1: DCT-I (:96-140, :207-214); 2: DFT (:69-95, :181-205).  What each scalar means per family: include/brainfm_hip.h."""
     import math
-    z = math.sqrt(3.0) - 2.0
+    z = _POLE[order]
     gain = (1.0 - z) * (1.0 - 1.0 / z)
-    polen = z ** n
-    pole_last = polen * (1 + 1 / (z + polen * polen))
-    init_scale = z / (1 - polen * polen)
-    final_scale = z / (z - 1)
-    zt = torch.as_tensor(z, dtype=torch.float32)
-    w = (zt.pow(torch.arange(1, n - 1, dtype=torch.float32)) +
-         zt.pow(torch.arange(2 * n - 2, n, -1, dtype=torch.float32)))            # fp32 table exactly as the reference builds it
-    return z, gain, pole_last, init_scale, final_scale, w
+    max_iter = int(math.ceil(-30.0 / math.log(abs(z))))
+    if family == 0:
+        polen = z ** n
+        pole_last = polen * (1 + 1 / (z + polen * polen))
+        init_scale = z / (1 - polen * polen)
+        final_scale = z / (z - 1)
+        zt = torch.as_tensor(z, dtype=torch.float32)
+        w = (zt.pow(torch.arange(1, n - 1, dtype=torch.float32)) +
+             zt.pow(torch.arange(2 * n - 2, n, -1, dtype=torch.float32)))        # fp32 table exactly as the reference builds it
+        return z, gain, pole_last, init_scale, final_scale, w, max_iter
+    if family == 1:
+        polen = z ** (n - 1)
+        return z, gain, polen, 1.0 / (1.0 - polen * polen), z / (z * z - 1.0), None, max_iter
+    zm = z ** min(max_iter, n)
+    return z, gain, 0.0, 1.0 / (1.0 - zm), 1.0 / (zm - 1.0), None, max_iter
 
 
-_SPLINE_ORDER = {"nearest": 0, "linear": 1, "quadratic": 2, "cubic": 3, "fourth": 4, "fifth": 5, "sixth": 6, "seventh": 7}
-
-
-def spline_coeff_nd(input, interpolation="linear", bound="dct2", dim=None, inplace=False):
-    """utils/interpol/api.py:386-432 -> coeff.py:315-344 for cubic splines with DCT-II ('nearest' / 'dct2') conditions over
-    the last three dimensions (`dim` None or 3); orders 0 / 1 return the input, as the reference does."""
-    inp = input
-    if inp.device.type != "cuda":
-        raise L.BfmError("spline_coeff_nd runs on a HIP device only")
-    order = interpolation[0] if isinstance(interpolation, (list, tuple)) else interpolation
-    order = _SPLINE_ORDER.get(order.lower(), None) if isinstance(order, str) else int(order)
-    dim = 3 if dim is None else dim
-    if order in (0, 1):
-        return inp if inplace else inp.clone()
-    if order != 3 or dim != 3:
-        raise NotImplementedError("only cubic 3-D prefiltering is implemented")
-    b = bound if isinstance(bound, (str, int)) else bound[0]
-    b = _SPLINE_BOUND.get(b.lower() if isinstance(b, str) else b)
-    if b is None:
-        raise NotImplementedError("spline prefilter: only 'nearest'/'dct2' boundary conditions")
+def _coeff_raw(inp, orders, bounds, inplace):
+    """coeff.py:313-344 over the last three dimensions, one launch per volume and filtered axis (order 2 or 3, length
+    above 1).  Filters `inp` itself only if `inplace` and it is contiguous fp32; returns fp32."""
     lead = inp.shape[:-3]
     vols = inp.to(torch.float32).reshape((-1,) + tuple(inp.shape[-3:])).contiguous()
     if not inplace or vols.data_ptr() != inp.data_ptr():
@@ -238,12 +293,49 @@ def spline_coeff_nd(input, interpolation="linear", bound="dct2", dim=None, inpla
     nx, ny, nz = vols.shape[-3:]
     for v in vols:
         for axis, n in enumerate((nx, ny, nz)):
-            if n == 1:
+            if n == 1 or orders[axis] < 2:
                 continue
-            z, gain, pole_last, init_scale, final_scale, wd = _prefilter_scalars_dev(n, inp.device)
-            L.check(lib.bfm_bspline3_prefilter_axis(L.ptr(v), nx, ny, nz, axis, b, z, gain, L.ptr(wd), pole_last,
-                                                    init_scale, final_scale, L.stream_ptr()), "bspline3_prefilter")
+            z, gain, pole_last, init_scale, final_scale, wd, max_iter = _prefilter_scalars_dev(
+                n, inp.device, orders[axis], _PREFILTER_FAMILY[bounds[axis]])
+            L.check(lib.bfm_bspline3_prefilter_axis(L.ptr(v), nx, ny, nz, axis, bounds[axis], z, gain, L.ptr(wd), pole_last,
+                                                    init_scale, final_scale, max_iter, L.stream_ptr()), "bspline3_prefilter")
     return vols.reshape(tuple(lead) + (nx, ny, nz))
+
+
+class _SplineCoeffND(torch.autograd.Function):
+    """autograd.py:276-300: the filter is symmetric, so its backward is the same filter applied to the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, orders, bounds):
+        ctx.opt = (orders, bounds, x.dtype)
+        return _coeff_raw(x, orders, bounds, False)
+
+    @staticmethod
+    def backward(ctx, grad):
+        orders, bounds, dtype = ctx.opt
+        return _coeff_raw(grad.contiguous(), orders, bounds, False).to(dtype), None, None
+
+
+def spline_coeff_nd(input, interpolation="linear", bound="dct2", dim=None, inplace=False):
+    """utils/interpol/api.py:386-432 -> coeff.py:313-344 over the last three dimensions (`dim` None or 3): orders 2 and 3,
+    per axis if given as a list, under the DCT-I ('zero' / 'dct1'), DCT-II ('nearest' / 'dct2') or DFT ('dft') conditions;
+    an axis of order 0 / 1 or of length 1 is left as it is.  Differentiable (autograd.py:276-300); `inplace` holds only
+    for a tensor that needs no gradient."""
+    inp = input
+    orders = _order_list(interpolation)
+    bounds = tuple(_bound_list(bound))
+    dim = 3 if dim is None else dim
+    if dim == 3:
+        _check_prefilter_bounds(orders, bounds, inp.shape[-3:])
+    if inp.device.type != "cuda":
+        raise L.BfmError("spline_coeff_nd runs on a HIP device only")
+    if all(o < 2 for o in orders):
+        return inp if inplace else inp.clone()
+    if dim != 3:
+        raise NotImplementedError("only 3-D prefiltering is implemented")
+    if torch.is_grad_enabled() and inp.requires_grad:
+        return _SplineCoeffND.apply(inp, orders, bounds)
+    return _coeff_raw(inp, orders, bounds, inplace)
 
 
 def _make_list(x, n=None):
@@ -254,8 +346,10 @@ def _make_list(x, n=None):
 
 
 def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilter=True, **kwargs):
-    """utils/interpol/resize.py:13-119.  image: (..., X, Y, Z).  Cubic (interpolation=3) runs as prefilter + three
-    separable 4-tap passes; linear builds the grid and goes through grid_pull like the reference."""
+    """utils/interpol/resize.py:13-119.  image: (..., X, Y, Z).  Cubic (interpolation=3) with extrapolation under the
+    'nearest' / 'dct2' bounds runs as prefilter + three separable 4-tap passes; every other case (orders 0 to 3, any
+    bound, extrapolate=False) builds the grid and goes through grid_pull like the reference."""
+    orders = _order_list(kwargs.get("interpolation", interpolation))
     if image.device.type != "cuda":
         raise L.BfmError("resize runs on a HIP device only; there is no CPU fallback in the product path")
     factor = _make_list(factor) if factor else []
@@ -292,19 +386,17 @@ def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilte
         else:
             raise ValueError("Unknown anchor {}".format(anch))
     bound = kwargs.get("bound", "nearest")
-    order = kwargs.get("interpolation", interpolation)
     prefilter = kwargs.get("prefilter", prefilter)
-    if order in (1, "linear"):
+    if orders == _LINEAR:
         grid = torch.stack(torch.meshgrid(*[v.to(image.device) for v in lin], indexing="ij"), dim=-1)
         return grid_pull(image, grid, interpolation=1, bound=bound, extrapolate=kwargs.get("extrapolate", True))
-    if order not in (3, "cubic"):
-        raise NotImplementedError("resize: interpolation orders 1 and 3 are implemented")
-    if not kwargs.get("extrapolate", True):
-        raise NotImplementedError("resize: cubic path assumes extrapolate=True (the reference default here)")
-    b = bound if isinstance(bound, (str, int)) else bound[0]
-    b = _SPLINE_BOUND.get(b.lower() if isinstance(b, str) else b)
-    if b is None:
-        raise NotImplementedError("resize: cubic path supports 'nearest'/'dct2' bounds")
+    bl = _bound_list(bound)
+    b = bl[0] if bl[0] in (1, 3) and bl == [bl[0]] * 3 else None           # the separable path: 'nearest' / 'dct2'
+    if orders != (3, 3, 3) or not kwargs.get("extrapolate", True) or b is None:
+        # every case but the separable cubic one: build the grid and pull, like the reference (resize.py:111-117)
+        grid = torch.stack(torch.meshgrid(*[v.to(image.device) for v in lin], indexing="ij"), dim=-1)
+        return grid_pull(image, grid, interpolation=list(orders), bound=bound,
+                         extrapolate=kwargs.get("extrapolate", True), prefilter=prefilter)
     coeff = spline_coeff_nd(image, interpolation=3, bound=b, dim=3) if prefilter else image.to(torch.float32)
     lead = coeff.shape[:-3]
     vols = coeff.reshape((-1,) + tuple(coeff.shape[-3:])).contiguous()

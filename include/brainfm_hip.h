@@ -589,10 +589,17 @@ int bfm_mean_lastdim(const float* in, int64_t n, int c, float* out, bfm_stream_t
  * prefilter: bound 1 ('nearest') or 3 ('dct2') -> DCT-II conditions; the host passes the scalars the reference derives
  * from the pole z = sqrt(3)-2 (gain (1-z)(1-1/z), pole_last, init_scale z/(1-z^2n), final_scale z/(z-1)) and the
  * fp32 table init_w[i-1] = z^i + z^(2n-1-i), i = 1..n-2.  resample: out[o] = sum of 4 cubic B-spline taps around
- * coord[o] (fp32 source coordinates of the output samples along `axis`), indices reflected (3) or clamped (1). */
+ * coord[o] (fp32 source coordinates of the output samples along `axis`), indices reflected (3) or clamped (1).
+ * The prefilter also serves interpol.spline_coeff_nd for order 2 (pole sqrt(8)-3, coeff.py:35-57) and the other two
+ * families of conditions the reference has (coeff.py:229-251); max_iter = ceil(-30 / log|z|) (coeff.py:72, :99):
+ *   bound 0 ('zero') or 2 ('dct1') -> DCT-I (coeff.py:96-140, 207-214): pole_last = z^(n-1),
+ *     init_scale = 1/(1-z^(2n-2)) (used when max_iter >= n), final_scale = z/(z^2-1); init_w unused;
+ *   bound 6 ('dft') -> DFT (coeff.py:69-95, 181-205): with m = min(max_iter, n), init_scale = 1/(1-z^m),
+ *     final_scale = 1/(z^m-1); init_w and pole_last unused.
+ * bound 4 / 5 ('dst1' / 'dst2') -> BFM_E_SHAPE: the reference has no prefilter for them. */
 int bfm_bspline3_prefilter_axis(float* vol, int nx, int ny, int nz, int axis, int bound, float pole, float gain,
                                 const float* init_w, float pole_last, float init_scale, float final_scale,
-                                bfm_stream_t stream);
+                                int max_iter, bfm_stream_t stream);
 int bfm_bspline3_resample_axis(const float* in, int nx, int ny, int nz, int axis, const float* coord, int n_out,
                                int bound, float* out, bfm_stream_t stream);
 
@@ -601,6 +608,21 @@ int bfm_bspline3_resample_axis(const float* in, int nx, int ny, int nz, int axis
  * (zero, replicate, dct1, dct2, dst1, dst2, dft -- bounds.py:8-15); extrapolate 0 no / 1 yes / 2 hist. */
 int bfm_grid_pull3d_linear(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox,
                            int oy, int oz, const int* bound, int extrapolate, float* out, bfm_stream_t stream);
+/* interpol.grid_pull / grid_push / grid_grad for spline orders 0 to 3, any order per axis -> nd.pull / nd.push /
+ * nd.grad -- utils/interpol/nd.py:30-290, splines.py:30-43 and :90-103, bounds.py:24-89.  The arguments of the _linear
+ * exports plus order[3], each 0..3 (BFM_E_ARG otherwise): per axis grid0 = floor(g - (order-1)/2), node k in 0..order
+ * at bound_index(grid0+k) with bound_sign(grid0+k) and weight fastweight(g - grid0 - k); grad takes fastgrad on its
+ * own axis.  push: out MUST be zero on entry (fp32 atomics).  order {1,1,1} follows nd.py here, whose gradient on a
+ * linear axis has the sign of splines.py:93-97; the _linear exports follow iso1.py. */
+int bfm_grid_pull3d_spline(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox,
+                           int oy, int oz, const int* bound, const int* order, int extrapolate, float* out,
+                           bfm_stream_t stream);
+int bfm_grid_push3d_spline(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg, int nx,
+                           int ny, int nz, const int* bound, const int* order, int extrapolate, float* out_zeroed,
+                           bfm_stream_t stream);
+int bfm_grid_grad3d_spline(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox,
+                           int oy, int oz, const int* bound, const int* order, int extrapolate, float* out,
+                           bfm_stream_t stream);
 /* BaseGen.deform_grid -- Generator/datasets.py:264-303: (xc+F) -> A*. + c2, clamp to the source shape, and the
  * six global min/max (minmax = {min x,y,z, max x,y,z}, device).  F is [n][3] or NULL. */
 size_t bfm_deform_grid_workspace(int sx, int sy, int sz);
