@@ -1,8 +1,10 @@
 """Host-side mirror of ``utils/interpol`` (vendored torch-interpol): ``grid_pull`` / ``grid_push`` / ``grid_count`` /
 ``grid_grad`` for spline orders 0 to 3, any order per axis, in 3-D (utils/interpol/api.py:137-335, autograd.py:125-245,
-pushpull.py:35-282).  All-linear calls run ``iso1`` (iso1.py:28-387) on the kernels of synth_interp.hip; every other
-combination runs the generic path (nd.py:30-290, splines.py:30-103, bounds.py:24-89) on spline_grid.hip.  ``prefilter``
-goes through ``spline_coeff_nd`` (coeff.py:254-344), which is differentiable (autograd.py:276-300).
+pushpull.py:35-282), ``resize`` (resize.py:13-119) and ``restrict`` (restrict.py:9-122; separable axis passes on
+restrict.hip, which also give the separable cubic ``resize`` its gradient).  All-linear calls run ``iso1``
+(iso1.py:28-387) on the kernels of synth_interp.hip; every other combination runs the generic path (nd.py:30-290,
+splines.py:30-103, bounds.py:24-89) on spline_grid.hip.  ``prefilter`` goes through ``spline_coeff_nd``
+(coeff.py:254-344), which is differentiable (autograd.py:276-300).
 
 grid_pull / grid_push are differentiable to first order through grid_push / grid_grad; grid_grad itself
 is forward only.
@@ -400,19 +402,164 @@ def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilte
     coeff = spline_coeff_nd(image, interpolation=3, bound=b, dim=3) if prefilter else image.to(torch.float32)
     lead = coeff.shape[:-3]
     vols = coeff.reshape((-1,) + tuple(coeff.shape[-3:])).contiguous()
-    lib = L.load()
-    coords = [v.to(image.device) for v in lin]
-    outs = []
-    for v in vols:
-        cur = v
-        dims = list(v.shape)
-        for axis in range(3):
-            nxt_dims = list(dims)
-            nxt_dims[axis] = shape[axis]
-            nxt = torch.empty(nxt_dims, dtype=torch.float32, device=image.device)
-            L.check(lib.bfm_bspline3_resample_axis(L.ptr(cur), dims[0], dims[1], dims[2], axis, L.ptr(coords[axis]),
-                                                   shape[axis], b, L.ptr(nxt), L.stream_ptr()), "bspline3_resample")
-            cur, dims = nxt, nxt_dims
-        outs.append(cur)
-    out = torch.stack(outs, 0) if len(outs) > 1 else outs[0][None]
+    out = _ResizeCubic.apply(vols, [v.to(image.device) for v in lin], tuple(shape), b)
     return out.reshape(tuple(lead) + tuple(shape))
+
+
+class _ResizeCubic(torch.autograd.Function):
+    """The separable cubic route of resize: three 4-tap passes per volume (spline.hip).  Its backward is the transposed
+    operator of each axis (restrict.hip) applied in reverse axis order, all volumes in one launch per axis."""
+
+    @staticmethod
+    def forward(ctx, vols, coords, shape, b):
+        ctx.opt = (coords, tuple(vols.shape[1:]), b)
+        lib = L.load()
+        outs = []
+        for v in vols:
+            cur = v
+            dims = list(v.shape)
+            for axis in range(3):
+                nxt_dims = list(dims)
+                nxt_dims[axis] = shape[axis]
+                nxt = torch.empty(nxt_dims, dtype=torch.float32, device=vols.device)
+                L.check(lib.bfm_bspline3_resample_axis(L.ptr(cur), dims[0], dims[1], dims[2], axis, L.ptr(coords[axis]),
+                                                       shape[axis], b, L.ptr(nxt), L.stream_ptr()), "bspline3_resample")
+                cur, dims = nxt, nxt_dims
+            outs.append(cur)
+        return torch.stack(outs, 0) if len(outs) > 1 else outs[0][None]
+
+    @staticmethod
+    def backward(ctx, grad):
+        coords, inshape, b = ctx.opt
+        cur = grad.contiguous().to(torch.float32)
+        for axis in (2, 1, 0):
+            cur = _axis_pass(cur, axis, _axis_table(coords[axis], inshape[axis], 3, b, 1, True))
+        return cur, None, None, None
+
+
+# ----------------------------------------------------------------------------- separable axis operators (restrict.hip)
+def _axis_table(coord, n, order, bound, ext, transpose, ties_even=False):
+    """The sparse operator of the fp32 device coordinates `coord` against an axis of n nodes as a CSR table (rowptr, col,
+    val, rows): rows = len(coord) in the pull direction, n in the transposed (push) direction.  ties_even: the node of
+    an order-0 axis is round(coord) as in iso0.py, not floor(coord + 0.5)."""
+    lib = L.load()
+    m = coord.numel()
+    rows = n if transpose else m
+    rowptr = torch.empty(rows + 1, dtype=torch.int32, device=coord.device)
+    col = torch.empty(m * (order + 1), dtype=torch.int32, device=coord.device)
+    val = torch.empty(m * (order + 1), dtype=torch.float32, device=coord.device)
+    nbytes = lib.bfm_spline_axis_table_workspace(m, n, order) if transpose else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=coord.device) if transpose else None
+    L.check(lib.bfm_spline_axis_table(L.ptr(coord), m, n, order, bound, ext, int(ties_even), int(transpose), L.ptr(rowptr),
+                                      L.ptr(col), L.ptr(val), L.ptr(ws), nbytes, L.stream_ptr()), "spline_axis_table")
+    return rowptr, col, val, rows
+
+
+def _axis_pass(x, axis, table):
+    """x (lead, X, Y, Z) contiguous fp32 -> the same block with `axis` (0, 1, 2) mapped through `table`."""
+    rowptr, col, val, rows = table
+    dims = list(x.shape)
+    out_dims = list(dims)
+    out_dims[axis + 1] = rows
+    out = torch.empty(out_dims, dtype=torch.float32, device=x.device)
+    if out.numel():
+        L.check(L.load().bfm_spline_axis_pass(L.ptr(x), dims[0], dims[1], dims[2], dims[3], axis, L.ptr(rowptr), L.ptr(col),
+                                              L.ptr(val), rows, L.ptr(out), L.stream_ptr()), "spline_axis_pass")
+    return out
+
+
+class _SeparablePush(torch.autograd.Function):
+    """grid_push on the meshgrid of three coordinate lists as three transposed axis passes, x then y then z (the order is
+    part of the result: it fixes the last bit).  Backward: the pull-direction passes of the same coordinates, z, y, x."""
+
+    @staticmethod
+    def forward(ctx, x, coords, shape, orders, bounds, ext):
+        ctx.opt = (coords, shape, orders, bounds, ext)
+        cur = x
+        iso0 = orders == (0, 0, 0)                   # the reference then takes iso0.py, which rounds ties to even
+        for axis in (0, 1, 2):
+            cur = _axis_pass(cur, axis, _axis_table(coords[axis], shape[axis], orders[axis], bounds[axis], ext, True, iso0))
+        return cur
+
+    @staticmethod
+    def backward(ctx, grad):
+        coords, shape, orders, bounds, ext = ctx.opt
+        cur = grad.contiguous().to(torch.float32)
+        iso0 = orders == (0, 0, 0)
+        for axis in (2, 1, 0):
+            cur = _axis_pass(cur, axis, _axis_table(coords[axis], shape[axis], orders[axis], bounds[axis], ext, False, iso0))
+        return cur, None, None, None, None, None
+
+
+def _restrict_geometry(image_shape, factor=None, shape=None, anchor="c"):
+    """restrict.py:66-110 as it stands: (output shape, fp32 host coordinates of the input samples in the output lattice,
+    one list per axis, fullscale).  Anchor 'c' with an output axis of length 1 divides by zero, as there."""
+    factor = _make_list(factor) if factor else []
+    shape = _make_list(shape) if shape else []
+    anchor = _make_list(anchor)
+    nb_dim = max(len(factor), len(shape), len(anchor)) or (len(image_shape) - 2)
+    if nb_dim != 3:
+        raise NotImplementedError("only 3-D restrict is implemented (factor, shape and anchor set the number of "
+                                  "dimensions: %d here)" % nb_dim)
+    anchor = [a[0].lower() for a in _make_list(anchor, nb_dim)]
+    inshape = tuple(image_shape[-nb_dim:])
+    if factor:
+        factor = _make_list(factor, nb_dim)
+    elif not shape:
+        raise ValueError("One of `factor` or `shape` must be provided")
+    if shape:
+        shape = _make_list(shape, nb_dim)
+    else:
+        shape = [int(i / f) for i, f in zip(inshape, factor)]
+    if not factor:
+        factor = [i / o for o, i in zip(shape, inshape)]
+    lin = []
+    fullscale = 1
+    for anch, f, inshp, outshp in zip(anchor, factor, inshape, shape):         # fp32 on the host: same values as torch CPU
+        if anch == "c":
+            lin.append(torch.linspace(0, outshp - 1, inshp, dtype=torch.float32))
+            fullscale *= (inshp - 1) / (outshp - 1)
+        elif anch == "e":
+            scale = outshp / inshp
+            shift = 0.5 * (scale - 1)
+            fullscale *= scale
+            lin.append(torch.arange(0., inshp, dtype=torch.float32) * scale + shift)
+        elif anch == "f":
+            fullscale *= 1 / f
+            lin.append(torch.arange(0., inshp, dtype=torch.float32) / f)
+        elif anch == "l":
+            shift = (outshp - 1) - (inshp - 1) / f
+            fullscale *= 1 / f
+            lin.append(torch.arange(0., inshp, dtype=torch.float32) / f + shift)
+        else:
+            raise ValueError("Unknown anchor {}".format(anch))
+    return tuple(int(v) for v in shape), lin, fullscale
+
+
+def restrict(image, factor=None, shape=None, anchor="c", interpolation=1, reduce_sum=False, **kwargs):
+    """utils/interpol/restrict.py:9-122, the adjoint of resize: image (..., X, Y, Z) is splatted onto the coarser lattice
+    of `shape` (or int(in / factor)) and divided by `fullscale` unless `reduce_sum`.  kwargs: bound ('nearest'),
+    extrapolate (True), interpolation (overrides the argument), prefilter (False; filters the result, like grid_push).
+    Orders 0 to 3 per axis, all seven bounds.  The grid is separable, so the push runs as three axis passes without
+    atomics (x, then y, then z): deterministic, and differentiable to first order in `image`.  Returns fp32."""
+    unknown = sorted(set(kwargs) - {"bound", "extrapolate", "interpolation", "prefilter"})
+    if unknown:
+        raise TypeError("grid_push() got an unexpected keyword argument '%s'" % unknown[0])
+    orders = _order_list(kwargs.get("interpolation", interpolation))
+    shape, lin, fullscale = _restrict_geometry(tuple(image.shape), factor, shape, anchor)
+    bound = kwargs.get("bound", "nearest")
+    b = _bound_list(bound)
+    extrapolate = kwargs.get("extrapolate", True)
+    ext = int({False: 0, True: 1, "no": 0, "yes": 1, "hist": 2}.get(extrapolate, extrapolate))
+    if any(not 0 <= v <= 6 for v in b) or not 0 <= ext <= 2:
+        raise ValueError("Unknown bound or extrapolate value")
+    prefilter = _needs_prefilter(kwargs.get("prefilter", False), orders, b, shape)
+    _require_cuda(image, "restrict")
+    lead = tuple(image.shape[:-3])
+    x = image.to(torch.float32).reshape((-1,) + tuple(image.shape[-3:])).contiguous()
+    out = _SeparablePush.apply(x, [v.to(image.device) for v in lin], shape, orders, tuple(b), ext)
+    if prefilter:
+        out = spline_coeff_nd(out, interpolation=list(orders), bound=bound, dim=3, inplace=True)
+    if not reduce_sum:
+        out = out.div_(fullscale)
+    return out.reshape(lead + shape)

@@ -623,6 +623,29 @@ int bfm_grid_push3d_spline(const float* inp, int Bi, int C, int ix, int iy, int 
 int bfm_grid_grad3d_spline(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox,
                            int oy, int oz, const int* bound, const int* order, int extrapolate, float* out,
                            bfm_stream_t stream);
+/* interpol.restrict -- utils/interpol/restrict.py:9-122 (grid_push, nd.py:148-214, on torch.stack(meshgrid_ij(*lin))) --
+ * and the backward of the separable cubic interpol.resize, as per-axis sparse operators.  A separable grid has one
+ * coordinate list per axis, so the (order+1)^3 taps of nd.py factor into three axis passes.
+ * axis_table: the operator of coord[m] (fp32, device) against an axis of n nodes as a CSR table: coordinate i touches
+ *   node k = 0..order at bound_index(g0+k) with value fastweight(g - g0 - k) * bound_sign(g0+k) * mask_i, the nodes and
+ *   the inbounds mask of the _spline exports above, the mask taken against this axis alone.  transpose 0 (pull
+ *   direction): m rows of order+1 entries, rowptr[m+1].  transpose 1 (push direction): n rows, rowptr[n+1], the entries
+ *   of a row in ascending (i, k), entries that are exactly 0 left out.  col / val hold m * (order+1) entries either way;
+ *   the transposed build needs bfm_spline_axis_table_workspace bytes (BFM_E_WORKSPACE otherwise).
+ *   ties_even 1 (order 0 only; 0 / 1, BFM_E_ARG otherwise): the node is round(g) with a tie to the even node, what
+ *   iso0.py:12 computes when all three orders of a call are 0, instead of floor(g + 0.5) of nd.py:45.
+ *   order 0..3, bound 0..6, extrapolate 0..2 (BFM_E_ARG otherwise); m, n <= 2^24 (BFM_E_SHAPE otherwise).
+ * axis_pass: in (lead,nx,ny,nz) -> out with the length of `axis` replaced by n_out, all lead volumes in one launch:
+ *   out[.., r, ..] = sum over e in rowptr[r]..rowptr[r+1]-1, ascending, of val[e] * in[.., col[e], ..].  Every element
+ *   of out is written (an empty row gives 0), nothing is added atomically, and the result does not depend on the run.
+ *   The table must come from axis_table with n = the length of `axis` (pull: n_out = m; transposed: the table's m is
+ *   the length of `axis` and n_out its n): col is not checked on the device. */
+size_t bfm_spline_axis_table_workspace(int m, int n, int order);
+int bfm_spline_axis_table(const float* coord, int m, int n, int order, int bound, int extrapolate, int ties_even,
+                          int transpose, int32_t* rowptr, int32_t* col, float* val, void* workspace,
+                          size_t workspace_bytes, bfm_stream_t stream);
+int bfm_spline_axis_pass(const float* in, int64_t lead, int nx, int ny, int nz, int axis, const int32_t* rowptr,
+                         const int32_t* col, const float* val, int n_out, float* out, bfm_stream_t stream);
 /* BaseGen.deform_grid -- Generator/datasets.py:264-303: (xc+F) -> A*. + c2, clamp to the source shape, and the
  * six global min/max (minmax = {min x,y,z, max x,y,z}, device).  F is [n][3] or NULL. */
 size_t bfm_deform_grid_workspace(int sx, int sy, int sz);
