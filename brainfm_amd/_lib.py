@@ -140,6 +140,11 @@ SIGNATURES = {
     "bfm_conv3x3x3_wino4_uniform": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P]),
     "bfm_conv3x3x3_wino4": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _P]),
     "bfm_conv3x3x3_wino4_batch": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _I, _P]),
+    "bfm_conv3x3x3_wino_b5_rows": (_I, [_I, _I, _I, _I]),
+    "bfm_conv3x3x3_wino_b5_splitk": (_I, [_I, _I, _I, _I, _I]),
+    "bfm_conv3x3x3_wino_b5_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "bfm_conv3x3x3_wino_b5_batch": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _I, _P, _Z,
+                                         _P]),
     "bfm_conv3x3x3_wino4_masked": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _P, _Z, _P]),
     "bfm_permute_flip3d": (_I, [_P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _P, _P]),
     "bfm_bbox_nonzero": (_I, [_P, _I, _I, _I, _F, _P, _P]),

@@ -58,7 +58,8 @@ def tap_row_table(lo, hi):
 
 _TUNE_CHOICES = {}          # (device, passes, shape key) -> conv variant that won UNetEngine._autotune in this process
 
-# The conv variants (cfg[6]): 0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino F(2,3), 4 conv_wino4 F(4,3).  Per variant
+# The conv variants (cfg[6]): 0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino F(2,3), 4 conv_wino4 F(4,3),
+# 5 conv_wino_b5 (F(2,3) on 5 x 5 x 10 boxes, split K; the batched levels only).  Per variant
 # the packed-weight layout and its packer; for the two Winograd families also the entry points that exist once per family
 # with one C signature (_lib.SIGNATURES).  Names here; UNetEngine._variant binds them to the library once per engine.
 _Variant = namedtuple("_Variant", "layout pack_bytes pack rows box dense masked_workspace masked uniform_scratch uniform",
@@ -74,8 +75,13 @@ _CONV_VARIANTS = (
     _Variant("wino4", "bfm_pack_conv_weights_wino4_bytes", "bfm_pack_conv_weights_wino4", "bfm_conv3x3x3_wino4_rows",
              "bfm_conv3x3x3_wino4_box", "bfm_conv3x3x3_wino4", "bfm_conv3x3x3_wino4_masked_workspace",
              "bfm_conv3x3x3_wino4_masked", "bfm_conv3x3x3_wino4_uniform_scratch", "bfm_conv3x3x3_wino4_uniform"),
+    # 5: conv_wino_b5, F(2,3) on 5 x 5 x 10 boxes with a split K loop -- conv_wino's pack; the batched levels only
+    # (UNetEngine._batch_launch), one moment row per box
+    _Variant("wino", "bfm_pack_conv_weights_wino_bytes", "bfm_pack_conv_weights_wino", "bfm_conv3x3x3_wino_b5_rows"),
 )
-_VARIANT_OF = {v.layout: ver for ver, v in enumerate(_CONV_VARIANTS)}      # packed-weight layout -> a variant that reads it
+_VARIANT_OF = {}                                        # packed-weight layout -> the first variant that reads it
+for _ver, _v in enumerate(_CONV_VARIANTS):
+    _VARIANT_OF.setdefault(_v.layout, _ver)
 
 # The persisted tune table: the variants agree to ~1e-6, not bit for bit, so a choice made by timing would let two
 # processes flip different argmax ties of the same volume.  brainfm_amd/conv_tune_gfx950.json (next to the .so, tracked)
@@ -134,8 +140,9 @@ def _tune_store(dev_index, passes, key, ver):
                 disk = {}
         for sct, tab in _tune_table().items():
             disk.setdefault(sct, {}).update(tab)
-        doc = {"about": "conv variant per layer shape (0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino, 4 conv_wino4); key = "
-                        "cin,cout,D,H,W,two_sources,accumulate[,samples]; written by UNetEngine._autotune under "
+        doc = {"about": "conv variant per layer shape (0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino, 4 conv_wino4, "
+                        "5 conv_wino_b5); key = cin,cout,D,H,W,two_sources,accumulate[,1 = batched levels[,5 = with "
+                        "conv_wino_b5 admitted]]; written by UNetEngine._autotune under "
                         "BFM_CONV_TUNE_SAVE=1 (scripts/make_tune_table.py)",
                "choices": {k: dict(sorted(v.items())) for k, v in sorted(disk.items())}}
         tmp = "%s.%d.tmp" % (TUNE_FILE, os.getpid())
@@ -461,11 +468,14 @@ class UNetEngine:
             L.check(self.lib.bfm_conv3x3x3_mfma_plan(cin, cout, dims[0], dims[1], dims[2], cfg), "mfma_plan")
             if two_src and cfg[6] in (3, 4):                        # BFM_CONV_VER=3/4: Winograd takes one source
                 cfg[6] = 0
+            if cfg[6] == 5:                                         # BFM_CONV_VER=5: conv_wino_b5 runs the batched levels only
+                cfg[6] = 0
             self._plan_cache[key] = cfg
         return self._plan_cache[key]
 
     def _autotune(self, ly, key, launch, vers=None):
-        """Pick the fastest conv variant (0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino, 4 conv_wino4) for this
+        """Pick the fastest conv variant (0 conv_mfma, 1 conv_mfma_ws, 2 conv_mfma16, 3 conv_wino, 4 conv_wino4; 5
+        conv_wino_b5 only where _deep_b5 puts it up against a batched layer's present variant) for this
         (Cin, Cout, dims, two-source) by timing them once on the real operands (HIP events on the launch stream).  All variants compute the same result; the chip is
         power-limited on this kernel, so which one wins is shape dependent (profiles/).  BFM_CONV_VER pins one."""
         cfg = self._plan_cache[key]
@@ -497,8 +507,9 @@ class UNetEngine:
         if hasattr(self, "enc") and self._needs_f23(ly):
             single = (0, 1, 2, 3)                               # these layers never run F(4,3): do not let it win their entry
         for ver in (vers if vers is not None else ((0, 1, 2) if key[3] else single)):
-            if ver == 4 and 4 not in single:
+            if ver == 4 and 4 not in single and cfg[6] != 4:
                 continue                                        # F(4,3) is timed when the table is made, never in-process
+                                                                # (unless the plan runs it already: _deep_b5's yardstick)
             trial = (C.c_int * 8)(*list(cfg))
             trial[6] = ver
             try:
@@ -519,6 +530,8 @@ class UNetEngine:
                 continue
             if ver == 4:
                 ms = ms / 0.97                                  # F(4,3) pays in rounding: it must win by 3 % to be taken
+            if ver == 5:
+                ms = ms / 0.97                                  # conv_wino_b5 displaces a present variant: not on a tie
             if best_ms is None or ms < best_ms:
                 best, best_ms = ver, ms
         cfg[6] = best
@@ -1011,6 +1024,12 @@ class UNetEngine:
     # per sample the bits of bfm_conv3x3x3_wino4) where the committed tune table says so -- the level-2 layers of the
     # 160 x 80 x 80-class tiles were 250-workgroup launches at half the kernel's rate, four of them per shape
     DEEP_VERS_1SRC = (0, 2, 4)
+    # Volumes that boxes of 5 x 5 x 10 divide (an 80-wide tile from level 2 down: 20 / 10 wide) may also run conv_wino_b5
+    # (variant 5: F(2,3), 18 of 27 tap-rows, split K) where the committed tune table says so.  Eligibility goes by the
+    # per-sample dims alone (_deep_b5).  It is admitted beside DEEP_VERS_1SRC, not inside it: its choice against the key's
+    # present variant is a table entry of its own, so that switching it off finds the entries above as they were.
+    # BFM_WINO_B5=0: the routes without it; =force: every eligible layer takes it.
+    use_wino_b5 = os.environ.get("BFM_WINO_B5", "1")
     deep_upfold = os.environ.get("BFM_DEEP_UPFOLD", "1") != "0"          # fold exact 2x upsamples inside the region too
     deep_upfold_min = int(os.environ.get("BFM_DEEP_UPFOLD_MIN", "100"))  # fewest low-res voxels per sample worth it
     # The smallest levels (2^3, 5 x 2 x 2, 5 x 5 x 2 voxels per sample) as tap-wise GEMMs over the batch's densely packed
@@ -1113,6 +1132,8 @@ class UNetEngine:
             cfg = self._autotune(ly, key, lambda c: self._batch_launch(ly, c, A[0:1], B[0:1] if B is not None else None, upp, dims,
                                                                        scale[0:1], shift[0:1], bound[0:1], out[0:1]),
                                  vers=vers)
+        if B is None:
+            cfg = self._deep_b5(ly, key, cfg, A, dims, scale, shift, bound)
         self._pack(ly, True, cfg[6])
         rows = self._rows_for(ly.cin, ly.cout, dims, cfg, S)
         nv = D * H * W
@@ -1138,14 +1159,55 @@ class UNetEngine:
             self._plan_cache[key] = cfg
         return self._plan_cache[key]
 
+    B5_TUNE_S = 4                                          # samples in the batch that times conv_wino_b5 against the present variant
+
+    def _deep_b5(self, ly, key, cfg, A, dims, scale, shift, bound):
+        """The plan of a single-source layer of the batched levels once conv_wino_b5 (variant 5) is admitted: `cfg` (the
+        variant the layer runs without it, plan key `key`) or a copy with variant 5.  Admitted where boxes of 5 x 5 x 10
+        divide the per-sample volume -- by the layer's shape alone, never by S.  The choice between the two is an entry of
+        its own in the tune table (key + (5,)), so that BFM_WINO_B5=0 finds the table's earlier entries as they were.  A
+        shape outside the table times the two on B5_TUNE_S copies of the first sample, whatever S is: these layers run
+        batched (x2 .. x8 in the tile flows), and on one sample both are bound by their launches (two kernels against
+        one or two), which says little about the batch."""
+        if self.use_wino_b5 == "0" or key[3]:
+            return cfg
+        trial = []
+
+        def launch(c):
+            if not trial:                                   # made only when something is timed
+                n = self.B5_TUNE_S
+                trial.extend(t[0:1].expand((n,) + tuple(t.shape[1:])).contiguous() for t in (A, scale, shift, bound))
+                trial.append(torch.zeros((n,) + tuple(dims) + (ly.cout,), dtype=torch.float32, device=self.device))
+            self._batch_launch(ly, c, trial[0], None, None, dims, trial[1], trial[2], trial[3], trial[4])
+        key5 = key + (5,)
+        if key5 not in self._plan_cache:
+            ok = self.lib.bfm_conv3x3x3_wino_b5_splitk(key[0], key[1], key[2][0], key[2][1], key[2][2]) > 0
+            self._plan_cache[key5] = (C.c_int * 8)(*list(cfg)) if ok else None
+        cfg5 = self._plan_cache[key5]
+        if cfg5 is None:
+            return cfg
+        if self.use_wino_b5 == "force" or os.environ.get("BFM_CONV_VER") == "5":
+            cfg5[6] = 5
+        elif key5 not in self._tuned:
+            cfg5 = self._autotune(ly, key5, launch, vers=(cfg[6], 5))
+        return cfg5
+
     def _batch_launch(self, ly, cfg, A, B, upp, dims, scale, shift, bound, out, rows=None, aff=0):
-        """One launch of `ly` on the batch A (S,D,H,W,CA) [+ B]: conv_wino4d on the batch (cfg[6] == 4, one source) or
-        bfm_conv3x3x3_mfma_batch.  cfg[7] bit 0: accumulate onto `out`; aff: pitch of the rows of scale / shift when they
-        are column windows of wider tables (0: ly.cin)."""
+        """One launch of `ly` on the batch A (S,D,H,W,CA) [+ B]: conv_wino4d on the batch (cfg[6] == 4, one source),
+        conv_wino_b5 (cfg[6] == 5, one source) or bfm_conv3x3x3_mfma_batch.  cfg[7] bit 0: accumulate onto `out`; aff: pitch
+        of the rows of scale / shift when they are column windows of wider tables (0: ly.cin)."""
         S, (D, H, W), ca = A.shape[0], dims, A.shape[-1]
         cb = 0 if B is None else B.shape[-1]
         st = L.stream_ptr()
         self._pack(ly, True, cfg[6])
+        if cfg[6] == 5:
+            ws = self._workspace(self.lib.bfm_conv3x3x3_wino_b5_workspace(ca, ly.cout, S, D, H, W))
+            L.check(self.lib.bfm_conv3x3x3_wino_b5_batch(L.ptr(A), ca, S, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound),
+                                                         ly.groups, L.ptr(ly.wpacked), ly.wexp, ly.cout, self.slope,
+                                                         self.passes, cfg[7] & 1, L.ptr(out),
+                                                         L.ptr(rows[0]) if rows is not None else None, aff, L.ptr(ws),
+                                                         ws.numel(), st), "conv_wino_b5_batch " + ly.name)
+            return
         if cfg[6] == 4:
             L.check(self.lib.bfm_conv3x3x3_wino4_batch(L.ptr(A), ca, S, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound),
                                                        ly.groups, L.ptr(ly.wpacked), ly.wexp, ly.cout, self.slope, self.passes,
@@ -1185,6 +1247,7 @@ class UNetEngine:
             cfg = self._autotune(sk, key, lambda c: self._batch_launch(sk, c, A[0:1], None, None, dims, sc_a[0:1], sh_a[0:1],
                                                                        bound[0:1], out[0:1], None, aff),
                                  vers=self.DEEP_VERS_1SRC)
+        cfg = self._deep_b5(sk, key, cfg, A, dims, sc_a, sh_a, bound)
         self._pack(sk, True, cfg[6])
         nv = D * H * W
         lo = lo_dims[0] * lo_dims[1] * lo_dims[2]

@@ -288,7 +288,22 @@ int bfm_conv3x3x3_wino4(const float* A, int CA, int D, int H, int W, const float
 int bfm_conv3x3x3_wino4_batch(const float* A, int CA, int S, int D, int H, int W, const float* scale, const float* shift,
                               const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
                               int flags, float* out, void* moment_rows, int affine_stride, bfm_stream_t stream);
-/* The masked form of the same kernel: the boxes (bfm_conv3x3x3_wino4_box) that hold a non-zero voxel of mask_image;
+/* F(2,3) along x (bfm_conv3x3x3_wino_ex's arithmetic and weight pack, bfm_pack_conv_weights_wino) on boxes of 5 x 5 x 10
+ * output voxels with a split K loop: the batched levels whose volumes are 5, 10 or 20 voxels wide, which no power-of-two
+ * box divides (conv3d_wino_b5.hip).  Arguments as bfm_conv3x3x3_wino4_batch, plus a workspace of
+ * bfm_conv3x3x3_wino_b5_workspace() bytes (16-byte aligned) for the K slabs, summed in slab order (no atomics); flags
+ * bit 0 adds what `out` holds before LeakyReLU; moment_rows [S * bfm_conv3x3x3_wino_b5_rows()][Cout], one row per box, or
+ * NULL.  Return codes as bfm_conv3x3x3_wino_ex, BFM_E_SHAPE unless D % 5 == 0, H % 5 == 0 and W % 10 == 0,
+ * BFM_E_WORKSPACE for a short workspace.  The split factor (bfm_conv3x3x3_wino_b5_splitk; 0: shape not taken) depends on
+ * the layer shape alone, never on S: a sample's workgroups do what they do in a launch of that sample alone. */
+int bfm_conv3x3x3_wino_b5_rows(int D, int H, int W, int passes);
+int bfm_conv3x3x3_wino_b5_splitk(int Cin, int Cout, int D, int H, int W);
+size_t bfm_conv3x3x3_wino_b5_workspace(int Cin, int Cout, int S, int D, int H, int W);
+int bfm_conv3x3x3_wino_b5_batch(const float* A, int CA, int S, int D, int H, int W, const float* scale, const float* shift,
+                                const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
+                                int flags, float* out, void* moment_rows, int affine_stride, void* workspace,
+                                size_t workspace_bytes, bfm_stream_t stream);
+/* The masked form of bfm_conv3x3x3_wino4: the boxes (bfm_conv3x3x3_wino4_box) that hold a non-zero voxel of mask_image;
  * workspace bfm_conv3x3x3_wino4_masked_workspace(D, H, W, passes) bytes (4-byte aligned).  There
  * is no uniform-box pair: F(4,3)'s rounding reaches 4 voxels along x where F(2,3)'s numerical support is its
  * mathematical one (conv3d_wino4.hip), so the layers that take that shortcut stay with bfm_conv3x3x3_wino_uniform. */

@@ -6,10 +6,17 @@ variants and the same volume gives the same bits run to run (the variants agree 
 
 Shapes covered: every tile shape of the reference tiling of 256^3 / 512^3 volumes (160/80 mixes) and a 128^3 tile
 (inference: forward layers, skip halves in accumulate mode), and one training iteration at 128^3 and 160^3 (the
-transposed data-gradient layers).  Anything else is timed in-process on first use, as before."""
+transposed data-gradient layers).  Anything else is timed in-process on first use, as before.
+
+    BFM_CONV_TUNE_SAVE=1 python scripts/make_tune_table.py --merge
+
+keeps every key the table has (none of them is timed again) and times and adds only the keys it lacks: what a new
+variant's own entries need (conv_wino_b5's ",5" keys)."""
 import os
 import sys
 
+if "--merge" in sys.argv[1:]:
+    os.environ["BFM_CONV_TUNE"] = "1"
 os.environ.setdefault("BFM_CONV_TUNE", "retune")
 os.environ.setdefault("BFM_CONV_TUNE_SAVE", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
