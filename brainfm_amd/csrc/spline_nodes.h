@@ -1,6 +1,7 @@
 // Per-axis spline nodes of the interpol grid kernels (utils/interpol/nd.py:44-75, splines.py:30-43 and :90-103), shared by
-// the voxel-wise kernels of spline_grid.hip and the separable axis tables of restrict.hip: the weight and its derivative,
-// the nodes of one axis (index, weight * sign, derivative * sign) and the inbounds mask (extrapolate 0 no / 1 yes / 2 hist).
+// the voxel-wise kernels of spline_grid.hip and grid_hess.hip and the separable axis tables of restrict.hip: the weight and
+// its first and second derivative (splines.py:149-157), the nodes of one axis (index, weight * sign, derivative * sign) and
+// the inbounds mask (extrapolate 0 no / 1 yes / 2 hist).
 #pragma once
 #include "bfm_common.h"
 #include "interp_bounds.h"
@@ -49,6 +50,36 @@ __device__ __forceinline__ void axis_nodes(float g, int order, int n, int b, int
         const float d = dist0 - (float)k;
         w[k] = spline_weight(order, d) * s;
         dw[k] = GRAD ? spline_dweight(order, d) * s : 0.f;
+    }
+}
+
+// splines.py:149-157: fasthess, even in x (no sign factor); 0 for orders 0 and 1
+__device__ __forceinline__ float spline_d2weight(int order, float x) {
+    if (order < 2) return 0.f;
+    x = fabsf(x);
+    if (order == 2) return x < 0.5f ? -2.f : 1.f;
+    return x < 1.f ? 3.f * x - 2.f : 2.f - x;
+}
+
+// axis_nodes with the second derivative as well (nd.py:368-391): d2w[k] = fasthess * sign.  ISO1 (order 1 only, T = 2):
+// the slope of iso1.py (-1 at the lower node, +1 at the upper), not the sign(x) of the generic path's fastgrad.  A sibling
+// of axis_nodes, whose instantiations stay as they are.
+template <int T, bool ISO1>
+__device__ __forceinline__ void axis_nodes2(float g, int order, int n, int b, int (&idx)[T], float (&w)[T], float (&dw)[T],
+                                            float (&d2w)[T]) {
+    const float g0f = floorf(g - 0.5f * (float)(order - 1));
+    const float dist0 = g - g0f;
+    const int g0 = (int)fminf(fmaxf(g0f, -1073741824.f), 1073741824.f);
+#pragma unroll
+    for (int k = 0; k < T; ++k) {
+        const bool used = k <= order;
+        const int node = used ? g0 + k : g0;
+        const float s = used ? (float)bound_sign(node, n, b) : 0.f;
+        idx[k] = bound_index(node, n, b);
+        const float d = dist0 - (float)k;
+        w[k] = spline_weight(order, d) * s;
+        dw[k] = (ISO1 ? (k == 0 ? -1.f : 1.f) : spline_dweight(order, d)) * s;
+        d2w[k] = spline_d2weight(order, d) * s;
     }
 }
 

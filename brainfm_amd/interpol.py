@@ -6,8 +6,10 @@ restrict.hip, which also give the separable cubic ``resize`` its gradient).  All
 splines.py:30-103, bounds.py:24-89) on spline_grid.hip.  ``prefilter`` goes through ``spline_coeff_nd``
 (coeff.py:254-344), which is differentiable (autograd.py:276-300).
 
-grid_pull / grid_push are differentiable to first order through grid_push / grid_grad; grid_grad itself
-is forward only.
+grid_pull / grid_push are differentiable to first order through grid_push / grid_grad, and grid_grad through
+``grid_pushgrad`` and ``grid_hess`` (pushpull.py:176-233 and :303-325; nd.py:291-464, iso1.py:390-675, iso0.py:326-368)
+on grid_hess.hip, which takes every order 0 to 3 in one export per operation.  Nothing here has a double backward, as in
+the reference.
 """
 import ctypes as C
 
@@ -124,6 +126,47 @@ def _grad_raw(x, g, b, o, ext):
     return out
 
 
+def _hess_raw(x, g, b, o, ext, cot=None):
+    """cot None: the Hessian (B,C,*out,3,3); cot (B,C,*out,3): its contraction with cot over channel and row, (B,*out,3)"""
+    B, Cc = x.shape[0], x.shape[1]
+    gs = tuple(g.shape[1:4])
+    out = torch.empty(((B, Cc) + gs + (3, 3)) if cot is None else ((B,) + gs + (3,)), dtype=torch.float32, device=x.device)
+    L.check(L.load().bfm_grid_hess3d(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0], gs[1], gs[2],
+                                     b, (C.c_int * 3)(*o), ext, L.ptr(cot), L.ptr(out), L.stream_ptr()), "grid_hess3d")
+    return out
+
+
+def _pushgrad_raw(x, g, shape, b, o, ext):
+    """x (B,C,*in,3) -> (B,C,*shape)"""
+    B, Cc = x.shape[0], x.shape[1]
+    out = torch.zeros((B, Cc) + tuple(shape), dtype=torch.float32, device=x.device)
+    L.check(L.load().bfm_grid_pushgrad3d(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, shape[0],
+                                         shape[1], shape[2], b, (C.c_int * 3)(*o), ext, L.ptr(out), L.stream_ptr()),
+            "grid_pushgrad3d")
+    return out
+
+
+class _GridGrad(torch.autograd.Function):
+    """autograd.py:216-245 + pushpull.py:303-325: d/dinput = pushgrad(grad), d/dgrid = sum over channel and row of
+    hess(input) * grad, which grid_hess.hip forms without writing the Hessian.  First order only."""
+
+    @staticmethod
+    def forward(ctx, x, g, b, o, ext):
+        ctx.opt = (b, o, ext)
+        ctx.save_for_backward(x, g)
+        return _grad_raw(x, g, b, o, ext)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, g = ctx.saved_tensors
+        b, o, ext = ctx.opt
+        grad = grad.contiguous().to(torch.float32)
+        gi = _pushgrad_raw(grad, g, x.shape[2:], b, o, ext) if ctx.needs_input_grad[0] else None
+        gg = _hess_raw(x, g, b, o, ext, cot=grad) if ctx.needs_input_grad[1] else None
+        return gi, gg, None, None, None
+
+
 class _GridPull(torch.autograd.Function):
     """autograd.py:125-152 + pushpull.py:237-258: d/dinput = push(grad), d/dgrid = sum_c grad * grid_grad(input) (zero at
     order 0, where grid_grad is)."""
@@ -212,17 +255,61 @@ def grid_count(grid, shape=None, interpolation="linear", bound="zero", extrapola
 
 def grid_grad(input, grid, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):
     """api.py:290-332: spatial gradient of the interpolated image at `grid`: (..., [channel], *spatial_out, 3).
-    Forward only (its own backward needs pushgrad / hess, not implemented)."""
+    Differentiable to first order w.r.t. input (grid_pushgrad) and grid (grid_hess contracted with the incoming gradient),
+    autograd.py:216-245; with `prefilter` the gradient reaches the un-filtered image through spline_coeff_nd.  Zero at
+    order 0, and so are both gradients.  A second backward raises."""
     b, o, ext = _opts(interpolation, bound, extrapolate)
+    if grid.shape[-1] != 3:
+        raise NotImplementedError("grid_grad: only 3-D grids are implemented (1-D and 2-D grids are not)")
     prefilter = _needs_prefilter(prefilter, o, list(b), input.shape[-3:])
     _require_cuda(input, "grid_grad")
-    input = input.detach()
     if prefilter:
         input = spline_coeff_nd(input, interpolation=list(o), bound=bound, dim=3)
-    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid.detach())
-    out = _grad_raw(x, g, b, o, ext)
+    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid)
+    out = _GridGrad.apply(x, g, b, o, ext)
     out_channel = [channel] if channel else ([1] if batch else [])
     return out.reshape(*batch, *out_channel, *grid_spatial, 3)
+
+
+def grid_hess(input, grid, interpolation="linear", bound="zero", extrapolate=False):
+    """pushpull.py:207-233: the Hessian of the interpolated image at `grid`, (..., [channel], *spatial_out, 3, 3), symmetric.
+    Entry (d, d) takes the second derivative of the spline on axis d, entry (d, d2) the first derivative on both; zero
+    at order 0, zero diagonal at order 1.  The inbounds mask of extrapolate 0 / 2 multiplies it for every batch and
+    channel count (the reference's nd.hess raises there unless B = C = 1).  Forward only."""
+    b, o, ext = _opts(interpolation, bound, extrapolate)
+    if grid.shape[-1] != 3:
+        raise NotImplementedError("grid_hess: only 3-D grids are implemented (1-D and 2-D grids are not)")
+    _require_cuda(input, "grid_hess")
+    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input.detach(), grid.detach())
+    out = _hess_raw(x, g, b, o, ext)
+    out_channel = [channel] if channel else ([1] if batch else [])
+    return out.reshape(*batch, *out_channel, *grid_spatial, 3, 3)
+
+
+def grid_pushgrad(input, grid, shape=None, interpolation="linear", bound="zero", extrapolate=False):
+    """pushpull.py:176-203: the adjoint of grid_grad.  input (..., [channel], *spatial, 3) holds a 3-vector per voxel and
+    is splatted at the coordinates `grid` (..., *spatial, 3) into a volume of `shape` (default: the input's spatial
+    shape): (..., [channel], *shape).  fp32 atomics, like grid_push.  Forward only."""
+    b, o, ext = _opts(interpolation, bound, extrapolate)
+    if grid.shape[-1] != 3 or input.shape[-1] != 3:
+        raise NotImplementedError("grid_pushgrad: only 3-D grids are implemented (1-D and 2-D grids are not)")
+    if input.dim() < 4:
+        raise ValueError("grid_pushgrad: input must be (..., [channel], X, Y, Z, 3)")
+    if tuple(input.shape[-4:-1]) != tuple(grid.shape[-4:-1]):
+        raise ValueError("Input and grid should have the same spatial shape")
+    shape = tuple(int(v) for v in (shape if shape is not None else input.shape[-4:-1]))
+    _require_cuda(input, "grid_pushgrad")
+    # the batch and channel conventions of _prep, with the three components behind the spatial dimensions
+    in_spatial = tuple(input.shape[-4:-1])
+    channel = 0 if input.dim() == 4 else input.shape[-5]
+    in_batch = tuple(input.shape[:-5]) if input.dim() > 4 else ()
+    batch = torch.broadcast_shapes(tuple(grid.shape[:-4]), in_batch)
+    g = grid.detach().to(torch.float32).expand(*batch, *in_spatial, 3).reshape(-1, *in_spatial, 3).contiguous()
+    x = input.detach().to(torch.float32).expand(*batch, channel or 1, *in_spatial, 3)
+    x = x.reshape(-1, channel or 1, *in_spatial, 3).contiguous()
+    out = _pushgrad_raw(x, g, shape, b, o, ext)
+    out_channel = [channel] if channel else ([1] if batch else [])
+    return out.reshape(*batch, *out_channel, *shape)
 
 
 def grid_pull(input, grid, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):

@@ -638,6 +638,25 @@ int bfm_grid_push3d_spline(const float* inp, int Bi, int C, int ix, int iy, int 
 int bfm_grid_grad3d_spline(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox,
                            int oy, int oz, const int* bound, const int* order, int extrapolate, float* out,
                            bfm_stream_t stream);
+/* interpol.grid_hess / grid_pushgrad, the two halves of the backward of grid_grad (utils/interpol/pushpull.py:176-233 and
+ * :303-325) -> nd.hess / nd.pushgrad (nd.py:291-464), iso1.hess3d / pushgrad3d for order {1,1,1} (iso1.py:390-675) and
+ * the zeros of iso0.hess / pushgrad for order {0,0,0} (iso0.py:326-368).  One export per operation takes every order and
+ * dispatches inside; the nodes, signs, weights, mask and argument checks are those of the _spline exports above.
+ * hess: entry (d,d) takes fasthess (splines.py:149-157) on axis d, entry (d,d2) fastgrad on both axes, the lower
+ *   triangle mirrors the upper one, and the inbounds mask multiplies the result for every B and C (nd.py:456 raises, or
+ *   returns a wrong shape, unless B = C = 1, where it gives this product).  cot NULL: out (B,C,ox,oy,oz,3,3).  cot
+ *   (B,C,ox,oy,oz,3), B = max(Bi,Bg): out (B,ox,oy,oz,3), out[b,v,j] = sum_c sum_i hess[b,c,v,i,j] * cot[b,c,v,i] --
+ *   pushpull.py:322-324 without the Hessian in memory.  Every element of out is written.
+ * pushgrad: inp (Bi,C,ix,iy,iz,3) scattered through grid (Bg,ix,iy,iz,3) into out (B,C,nx,ny,nz), which MUST be zero on
+ *   entry: node by node sign * mask * (c_x dwx wy wz + c_y wx dwy wz + c_z wx wy dwz), one fp32 atomic each.
+ * Order {1,1,1} takes iso1's slope (-1 / +1), the opposite of the generic path's fastgrad on a linear axis of a
+ * mixed-order call: the same Hessian, the opposite sign for pushgrad. */
+int bfm_grid_hess3d(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox, int oy,
+                    int oz, const int* bound, const int* order, int extrapolate, const float* cot, float* out,
+                    bfm_stream_t stream);
+int bfm_grid_pushgrad3d(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg, int nx, int ny,
+                        int nz, const int* bound, const int* order, int extrapolate, float* out_zeroed,
+                        bfm_stream_t stream);
 /* interpol.restrict -- utils/interpol/restrict.py:9-122 (grid_push, nd.py:148-214, on torch.stack(meshgrid_ij(*lin))) --
  * and the backward of the separable cubic interpol.resize, as per-axis sparse operators.  A separable grid has one
  * coordinate list per axis, so the (order+1)^3 taps of nd.py factor into three axis passes.
