@@ -21,6 +21,11 @@
 // v_mfma_f32_32x32x16_f16 with fp32 accumulation: 3 MFMAs at 16x the fp32
 // matrix rate each => 5.3x faster than v_mfma_f32_32x32x2_f32 at ~2^-22
 // relative product error (passes=3).  passes=1 keeps only hi*hi.
+// The activation operand is t = fmaf(x, scale * 2^aexp, shift * 2^aexp): ONE fp32 rounding, not a multiply and an add.
+// passes=3: hi = fp16(t) to nearest even, lo = fp16(t - hi).  passes=1: t feeds nothing but the conversion, and the
+// compiler emits v_fma_mixlo_f16 for the pair, which rounds the EXACT affine to fp16 once -- one fp16 ulp away from
+// fp16(t) wherever t is an fp16 tie that the exact value is not (rare: one operand of 27 360 in the kernel test; a single
+// one moves a one-pass output by ~1e-5 of max|y|).  tests/conv_forward_refs.py emulates both (split_emulation, affine_hi_once).
 //
 // Wave tile 64x64 (2x2 MFMA blocks), workgroup = WM x WN waves.
 #include "conv_shared.h"
