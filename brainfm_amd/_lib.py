@@ -217,6 +217,10 @@ SIGNATURES = {
     "bfm_grad_sumsq": (_I, [_P, _L, _P, _P, _P, _Z, _P]),
     "bfm_grad_sumsq_multi": (_I, [_P, _I, _P, _I, _L, _P, _P, _P, _Z, _P]),
     "bfm_adamw_step_multi": (_I, [_P, _I, _P, _I, _L, _F, _F, _F, _F, _F, _P]),
+    "bfm_adam_step_multi": (_I, [_P, _I, _P, _I, _L, _F, C.c_double, C.c_double, _F, _F, _P]),
+    "bfm_sgd_step_multi": (_I, [_P, _I, _P, _I, _L, _F, _F, _F, _P]),
+    "bfm_lars_sums_multi": (_I, [_P, _I, _P, _I, _L, _P, _P, _P, _Z, _P]),
+    "bfm_lars_step_multi": (_I, [_P, _I, _P, _I, _L, _F, _F, _P]),
     "bfm_conv3x3x3_mfma_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
     "bfm_conv3x3x3_mfma_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "bfm_conv3x3x3_mfma": (_I, [_P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _P, _I, _P, _I, _I, _F, _I,

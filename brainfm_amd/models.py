@@ -848,6 +848,85 @@ def get_postprocessor(gen_args, train_args, outputs, samples, target, feats, tas
     return outputs, samples, target
 
 
+# --------------------------------------------------------------------------- optimisers (Trainer/models/__init__.py:355-396)
+OPTIMIZER_KINDS = ("adam", "adamw", "sgd", "lars")
+# what the reference's constructors leave at their defaults (it passes none but SGD's lr=0, momentum=0.9): torch.optim.Adam /
+# AdamW / SGD and utils.LARS (utils/misc.py:1283-1284).  eta and momentum only mean something to the kinds that have them.
+_OPTIMIZER_DEFAULTS = {
+    "adam": dict(lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8),
+    "adamw": dict(lr=1e-3, weight_decay=1e-2, betas=(0.9, 0.999), eps=1e-8),
+    "sgd": dict(lr=0.0, weight_decay=0.0, momentum=0.9),
+    "lars": dict(lr=0.0, weight_decay=0.0, momentum=0.9, eta=1e-3),
+}
+# switches of those constructors that the HIP steps do not build: any value but the inert one is refused by name
+_OPTIMIZER_UNBUILT = {"amsgrad": False, "nesterov": False, "dampening": 0, "maximize": False, "weight_decay_filter": None,
+                      "lars_adaptation_filter": None}
+
+
+class OptimizerSpec:
+    """What build_optimizer returns in place of a torch optimiser: the kind, its hyper-parameters and the one param group
+    the training loop writes lr / weight_decay into every iteration (Trainer/engine.py:95-97).  The update itself runs in
+    train.TrainStep(..., optimizer=spec) and its siblings, which read param_groups[0] at every step."""
+
+    def __init__(self, kind, param_groups=None, **hyper):
+        kind = str(kind).lower()
+        if kind not in OPTIMIZER_KINDS:
+            raise ValueError("optim type %r not supported: one of %s" % (kind, ", ".join(OPTIMIZER_KINDS)))
+        d = dict(_OPTIMIZER_DEFAULTS[kind])
+        group = {}
+        for g in (param_groups or []):
+            group.update({k: v for k, v in dict(g).items() if k != "params"})
+        group.update(hyper)
+        for k, inert in _OPTIMIZER_UNBUILT.items():
+            if k in group and group.pop(k) not in (inert, None):
+                raise L.BfmError("optimizer option %s is not built in the HIP training steps" % k)
+        unknown = sorted(set(group) - {"lr", "weight_decay", "betas", "eps", "momentum", "eta"})
+        if unknown:
+            raise L.BfmError("optimizer %r takes no option %s" % (kind, unknown))
+        d.update(group)
+        self.kind = kind
+        self.betas = tuple(float(b) for b in d.get("betas", (0.9, 0.999)))
+        self.eps = float(d.get("eps", 1e-8))
+        self.momentum = float(d.get("momentum", 0.9))
+        self.eta = float(d.get("eta", 1e-3))
+        self.param_groups = [dict(lr=d["lr"], weight_decay=d["weight_decay"])]
+
+    def zero_grad(self, set_to_none=True):
+        """Trainer/engine.py:90 calls it every iteration; the HIP steps overwrite their gradient buffers."""
+
+    def __repr__(self):
+        return "OptimizerSpec(%r, %r)" % (self.kind, self.param_groups)
+
+
+def optimizer_spec(optimizer):
+    """An OptimizerSpec as it is, or the default one of a kind's name."""
+    return optimizer if isinstance(optimizer, OptimizerSpec) else OptimizerSpec(optimizer)
+
+
+def build_optimizer(train_args, params_groups):
+    """Trainer/models/__init__.py:360-372.  params_groups is scripts/train.py:46-53's [{'params': [...]}]; the tensors are
+    not used (the step owns the parameters), options beside them are.  train_args.momentum is not read, as in the reference.
+    One deliberate deviation: an unknown name raises ValueError here; the reference builds the error without raising it and
+    returns None."""
+    return OptimizerSpec(train_args.optimizer, params_groups)
+
+
+def build_schedulers(train_args, itr_per_epoch, lr, min_lr):
+    """Trainer/models/__init__.py:375-396: (lr_scheduler, wd_scheduler), one value per iteration each."""
+    from . import train as TR
+    if train_args.lr_scheduler == "cosine":
+        lr_scheduler = TR.cosine_scheduler(lr, min_lr, train_args.n_epochs, itr_per_epoch,
+                                           warmup_epochs=train_args.warmup_epochs)
+    elif train_args.lr_scheduler == "multistep":
+        lr_scheduler = TR.multistep_scheduler(lr, train_args.lr_drops, train_args.n_epochs, itr_per_epoch,
+                                              warmup_epochs=train_args.warmup_epochs, gamma=train_args.lr_drop_multi)
+    else:
+        # the reference falls through to an UnboundLocalError at its return
+        raise ValueError("lr_scheduler %r: 'cosine' or 'multistep'" % (train_args.lr_scheduler,))
+    wd_scheduler = TR.cosine_scheduler(train_args.weight_decay, train_args.weight_decay_end, train_args.n_epochs, itr_per_epoch)
+    return lr_scheduler, wd_scheduler
+
+
 # --------------------------------------------------------------------------- factory
 backbone_options = {"unet3d": UNet3D}
 

@@ -8,7 +8,8 @@ Mirrors the reference's iteration -- Trainer/engine.py:96-147:
     losses = sum(loss_dict[k] * weight_dict[k])
     scaler.scale(losses).backward()                   -> bfm_head_bwd, bfm_normalize_bwd, backward.backbone_backward
     scaler.unscale_(optimizer); clip_gradients(...)   -> bfm_grad_sumsq (+ non-finite flag), per-parameter coefficient
-    scaler.step(optimizer); scaler.update()           -> bfm_adamw_step, LossScaler.update
+    scaler.step(optimizer); scaler.update()           -> bfm_adamw_step, LossScaler.update   (optimizer='adam' | 'sgd' | 'lars':
+                                                         bfm_adam_step_multi / bfm_sgd_step_multi / bfm_lars_step_multi)
 
 with the criterion of Trainer/models/criterion.py (SetMultiCriterion: sum over the samples / all_samples) restricted to
 the supervised dense heads: T1 T2 FLAIR CT (+_grad, optional <key>_DM weights), SR(+_grad), distance, registration
@@ -316,6 +317,23 @@ class GradStore:
 _ADAM_DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("grad_scale", "<f4"),
                        ("bias1", "<f4"), ("bias2_sqrt", "<f4"), ("first_chunk", "<i4"), ("reserved", "<i8")])
 assert _ADAM_DESC.itemsize == 64
+# bfm_optim_tensor_t (Adam, SGD, LARS): s0 = exp_avg | momentum_buffer | mu, s1 = exp_avg_sq (Adam alone, else 0); q and wd
+# are LARS' per-tensor trust ratio and decay.  Every field bfm_grad_sumsq_multi reads (g, n, first_chunk) sits where
+# bfm_adam_tensor_t has it, so the clip norms of Adam and SGD come from that launch on these descriptors.
+_OPT_DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("s0", "<u8"), ("s1", "<u8"), ("n", "<i8"), ("grad_scale", "<f4"),
+                      ("bias1", "<f4"), ("bias2_sqrt", "<f4"), ("first_chunk", "<i4"), ("q", "<f4"), ("wd", "<f4")])
+assert _OPT_DESC.itemsize == 64 and all(_OPT_DESC.fields[k][1] == _ADAM_DESC.fields[k][1] for k in ("g", "n", "first_chunk"))
+# how a checkpoint's optimiser state names its buffers, per kind (torch.optim.Adam / AdamW / SGD, utils.LARS)
+_STATE_KEYS = {"adam": ("exp_avg", "exp_avg_sq"), "adamw": ("exp_avg", "exp_avg_sq"), "sgd": ("momentum_buffer",),
+               "lars": ("mu",)}
+
+
+def lars_trust_ratio(sum_gg, sum_pp, sum_pg, coef, weight_decay, eta):
+    """q of utils/misc.py:1302-1309 from the three sums of bfm_lars_sums_multi, in float64: |dp|^2 of dp = coef g + wd p is
+    coef^2 sum g^2 + 2 coef wd sum p g + wd^2 sum p^2.  q = eta |p| / |dp| where both norms are positive, else 1."""
+    dp2 = coef * coef * sum_gg + 2.0 * coef * weight_decay * sum_pg + weight_decay * weight_decay * sum_pp
+    pn, un = math.sqrt(max(sum_pp, 0.0)), math.sqrt(max(dp2, 0.0))
+    return eta * pn / un if (pn > 0.0 and un > 0.0) else 1.0
 
 
 class TrainStep:
@@ -325,7 +343,7 @@ class TrainStep:
 
     def __init__(self, engine, tail, loss_names, loss_weights, weights_ce, all_samples, max_surf_distance=3.0,
                  bias_field_log_type="l2", lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, clip_max_norm=0.0,
-                 scaler=None, age_head=None):
+                 scaler=None, age_head=None, optimizer="adamw"):
         if "contrastive" in loss_names:
             # the reference never mixes it with other losses (get_criterion returns early, Trainer/models/__init__.py:169-178)
             raise L.BfmError("loss 'contrastive' is the head-less pre-training mode: use ContrastiveStep, not TrainStep")
@@ -337,7 +355,7 @@ class TrainStep:
         self.hidden = list(getattr(tail, "hidden", ()))
         if self.hidden and age_head is not None:
             raise L.BfmError("task_f_maps with hidden head layers and the pooled scalar head together are not built")
-        self._init_optim(engine, loss_names, loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler)
+        self._init_optim(engine, loss_names, loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler, optimizer)
         self.all_samples = float(all_samples)
         self.max_dist = float(max_surf_distance)
         self.bias_l2 = 1 if bias_field_log_type == "l2" else 0
@@ -354,8 +372,18 @@ class TrainStep:
         if any(n in REG_REGULARISERS for n in self.loss_names) and "registration" not in tail.row_of:
             raise L.BfmError("losses %s need the registration head" % [n for n in self.loss_names if n in REG_REGULARISERS])
 
-    def _init_optim(self, engine, loss_names, loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler):
-        """What every kind of step holds: the engine, the loss table, the optimiser's and the scaler's state, the lanes."""
+    def _init_optim(self, engine, loss_names, loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler,
+                    optimizer="adamw"):
+        """What every kind of step holds: the engine, the loss table, the optimiser's and the scaler's state, the lanes.
+        optimizer: 'adam', 'adamw', 'sgd', 'lars' (Trainer/models/__init__.py:360-372), or what models.build_optimizer
+        returned -- its betas / eps / momentum / eta then hold, and apply() / step() read lr and weight_decay from its
+        param_groups[0] (the dictionary the loop of Trainer/engine.py:95-97 writes every iteration) when theirs are None."""
+        spec = M.optimizer_spec(optimizer)
+        self.opt_kind = spec.kind
+        self.opt_spec = spec if spec is optimizer else None
+        if self.opt_spec is not None:
+            betas, eps = tuple(spec.betas), spec.eps
+        self.momentum, self.eta = float(spec.momentum), float(spec.eta)
         self.eng = engine
         self.lib = engine.lib
         self.dev = engine.device
@@ -368,7 +396,7 @@ class TrainStep:
                                                             # loss is not stepped: its .grad is None in the reference)
         self._touched_heads = set()
         self._active_rows = set()
-        self.state = {}                                   # name -> (m, v)
+        self.state = {}                                   # name -> (m, v) | (momentum buffer,) | (mu,)
         self.age = None
         self.sample_lanes = max(1, int(os.environ.get("BFM_TRAIN_LANES", "2")))
         self._lane_streams = []
@@ -449,8 +477,12 @@ class TrainStep:
 
     def optimizer_state_dict(self, lr=None, weight_decay=None):
         """torch.optim.AdamW.state_dict() layout for the single parameter group of scripts/train.py:46-53 (parameters in
-        model.named_parameters() order == self.parameters() order)."""
+        model.named_parameters() order == self.parameters() order); with another optimiser, that one's layout."""
         names = list(self.parameters().keys())
+        if self.opt_kind != "adamw":
+            return self._other_optimizer_state_dict(names, lr, weight_decay)
+        if self.opt_spec is not None:
+            lr, weight_decay = self._hyper(lr, weight_decay)
         state = {}
         for i, k in enumerate(names):
             if k in self.state:
@@ -464,17 +496,71 @@ class TrainStep:
                  "params": list(range(len(names)))}
         return {"state": state, "param_groups": [group]}
 
+    def _hyper(self, lr=None, weight_decay=None):
+        """(lr, weight_decay) of this call: the arguments, else the spec's param group, else the constructor's."""
+        group = self.opt_spec.param_groups[0] if self.opt_spec is not None else {}
+        lr = group.get("lr", self.lr) if lr is None else lr
+        wd = group.get("weight_decay", self.wd) if weight_decay is None else weight_decay
+        return float(lr), float(wd)
+
+    def _other_optimizer_state_dict(self, names, lr=None, weight_decay=None):
+        """state_dict() layout of torch.optim.Adam / torch.optim.SGD as the installed torch writes it (the param-group keys
+        are read off a throw-away instance), or of utils.LARS (utils/misc.py:1283-1289), for the single parameter group."""
+        lr, wd = self._hyper(lr, weight_decay)
+        params = self.parameters()
+        state = {}
+        for i, k in enumerate(names):
+            if k in self.state:
+                shp = self._ref_shape(k, params[k])
+                st = {key: buf.reshape(shp).cpu().clone() for key, buf in zip(_STATE_KEYS[self.opt_kind], self.state[k])}
+                if self.opt_kind == "adam":
+                    st = dict(step=torch.tensor(float(self.steps.get(k, self.t))), **st)
+                state[i] = st
+        if self.opt_kind == "lars":
+            group = {"lr": lr, "weight_decay": wd, "momentum": self.momentum, "eta": self.eta, "weight_decay_filter": None,
+                     "lars_adaptation_filter": None}
+        else:
+            dummy = [torch.nn.Parameter(torch.zeros(1))]
+            opt = torch.optim.Adam(dummy) if self.opt_kind == "adam" else torch.optim.SGD(dummy, lr=0.0, momentum=self.momentum)
+            group = dict(opt.state_dict()["param_groups"][0])
+            group.update(lr=lr, weight_decay=wd)
+            if self.opt_kind == "adam":
+                group.update(betas=tuple(self.betas), eps=self.eps)
+        group["params"] = list(range(len(names)))
+        return {"state": state, "param_groups": [group]}
+
     def save_checkpoint(self, path, epoch=0, **extra):
         """torch.save of {'model', 'optimizer', 'epoch', ...}: what utils.save_on_master writes in scripts/train.py, and
         what brainfm_amd.models.load_checkpoint / the reference's load_checkpoint read back."""
         ckp = {"model": self.state_dict(), "optimizer": self.optimizer_state_dict(), "epoch": int(epoch),
-               "scaler_scale": self.scaler.scale}
+               "scaler_scale": self.scaler.scale, "optimizer_kind": self.opt_kind}
         ckp.update(extra)
         torch.save(ckp, path)
 
     def load_checkpoint(self, path):
-        """Parameters (matched by name suffix, as utils/checkpoint.py:558-571) and AdamW moments back into the engine."""
+        """Parameters (matched by name suffix, as utils/checkpoint.py:558-571) and the optimiser's buffers back into the
+        engine.  Optimiser state of another kind than this step's raises: 'optimizer_kind' decides, or the state's keys for a
+        checkpoint the reference wrote (exp_avg is never read as a momentum buffer)."""
         ckp = M.read_checkpoint_file(path)
+        opt = ckp.get("optimizer")
+        if opt and opt.get("state"):
+            keys = set().union(*(set(st.keys()) for st in opt["state"].values()))
+            found = ckp.get("optimizer_kind")
+            if found is None:
+                found = next((k_ for k_ in ("adamw", "sgd", "lars") if set(_STATE_KEYS[k_]) <= keys), None)
+                same = found is not None and _STATE_KEYS[found] == _STATE_KEYS[self.opt_kind]
+                found = "adam or adamw" if found == "adamw" else found      # their states look alike
+            else:
+                same = found == self.opt_kind and set(_STATE_KEYS[self.opt_kind]) <= keys
+            if not same:
+                raise L.BfmError("checkpoint %s holds the state of optimiser %r (keys %s); this step runs %r and does not "
+                                 "reinterpret it" % (path, found, sorted(keys), self.opt_kind))
+            if self.opt_kind != "adamw":
+                for g in opt.get("param_groups", ()):
+                    for k_, inert in M._OPTIMIZER_UNBUILT.items():
+                        if g.get(k_) not in (inert, None):
+                            raise L.BfmError("checkpoint %s was written with %s=%r, which the HIP %s step does not build"
+                                             % (path, k_, g.get(k_), self.opt_kind))
         key = next((k for k in ckp if "model" in k), None)
         sd = ckp[key] if key is not None else ckp
         params = self.parameters()
@@ -487,15 +573,15 @@ class TrainStep:
                 raise ValueError("shape mismatch for %s: %s vs %s" % (k, tuple(src.shape), tuple(p.shape)))
             p.copy_(src.reshape(p.shape).to(device=self.dev, dtype=torch.float32))
         self._weights_changed()
-        opt = ckp.get("optimizer")
         if opt and opt.get("state"):
             names = list(params.keys())
             self.state = {}
             for i, st in opt["state"].items():
                 k = names[int(i)]
-                self.state[k] = (st["exp_avg"].reshape(-1).to(device=self.dev, dtype=torch.float32).contiguous(),
-                                 st["exp_avg_sq"].reshape(-1).to(device=self.dev, dtype=torch.float32).contiguous())
-                self.steps[k] = int(float(st["step"]))
+                self.state[k] = tuple(st[key].reshape(-1).to(device=self.dev, dtype=torch.float32).contiguous()
+                                      for key in _STATE_KEYS[self.opt_kind])
+                # SGD and LARS keep no step count: a buffer means at least one step
+                self.steps[k] = int(float(st["step"])) if "step" in st else 1
             self.t = max(self.steps.values()) if self.steps else 0
         if "scaler_scale" in ckp and self.scaler.enabled:
             self.scaler.scale = float(ckp["scaler_scale"])
@@ -941,8 +1027,10 @@ class TrainStep:
             if not params[k].is_contiguous():
                 raise L.BfmError("parameter %s is not contiguous" % k)
             if k not in self.state:
-                self.state[k] = (torch.zeros(params[k].numel(), dtype=torch.float32, device=self.dev),
-                                 torch.zeros(params[k].numel(), dtype=torch.float32, device=self.dev))
+                self.state[k] = tuple(torch.zeros(params[k].numel(), dtype=torch.float32, device=self.dev)
+                                      for _ in _STATE_KEYS[self.opt_kind])
+        if self.opt_kind != "adamw":
+            return self._measure_other(grads, params, names, sums, flag, grad_div)
         if multi:
             # every tensor's sum of squares in one launch (+ a fold): descriptors and chunk map in device memory
             CH = 65536
@@ -975,11 +1063,94 @@ class TrainStep:
         return dict(grads=grads, params=params, names=names, norms=norms, inv=inv, found_inf=found_inf, multi=multi,
                     desc=desc if multi else None, CH=CH if multi else 0)
 
-    def _update(self, plan, lr=None, weight_decay=None):
-        """Second half of apply: per-parameter clip and AdamW on what _measure prepared, then the packed weights."""
+    def _chunks(self, names, params, CH):
+        """The chunk map (device) of these tensors and each one's first chunk; kept while the sizes stay the same."""
+        first, firsts, cmap = 0, [], []
+        for i, k in enumerate(names):
+            nch = (params[k].numel() + CH - 1) // CH
+            firsts.append(first)
+            cmap.extend([i] * nch)
+            first += nch
+        key = tuple(params[k].numel() for k in names)
+        if getattr(self, "_chunk_key", None) != key:
+            self._chunk_key = key
+            self._chunk_map = torch.tensor(cmap, dtype=torch.int32, device=self.dev)
+            self._chunk_ws = torch.empty(len(cmap), dtype=torch.float64, device=self.dev)
+        return firsts, len(cmap)
+
+    def _measure_other(self, grads, params, names, sums, flag, grad_div):
+        """_measure for Adam, SGD and LARS (multi-tensor kernels only): bfm_optim_tensor_t descriptors; the clip norms from
+        bfm_grad_sumsq_multi, or for LARS from bfm_lars_sums_multi, whose sum p^2 and sum p g the update's trust ratio needs."""
         lib, st = self.lib, L.stream_ptr()
-        lr = self.lr if lr is None else float(lr)
-        wd = self.wd if weight_decay is None else float(weight_decay)
+        CH = 65536
+        firsts, nchunks = self._chunks(names, params, CH)
+        desc = np.zeros(len(names), dtype=_OPT_DESC)
+        for i, k in enumerate(names):
+            bufs = self.state[k]
+            desc[i] = (params[k].data_ptr(), grads[k].data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr() if len(bufs) > 1 else 0,
+                       params[k].numel(), 0.0, 1.0, 1.0, firsts[i], 1.0, 0.0)
+        tdev = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(self.dev)
+        sums3 = None
+        if self.opt_kind == "lars":
+            sums3 = torch.zeros(len(names) * 3, dtype=torch.float64, device=self.dev)
+            ws = torch.empty(nchunks * 3, dtype=torch.float64, device=self.dev)
+            L.check(lib.bfm_lars_sums_multi(L.ptr(tdev), len(names), L.ptr(self._chunk_map), nchunks, CH, L.ptr(sums3),
+                                            L.ptr(flag), L.ptr(ws), ws.numel() * 8, st), "lars_sums_multi")
+            sums3 = sums3.cpu().reshape(-1, 3)
+            sumsq = sums3[:, 0].tolist()
+        else:
+            L.check(lib.bfm_grad_sumsq_multi(L.ptr(tdev), len(names), L.ptr(self._chunk_map), nchunks, CH, L.ptr(sums),
+                                             L.ptr(flag), L.ptr(self._chunk_ws), self._chunk_ws.numel() * 8, st),
+                    "grad_sumsq_multi")
+            sumsq = sums.cpu().tolist()
+        inv = 1.0 / (self.scaler.scale * grad_div)
+        found_inf = bool(flag.item())
+        norms = [math.sqrt(v) * inv if math.isfinite(v) else float("inf") for v in sumsq]
+        found_inf = found_inf or any(not math.isfinite(v) for v in norms)
+        return dict(grads=grads, params=params, names=names, norms=norms, inv=inv, found_inf=found_inf, multi=True, desc=desc,
+                    CH=CH, sums3=sums3)
+
+    def _update_other(self, plan, lr, wd):
+        """_update for Adam, SGD and LARS: the per-tensor numbers into the descriptors, then one launch."""
+        lib, st = self.lib, L.stream_ptr()
+        params, names, norms, inv, desc, CH = (plan[k] for k in ("params", "names", "norms", "inv", "desc", "CH"))
+        self.t += 1
+        for i, (k, nrm) in enumerate(zip(names, norms)):
+            self.steps[k] = self.steps.get(k, 0) + 1        # one step count per parameter, as torch's optimisers keep
+            coef = inv
+            if self.clip > 0:
+                c = self.clip / (nrm + 1e-6)
+                if c < 1:
+                    coef *= c
+            desc[i]["grad_scale"] = coef
+            if self.opt_kind == "adam":
+                # bias corrections in float32, as _update forms them for AdamW
+                desc[i]["bias1"] = np.float32(1.0) - np.power(np.float32(self.betas[0]), np.float32(self.steps[k]), dtype=np.float32)
+                desc[i]["bias2_sqrt"] = np.sqrt(np.float32(1.0) - np.power(np.float32(self.betas[1]), np.float32(self.steps[k]),
+                                                                          dtype=np.float32), dtype=np.float32)
+            elif self.opt_kind == "lars" and len(self._ref_shape(k, params[k])) != 1:
+                # utils/misc.py:1299-1310: decay and trust ratio for everything but the reference's 1-D parameters
+                sgg, spp, spg = (float(v) for v in plan["sums3"][i])
+                desc[i]["wd"] = wd
+                desc[i]["q"] = lars_trust_ratio(sgg, spp, spg, float(np.float32(coef)), float(np.float32(wd)), self.eta)
+        tdev = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(self.dev)
+        head = (L.ptr(tdev), len(names), L.ptr(self._chunk_map), int(self._chunk_map.numel()), CH)
+        if self.opt_kind == "adam":
+            rc = lib.bfm_adam_step_multi(*head, lr, self.betas[0], self.betas[1], self.eps, wd, st)
+        elif self.opt_kind == "sgd":
+            rc = lib.bfm_sgd_step_multi(*head, lr, self.momentum, wd, st)
+        else:
+            rc = lib.bfm_lars_step_multi(*head, lr, self.momentum, st)
+        L.check(rc, self.opt_kind + "_step_multi")
+        self._keep_desc = tdev
+        self._weights_changed()
+
+    def _update(self, plan, lr=None, weight_decay=None):
+        """Second half of apply: per-parameter clip and the optimiser on what _measure prepared, then the packed weights."""
+        lib, st = self.lib, L.stream_ptr()
+        lr, wd = self._hyper(lr, weight_decay)
+        if self.opt_kind != "adamw":
+            return self._update_other(plan, lr, wd)
         grads, params, names, norms, inv = plan["grads"], plan["params"], plan["names"], plan["norms"], plan["inv"]
         multi, desc, CH = plan["multi"], plan["desc"], plan["CH"]
         self.t += 1
@@ -1339,9 +1510,9 @@ class ContrastiveStep(TrainStep):
     More than one rank is refused (BfmError): the gradient all-reduce of this step is not built."""
 
     def __init__(self, engine, loss_weights, temperatures, lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8,
-                 clip_max_norm=0.0, scaler=None):
+                 clip_max_norm=0.0, scaler=None, optimizer="adamw"):
         self.tail = _NoHead()
-        self._init_optim(engine, ["contrastive"], loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler)
+        self._init_optim(engine, ["contrastive"], loss_weights, lr, weight_decay, betas, eps, clip_max_norm, scaler, optimizer)
         self.alpha, self.beta, self.gamma = (float(t) for t in temperatures)
         if not (self.alpha > 0 and self.beta > 0 and self.gamma > 0):
             raise L.BfmError("contrastive temperatures must be positive, got %s" % (tuple(temperatures),))

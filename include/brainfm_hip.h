@@ -1059,6 +1059,42 @@ int bfm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, floa
 int bfm_grad_sumsq(const float* g, int64_t n, double* out, int32_t* nonfinite, void* workspace, size_t workspace_bytes,
                    bfm_stream_t stream);
 
+/* ---- the other optimisers of build_optimizer (Trainer/models/__init__.py:360-372; optim.hip) ---------------------------
+ * One descriptor per parameter tensor (device memory, 64 bytes), in the multi-tensor form of bfm_adamw_step_multi: a block
+ * owns one chunk (chunk_elems elements, a multiple of 4) of one tensor, chunk_tensor[c] = tensor of chunk c, first_chunk =
+ * index of the tensor's first chunk.  s0 = exp_avg (Adam) | momentum_buffer (SGD) | mu (LARS); s1 = exp_avg_sq (Adam; not
+ * read by the others, may be NULL).  g is multiplied by grad_scale first (unscale * clip).  bias1 / bias2_sqrt as in
+ * bfm_adam_tensor_t (Adam alone).  q and wd are LARS' per-tensor trust ratio and weight decay (1 and 0 for a parameter the
+ * reference sees as 1-D, utils/misc.py:1299-1310).  16-byte accesses where p, g, s0 (and s1) are all 16-byte aligned and the
+ * chunk's length is a multiple of 4, element by element otherwise.  No float atomics: the same bits on every run. */
+typedef struct bfm_optim_tensor {
+    float* p; const float* g; float* s0; float* s1;
+    int64_t n;
+    float grad_scale, bias1, bias2_sqrt;
+    int32_t first_chunk;
+    float q, wd;
+} bfm_optim_tensor_t;
+/* torch.optim.Adam(params_groups) of Trainer/models/__init__.py:361-362 (amsgrad off, maximize off; coupled decay):
+ * g = grad_scale g + wd p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g g;  p -= (lr / bias1) m / (sqrt(v) / bias2_sqrt + eps).
+ * The betas are doubles so that 1 - beta is rounded to fp32 once, as torch forms it. */
+int bfm_adam_step_multi(const bfm_optim_tensor_t* tensors, int ntensors, const int32_t* chunk_tensor, int nchunks,
+                        int64_t chunk_elems, float lr, double beta1, double beta2, float eps, float weight_decay,
+                        bfm_stream_t stream);
+/* torch.optim.SGD(params_groups, lr=0, momentum=0.9) of Trainer/models/__init__.py:365-366 (dampening 0, nesterov off):
+ * g = grad_scale g + wd p;  buf = momentum buf + g;  p -= lr buf.  A zero buffer gives torch's first step. */
+int bfm_sgd_step_multi(const bfm_optim_tensor_t* tensors, int ntensors, const int32_t* chunk_tensor, int nchunks,
+                       int64_t chunk_elems, float lr, float momentum, float weight_decay, bfm_stream_t stream);
+/* What utils.LARS.step (utils/misc.py:1291-1317, Trainer/models/__init__.py:367-368) and clip_gradients (:1329-1338) need of
+ * every tensor, from ONE read of p and g: sums_out[3 t + {0, 1, 2}] = sum g^2, sum p^2, sum p g (fp64, fixed order);
+ * nonfinite[0] |= 1 when some g holds inf / nan.  workspace >= nchunks * 24 bytes, 8-byte aligned. */
+int bfm_lars_sums_multi(const bfm_optim_tensor_t* tensors, int ntensors, const int32_t* chunk_tensor, int nchunks,
+                        int64_t chunk_elems, double* sums_out, int32_t* nonfinite, void* workspace, size_t workspace_bytes,
+                        bfm_stream_t stream);
+/* utils/misc.py:1296-1317 with the norms already taken (q = eta |p| / |dp| or 1, formed by the caller from the sums above):
+ * dp = grad_scale g (+ wd p when wd != 0);  dp *= q;  mu = momentum mu + dp;  p -= lr mu */
+int bfm_lars_step_multi(const bfm_optim_tensor_t* tensors, int ntensors, const int32_t* chunk_tensor, int nchunks,
+                        int64_t chunk_elems, float lr, float momentum, bfm_stream_t stream);
+
 /* ------------------------------------------------------------------- pooled scalar (brain-age) head
  * TaskHead's head for out_channels['age'] = -1 (Trainer/models/head.py:39-48 building, :61-66 forward):
  * MaxPool3d(4,4) -> ConvBlock(C_feat->16) -> MaxPool3d(4,4) -> ConvBlock(16->4) -> torch.flatten(x, 1) (NCDHW order)
