@@ -57,6 +57,17 @@ class Dopri5Advect(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+ODE_EULER, ODE_MIDPOINT, ODE_RK4 = 0, 1, 2          # BFM_ODE_* of include/brainfm_hip.h
+
+
+class OdeFixedAdvect(C.Structure):
+    """bfm_ode_fixed_advect_t: sol / k / V are device pointers, coef is a HOST array of floats."""
+    _fields_ = [("sol", C.c_void_p), ("k", C.c_void_p * 3),
+                ("Vx", C.c_void_p), ("Vy", C.c_void_p), ("Vz", C.c_void_p),
+                ("sx", C.c_int), ("sy", C.c_int), ("sz", C.c_int), ("neumann_bc", C.c_int), ("is_f64", C.c_int),
+                ("method", C.c_int), ("nt", C.c_int), ("coef", C.POINTER(C.c_float))]
+
+
 class AgeParams(C.Structure):
     """bfm_age_params_t: device pointers of the age head's parameters (torch layouts)."""
     _fields_ = [(n, C.c_void_p) for n in ("c1w", "c1b", "c2w", "c2b", "l1w", "l1b", "l2w", "l2b", "l3w", "l3b")]
@@ -265,6 +276,8 @@ SIGNATURES = {
     "bfm_dopri5_advect_workspace": (_Z, [_I, _I, _I]),
     "bfm_dopri5_advect_init": (_I, [C.POINTER(Dopri5Advect), C.c_double, C.c_double, _P]),
     "bfm_dopri5_advect_steps": (_I, [C.POINTER(Dopri5Advect), _I, _P]),
+    "bfm_ode_fixed_ncoef": (_I, [_I]),
+    "bfm_ode_fixed_advect": (_I, [C.POINTER(OdeFixedAdvect), _P]),
     "bfm_randn_philox": (_I, [_P, _L, C.c_uint64, C.c_uint64, _F, _P]),
     "bfm_svf_integrate_workspace": (_Z, [_I, _I, _I]),
     "bfm_svf_integrate": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),

@@ -339,3 +339,154 @@ extern "C" int bfm_dopri5_advect_steps(const bfm_dopri5_advect_t* d, int nsteps,
     }
     return bfm_launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Fixed-grid solvers: euler, midpoint, rk4 (DiffEqs/fixed_grid.py:5-33, solvers.py:158-207, rk_common.py:72-78).
+// The grid is the requested times, so step i reads row i of the (nt, ...) solution and writes row i + 1: no controller,
+// no state block, no read-back; the whole integration is enqueued at once.  A stage is the box kernel of ode_stage
+// above: stage state y + sum_j c_j k_j on the box and its halo into LDS (rk_combine's expression at the
+// boundary-conditioned position), then the upwind RHS from LDS.  The LAST stage of a step does not store its k: the
+// thread that formed k_n at voxel i also forms y1[i] = y[i] + (sum_{j < NF} cf_j k_j[i] + cf_NF k_n), rk_combine's
+// expression over (k_1 .. k_n) at the UNconditioned position, and stores it into the next row.
+//   NK: stages in the stage state (0: the state itself);  NF: earlier stages in the final sum, -1: not the last stage.
+// The coefficients come from the host already rounded to the fp32 values the unfused route hands to rk_combine.
+namespace {
+
+struct FixedArgs {
+    const float* k[3]; float c[3]; float cf[4];
+    const float *Vx, *Vy, *Vz;
+    float* kout;
+    int sx, sy, sz, neumann;
+};
+
+template <typename T, int NK, int NF>
+__global__ void __launch_bounds__(256) ode_fixed_stage(const T* __restrict__ y, T* __restrict__ y1, FixedArgs A) {
+    __shared__ T sU[HX * HY * HZ];
+    const int sx = A.sx, sy = A.sy, sz = A.sz;
+    const int64_t stx = (int64_t)sy * sz, sty = sz;
+    const int nbz = (sz + TZ - 1) / TZ, nby = (sy + TY - 1) / TY;
+    const int bz = blockIdx.x % nbz, by = (blockIdx.x / nbz) % nby, bx = blockIdx.x / (nbz * nby);
+    const int x0 = bx * TX, y0 = by * TY, z0 = bz * TZ;
+    // ---- phase 1: the stage state on the box + halo
+    for (int p = threadIdx.x; p < HX * HY * HZ; p += 256) {
+        const int hz = p % HZ, hy = (p / HZ) % HY, hx = p / (HZ * HY);
+        int a = x0 + hx - 1, b = y0 + hy - 1, cc = z0 + hz - 1;
+        if (A.neumann) {
+            a = min(max(a, 1), sx - 2); b = min(max(b, 1), sy - 2); cc = min(max(cc, 1), sz - 2);
+        } else {
+            a = min(max(a, 0), sx - 1); b = min(max(b, 0), sy - 1); cc = min(max(cc, 0), sz - 1);   // never used beyond the faces
+        }
+        const int64_t q = a * stx + b * sty + cc;
+        T v = y[q];
+        if (NK > 0) {
+            float acc = A.c[0] * A.k[0][q];
+#pragma unroll
+            for (int j = 1; j < NK; ++j) acc = acc + A.c[j] * A.k[j][q];
+            v = (T)(v + (T)acc);
+        }
+        sU[p] = v;
+    }
+    __syncthreads();
+    // ---- phase 2: upwind right-hand side of the box's voxels
+    const int tz = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int yy = y0 + ty, z = z0 + tz;
+    if (yy < sy && z < sz) {
+#pragma unroll 2
+        for (int tx = 0; tx < TX; ++tx) {
+            const int x = x0 + tx;
+            if (x >= sx) break;
+            const int64_t i = x * stx + yy * sty + z;
+            auto U = [&](int dx, int dy, int dz) -> T { return sU[((tx + 1 + dx) * HY + (ty + 1 + dy)) * HZ + (tz + 1 + dz)]; };
+            const T u = U(0, 0, 0);
+            float acc = 0.f;
+            bool first = true;
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const int pos = ax == 0 ? x : (ax == 1 ? yy : z);
+                const int len = ax == 0 ? sx : (ax == 1 ? sy : sz);
+                const int ex = ax == 0, ey = ax == 1, ez = ax == 2;
+                const int fw = pos < len - 1 ? 1 : 0, bw = pos > 0 ? 1 : 0;
+                const T up = U(ex * fw, ey * fw, ez * fw);
+                const T dn = U(-ex * bw, -ey * bw, -ez * bw);
+                const float df = pos < len - 1 ? (float)(up - u) : (float)(u - dn);
+                const float db = pos > 0 ? (float)(u - dn) : (float)(up - u);
+                const float V = ax == 0 ? A.Vx[i] : (ax == 1 ? A.Vy[i] : A.Vz[i]);
+                const float flag = V > 0.f ? 1.f : 0.f;
+                const float d = df * (1.f - flag) + db * flag;
+                const float term = V * d;
+                acc = first ? term : acc + term;
+                first = false;
+            }
+            const float kn = -acc;
+            if constexpr (NF < 0) {
+                A.kout[i] = kn;
+            } else if constexpr (NF == 0) {
+                y1[i] = (T)(y[i] + (T)(A.cf[0] * kn));
+            } else {
+                float s = A.cf[0] * A.k[0][i];
+#pragma unroll
+                for (int j = 1; j < NF; ++j) s = s + A.cf[j] * A.k[j][i];
+                s = s + A.cf[NF] * kn;
+                y1[i] = (T)(y[i] + (T)s);
+            }
+        }
+    }
+}
+
+template <typename T, int NK, int NF>
+void fixed_launch(const T* y, T* y1, const FixedArgs& A, int nb, hipStream_t s) {
+    hipLaunchKernelGGL((ode_fixed_stage<T, NK, NF>), dim3(nb), dim3(256), 0, s, y, y1, A);
+}
+
+template <typename T>
+void fixed_enqueue(const bfm_ode_fixed_advect_t* d, hipStream_t s) {
+    const int64_t n = (int64_t)d->sx * d->sy * d->sz;
+    const int nb = ((d->sx + TX - 1) / TX) * ((d->sy + TY - 1) / TY) * ((d->sz + TZ - 1) / TZ);
+    FixedArgs A{};
+    A.Vx = d->Vx; A.Vy = d->Vy; A.Vz = d->Vz;
+    A.sx = d->sx; A.sy = d->sy; A.sz = d->sz; A.neumann = d->neumann_bc ? 1 : 0;
+    for (int j = 0; j < 3; ++j) A.k[j] = d->k[j];
+    T* sol = static_cast<T*>(d->sol);
+    for (int i = 0; i + 1 < d->nt; ++i) {
+        const T* y = sol + (int64_t)i * n;
+        T* y1 = sol + (int64_t)(i + 1) * n;
+        const float* c = d->coef + (size_t)i * bfm_ode_fixed_ncoef(d->method);
+        if (d->method == BFM_ODE_EULER) {                       // dy = dt * f(y)
+            A.cf[0] = c[0];
+            fixed_launch<T, 0, 0>(y, y1, A, nb, s);
+        } else if (d->method == BFM_ODE_MIDPOINT) {             // dy = dt * f(y + f(y) * dt / 2)
+            A.kout = d->k[0];
+            fixed_launch<T, 0, -1>(y, y1, A, nb, s);
+            A.c[0] = c[0]; A.cf[0] = c[1];
+            fixed_launch<T, 1, 0>(y, y1, A, nb, s);
+        } else {                                                // the 3/8 rule, rk4_alt_step_func
+            A.kout = d->k[0];
+            fixed_launch<T, 0, -1>(y, y1, A, nb, s);
+            A.c[0] = c[0]; A.kout = d->k[1];
+            fixed_launch<T, 1, -1>(y, y1, A, nb, s);
+            A.c[0] = c[1]; A.c[1] = c[2]; A.kout = d->k[2];
+            fixed_launch<T, 2, -1>(y, y1, A, nb, s);
+            A.c[0] = c[3]; A.c[1] = c[4]; A.c[2] = c[5];
+            A.cf[0] = c[6]; A.cf[1] = c[7]; A.cf[2] = c[8]; A.cf[3] = c[9];
+            A.kout = nullptr;
+            fixed_launch<T, 3, 3>(y, y1, A, nb, s);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int bfm_ode_fixed_ncoef(int method) {
+    return method == BFM_ODE_EULER ? 1 : (method == BFM_ODE_MIDPOINT ? 2 : (method == BFM_ODE_RK4 ? 10 : 0));
+}
+
+extern "C" int bfm_ode_fixed_advect(const bfm_ode_fixed_advect_t* d, bfm_stream_t stream) {
+    if (!d || !d->sol || !d->Vx || !d->Vy || !d->Vz || !d->coef || d->nt < 2) return BFM_E_ARG;
+    const int nk = d->method == BFM_ODE_EULER ? 0 : (d->method == BFM_ODE_MIDPOINT ? 1 : (d->method == BFM_ODE_RK4 ? 3 : -1));
+    if (nk < 0) return BFM_E_ARG;
+    for (int j = 0; j < nk; ++j) if (!d->k[j]) return BFM_E_ARG;
+    if (d->sx < 3 || d->sy < 3 || d->sz < 3 || (int64_t)d->sx * d->sy > INT32_MAX) return BFM_E_ARG;
+    if (d->is_f64) fixed_enqueue<double>(d, bfm_s(stream));
+    else fixed_enqueue<float>(d, bfm_s(stream));
+    return bfm_launch_status();
+}

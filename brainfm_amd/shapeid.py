@@ -5,6 +5,8 @@
   AdvDiffPDE(...).forward(t, batch_C)                                     ShapeID/DiffEqs/pde.py:563-640
   odeint / odeint_adjoint (method 'dopri5')                               DiffEqs/odeint.py:20-75, adjoint.py:105-132,
                                                                           dopri5.py:58-172, rk_common.py, interp.py, misc.py
+  odeint_adjoint (methods 'euler', 'midpoint', 'rk4')                     DiffEqs/fixed_grid.py:5-33, solvers.py:158-207,
+                                                                          rk_common.py:72-78
 
 The lattice gradients are drawn on the host with ``np.random`` exactly like the reference (two
 ``rand`` calls per field) and uploaded; everything per voxel runs in libbrainfm_hip.so.  The
@@ -402,8 +404,118 @@ class Dopri5Solver:
         return out
 
 
+# ----------------------------------------------------------------------------- fixed-grid solvers
+# method -> (stage states after the first: coefficients of k_1.. in units of dt, index of the first k in the final sum,
+# coefficients of the final sum).  DiffEqs/fixed_grid.py:5-33; rk4 is rk_common.rk4_alt_step_func (the 3/8 rule), :72-78.
+_FIXED_TABLES = {
+    "euler": ([], 0, [1.]),
+    "midpoint": ([[1 / 2]], 1, [1.]),
+    "rk4": ([[1 / 3], [-1 / 3, 1.], [1., -1., 1.]], 0, [1 / 8, 3 / 8, 3 / 8, 1 / 8]),
+}
+_FIXED_IDS = {"euler": L.ODE_EULER, "midpoint": L.ODE_MIDPOINT, "rk4": L.ODE_RK4}
+_REFUSED_METHODS = ("adams", "tsit5", "fixed_adams", "explicit_adams")
+
+
+class FixedGridSolver:
+    """FixedGridODESolver.integrate (DiffEqs/solvers.py:158-207) with the step functions of fixed_grid.py.
+
+    No step_size is passed by odeint, so the grid is `t` itself, cast to the state dtype (:160-165): with an fp32 state
+    a step is t[i+1] - t[i] in fp32, not the configured dt.  One solution row is appended per step and
+    `_linear_interp` returns y1 itself (t == t1), so nothing is interpolated.  Stage states and the final sum are
+    bfm_rk_combine's (dt * c in the state dtype, rounded to the fp32 that torch's 0-dim promotion multiplies the fp32
+    stage with, summed left to right): euler and midpoint are the reference's expressions; rk4's `dt * k1 / 3`,
+    `dt * (k1 / -3 + k2)` and `(k1 + 3 k2 + 3 k3 + k4) * (dt / 8)` are formed as sums of (dt c_j) k_j, which rounds
+    differently in the last fp32 place of dy."""
+
+    def __init__(self, func, y0, method):
+        self.func, self.y0, self.method = func, y0, method
+        self.stages, self.first, self.final = _FIXED_TABLES[method]
+        self.lib = L.load()
+        self.f64 = y0.dtype == torch.float64
+        self.sd = np.float64 if self.f64 else np.float32
+        self.n = y0.numel()
+
+    def grid_steps(self, t):
+        tg = [self.sd(v) for v in t]
+        return [self.sd(b - a) for a, b in zip(tg[:-1], tg[1:])]
+
+    def _coefs(self, dt, coef):
+        return [float(np.float32(self.sd(dt) * self.sd(c))) for c in coef]
+
+    def _combine(self, y, ks, dt, coef):
+        out = torch.empty_like(y)
+        s = _kset(ks, dt, coef, self.sd)
+        L.check(self.lib.bfm_rk_combine(L.ptr(y), int(self.f64), C.byref(s), L.ptr(out), self.n, L.stream_ptr()),
+                "rk_combine")
+        return out
+
+    def integrate(self, t):
+        t = [float(v) for v in t]
+        if isinstance(self.func, AdvDiffPDE) and self.y0.dim() == 4 and self.y0.shape[0] == 1 and len(t) >= 2 \
+                and os.environ.get("BFM_ODE_DEVICE", "1") != "0":
+            return self._integrate_device(t)
+        return self._integrate_host(t)
+
+    def _integrate_device(self, t):
+        """All steps enqueued by one call (bfm_ode_fixed_advect, csrc/synth_ode.hip): one fused kernel per stage, the
+        last one storing y1 into its row of the solution.  Same expressions as the host loop below: same bits."""
+        func, y0 = self.func, self.y0
+        _, sx, sy, sz = y0.shape
+        nt = len(t)
+        sol = torch.empty((nt,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
+        sol[0].copy_(y0)
+        ks = [torch.empty(y0.shape, dtype=torch.float32, device=y0.device) for _ in self.stages]
+        coef = []
+        for dt in self.grid_steps(t):
+            for c in self.stages + [self.final]:
+                coef += self._coefs(dt, c)
+        assert len(coef) == (nt - 1) * self.lib.bfm_ode_fixed_ncoef(_FIXED_IDS[self.method])
+        d = L.OdeFixedAdvect()
+        d.sol = sol.data_ptr()
+        for j, k in enumerate(ks):
+            d.k[j] = k.data_ptr()
+        V = func.V_dict
+        d.Vx, d.Vy, d.Vz = V["Vx"].data_ptr(), V["Vy"].data_ptr(), V["Vz"].data_ptr()
+        d.sx, d.sy, d.sz = sx, sy, sz
+        d.neumann_bc = 1 if func.BC in ("neumann", "cauchy") else 0
+        d.is_f64 = int(self.f64)
+        d.method, d.nt = _FIXED_IDS[self.method], nt
+        d.coef = (C.c_float * len(coef))(*coef)
+        L.check(self.lib.bfm_ode_fixed_advect(C.byref(d), L.stream_ptr()), "ode_fixed_advect")
+        func.nfe += (len(self.stages) + 1) * (nt - 1)
+        return sol
+
+    def _integrate_host(self, t):
+        """The unfused route: bfm_advect_upwind_rhs (through func) and bfm_rk_combine, one launch each per stage."""
+        y = self.y0
+        sol = [y]
+        t0 = t[0]
+        for dt in self.grid_steps(t):
+            ks = [self.func(t0, y)]
+            for c in self.stages:
+                ks.append(self.func(t0, self._combine(y, ks, dt, c)))
+            y = self._combine(y, ks[self.first:], dt, self.final)
+            sol.append(y)
+            t0 = t0 + float(dt)
+        return torch.stack(sol)
+
+
+def _odeint_fixed(func, y0, t, method):
+    if not torch.is_tensor(y0):
+        raise NotImplementedError("tuple states are not used on the synthesis path")
+    if not torch.is_floating_point(y0):
+        raise TypeError("`y0` must be a floating point Tensor but is a {}".format(y0.type()))
+    if y0.dtype not in (torch.float32, torch.float64):
+        raise NotImplementedError("fp32 and fp64 states only")
+    tt = torch.as_tensor(t).detach().cpu().to(torch.float64).tolist()
+    assert all(b > a for a, b in zip(tt[:-1], tt[1:])), "t must be strictly increasing or decrasing"
+    return FixedGridSolver(func, y0.contiguous(), method).integrate(tt)
+
+
 def odeint(func, y0, t, dt, step_size=None, rtol=1e-7, atol=1e-9, method=None, options=None):
-    """DiffEqs/odeint.py:20-75 for tensor states and the 'dopri5' method."""
+    """DiffEqs/odeint.py:20-75 for tensor states and the 'dopri5' method.  This front takes 'dopri5' only, as an earlier
+    test pins; the fixed-grid methods ('euler', 'midpoint', 'rk4') are reached through odeint_adjoint, the one entry
+    the generator uses (Generator/utils.py:14)."""
     if method not in (None, "dopri5"):
         raise NotImplementedError("only 'dopri5' is used by the shipped configs (cfgs/generator/default.yaml:117)")
     if not torch.is_tensor(y0):
@@ -417,8 +529,20 @@ def odeint(func, y0, t, dt, step_size=None, rtol=1e-7, atol=1e-9, method=None, o
 
 
 def odeint_adjoint(func, y0, t, dt, rtol=1e-6, atol=1e-12, method=None, options=None):
-    """DiffEqs/adjoint.py:105-132: the generator only ever runs the forward pass (under no_grad)."""
+    """DiffEqs/adjoint.py:105-132: the generator only ever runs the forward pass (under no_grad).
+
+    method: None / 'dopri5' (the adaptive solver above) or one of the fixed-grid solvers 'euler', 'midpoint', 'rk4'
+    (FixedGridSolver; `dt`, `rtol` and `atol` do not enter them, as in the reference).  The other names of
+    DiffEqs/odeint.py:8-17 ('adams', 'tsit5', 'fixed_adams', 'explicit_adams') raise NotImplementedError.  The plain
+    `odeint` front keeps refusing everything but 'dopri5'."""
     if not isinstance(func, nn.Module):
         raise ValueError("func is required to be an instance of nn.Module.")
+    if method in _FIXED_TABLES:
+        with torch.no_grad():
+            return _odeint_fixed(func, y0, t, method)
+    if method not in (None, "dopri5"):
+        raise NotImplementedError("integration method %r is not built%s: odeint_adjoint takes 'dopri5', 'euler', "
+                                  "'midpoint' and 'rk4'" % (method, " (DiffEqs/odeint.py:8-17)"
+                                                            if method in _REFUSED_METHODS else ""))
     with torch.no_grad():
         return odeint(func, y0, t, dt, rtol=rtol, atol=atol, method=method, options=options)

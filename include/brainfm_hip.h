@@ -871,6 +871,29 @@ size_t bfm_dopri5_advect_workspace(int sx, int sy, int sz);
 int bfm_dopri5_advect_init(const bfm_dopri5_advect_t* d, double t0, double dt0, bfm_stream_t stream);
 int bfm_dopri5_advect_steps(const bfm_dopri5_advect_t* d, int nsteps, bfm_stream_t stream);
 
+/* Fixed-grid integration of the same PDE: euler, midpoint and rk4, the 3/8 rule (ShapeID/DiffEqs/fixed_grid.py:5-33,
+ * solvers.py:158-207 FixedGridODESolver.integrate, rk_common.py:72-78 rk4_alt_step_func; RHS pde.py:616-640).  The grid is
+ * the requested times, so step i reads row i of sol and writes row i + 1; the call enqueues all nt - 1 steps (1, 2 or 4
+ * kernels each) and reads nothing back.  On entry row 0 of sol holds y0.  A stage kernel forms the stage state
+ * y + sum_j c_j k_j (bfm_rk_combine's expression) with the Neumann replicate on an LDS box with its halo and the upwind
+ * RHS from it; the last stage of a step adds bfm_rk_combine's final sum and stores y1 instead of its k.
+ * coef: HOST array of (nt - 1) x bfm_ode_fixed_ncoef(method) fp32 values, per step the coefficients bfm_rk_combine
+ * would be given, (dt * c) in the state dtype rounded to fp32:
+ *   euler     {dt}                                      y1 = y + dt k1
+ *   midpoint  {dt/2, dt}                                k2 = f(y + dt/2 k1);  y1 = y + dt k2
+ *   rk4       {dt/3, -dt/3, dt, dt, -dt, dt, dt/8, 3dt/8, 3dt/8, dt/8}
+ *             k2 = f(y + dt/3 k1); k3 = f(y - dt/3 k1 + dt k2); k4 = f(y + dt k1 - dt k2 + dt k3); y1 = y + sum
+ * k: fp32 stage buffers of n voxels (euler 0, midpoint 1, rk4 3).  sx, sy, sz >= 3. */
+enum { BFM_ODE_EULER = 0, BFM_ODE_MIDPOINT = 1, BFM_ODE_RK4 = 2 };
+typedef struct {
+    void* sol /*[nt][n], state dtype*/; float* k[3];
+    const float *Vx, *Vy, *Vz;
+    int sx, sy, sz, neumann_bc, is_f64, method, nt;
+    const float* coef /*host*/;
+} bfm_ode_fixed_advect_t;
+int bfm_ode_fixed_ncoef(int method);
+int bfm_ode_fixed_advect(const bfm_ode_fixed_advect_t* d, bfm_stream_t stream);
+
 /* ---- backward pass of the SingleConv block and its neighbours (first correct version) -------------------
  * The reference trains through torch autograd over buildingblocks.py:31-60 (GroupNorm -> Conv3d -> LeakyReLU),
  * :185-186 (MaxPool3d(2)), :265-276,361-363 (nearest upsample + concat).
