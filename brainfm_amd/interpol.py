@@ -10,6 +10,10 @@ grid_pull / grid_push are differentiable to first order through grid_push / grid
 ``grid_pushgrad`` and ``grid_hess`` (pushpull.py:176-233 and :303-325; nd.py:291-464, iso1.py:390-675, iso0.py:326-368)
 on grid_hess.hip, which takes every order 0 to 3 in one export per operation.  Nothing here has a double backward, as in
 the reference.
+
+``grid_pull`` of an integer image is the reference's label branch (api.py:182-193) in one pass of label_pull.hip.  The grid
+builders ``identity_grid`` / ``add_identity_grid`` / ``add_identity_grid_`` / ``affine_grid`` (api.py:455-560) run on
+grid_builders.hip, and ``spline_coeff`` (api.py:335-383) filters one dimension on the prefilter kernels.
 """
 import ctypes as C
 
@@ -312,15 +316,62 @@ def grid_pushgrad(input, grid, shape=None, interpolation="linear", bound="zero",
     return out.reshape(*batch, *out_channel, *shape)
 
 
+_LABEL_DTYPE = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}      # BFM_LABEL_* of include/brainfm_hip.h
+LABEL_PULL_AUTO, LABEL_PULL_LDS, LABEL_PULL_REGS, LABEL_PULL_PASSES = 0, 1, 2, 3         # BFM_LABEL_PULL_*
+
+
+def _label_pull_raw(x, g, b, o, ext, variant=LABEL_PULL_AUTO):
+    """x (Bi,C,*in) uint8 / int16 / int32 / int64, g (Bg,*out,3) fp32, both contiguous -> (B,C,*out) of x's dtype"""
+    Bi, Cc = x.shape[0], x.shape[1]
+    Bg = g.shape[0]
+    gs = tuple(g.shape[1:4])
+    out = torch.empty((max(Bi, Bg), Cc) + gs, dtype=x.dtype, device=x.device)
+    L.check(L.load().bfm_label_pull3d(L.ptr(x), _LABEL_DTYPE[x.dtype], Bi, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g),
+                                      Bg, gs[0], gs[1], gs[2], b, (C.c_int * 3)(*o), ext, variant, L.ptr(out),
+                                      L.stream_ptr()), "label_pull3d")
+    return out
+
+
+def _label_pull(input, grid, b, o, ext, prefilter):
+    """api.py:182-193: an integer image holds labels, and labels are not interpolated.  The result holds, per output
+    voxel, the label whose indicator has the largest interpolated weight at the call's orders, bounds and `extrapolate`
+    (the smallest label among equal weights, 0 where no weight is positive), in one pass of label_pull.hip instead of
+    one pull per label.  Same dtype as the image, no gradient."""
+    if input.dtype == torch.bool:
+        raise TypeError("grid_pull: a bool image is neither an image nor a label map; cast it to a float dtype to "
+                        "interpolate it or to uint8 to pull it as labels")
+    if input.dtype not in _LABEL_DTYPE:
+        raise TypeError("grid_pull: label maps are uint8, int16, int32 or int64, not %s" % input.dtype)
+    if prefilter:
+        raise NotImplementedError("grid_pull: prefilter=True is not implemented for an integer (label) image: the "
+                                  "reference overwrites its own input with the first label's coefficients there and has "
+                                  "no defined result")
+    _require_cuda(input, "grid_pull")
+    dim = 3
+    grid_spatial = tuple(grid.shape[-dim - 1:-1])
+    in_spatial = tuple(input.shape[-dim:])
+    channel = 0 if input.dim() == dim else input.shape[-dim - 1]
+    in_batch = tuple(input.shape[:-dim - 1]) if input.dim() > dim else ()
+    batch = torch.broadcast_shapes(tuple(grid.shape[:-dim - 1]), in_batch)
+    g = grid.detach().to(torch.float32).expand(*batch, *grid_spatial, dim).reshape(-1, *grid_spatial, dim).contiguous()
+    x = input.expand(*batch, channel or 1, *in_spatial).reshape(-1, channel or 1, *in_spatial).contiguous()
+    out = _label_pull_raw(x, g, b, o, ext)
+    out_channel = [channel] if channel else ([1] if batch else [])
+    return out.reshape(*batch, *out_channel, *grid_spatial)
+
+
 def grid_pull(input, grid, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):
-    """Sample `input` at the voxel coordinates in `grid` (api.py:137-200; an integer image is sampled as values, not label by label).
+    """Sample `input` at the voxel coordinates in `grid` (api.py:137-200).
 
     input: (..., [channel], *spatial) ; grid: (..., *spatial_out, 3).  Returns (..., [channel], *spatial_out).
     Computes in fp32 like the reference's custom_fwd(cast_inputs=torch.float32).  `prefilter` turns the image into
-    spline coefficients first, so that the result interpolates it."""
+    spline coefficients first, so that the result interpolates it.  An integer image (uint8, int16, int32, int64) is a
+    label map: the result has its dtype and holds the label with the largest interpolated weight (_label_pull)."""
     b, o, ext = _opts(interpolation, bound, extrapolate)
     if grid.shape[-1] != 3:
         raise NotImplementedError("only 3-D grids are on the hot path")
+    if not input.dtype.is_floating_point:
+        return _label_pull(input, grid, b, o, ext, prefilter)
     prefilter = _needs_prefilter(prefilter, o, list(b), input.shape[-3:])
     if input.device.type != "cuda":
         raise L.BfmError("grid_pull runs on a HIP device only; there is no CPU fallback in the product path")
@@ -425,6 +476,162 @@ def spline_coeff_nd(input, interpolation="linear", bound="dct2", dim=None, inpla
     if torch.is_grad_enabled() and inp.requires_grad:
         return _SplineCoeffND.apply(inp, orders, bounds)
     return _coeff_raw(inp, orders, bounds, inplace)
+
+
+def _coeff_axis_raw(inp, order, bound, dim):
+    """The prefilter of _coeff_raw along one dimension of a tensor of any rank: the contiguous fp32 tensor is the volume
+    (everything before `dim`, the length of `dim`, everything behind it) filtered along its middle axis, one launch.
+    Filters `inp` itself if it is contiguous fp32, a copy otherwise; returns what it filtered."""
+    x = inp.to(torch.float32).contiguous()
+    n = x.shape[dim]
+    if n > 1 and x.numel():
+        outer = 1
+        for s in x.shape[:dim]:
+            outer *= s
+        inner = x.numel() // (outer * n)
+        z, gain, pole_last, init_scale, final_scale, wd, max_iter = _prefilter_scalars_dev(
+            n, x.device, order, _PREFILTER_FAMILY[bound])
+        dims, axis = ((1, outer, n), 2) if inner == 1 else ((outer, n, inner), 1)
+        L.check(L.load().bfm_bspline3_prefilter_axis(L.ptr(x), dims[0], dims[1], dims[2], axis, bound, z, gain, L.ptr(wd),
+                                                     pole_last, init_scale, final_scale, max_iter, L.stream_ptr()),
+                "bspline3_prefilter")
+    return x
+
+
+class _SplineCoeff(torch.autograd.Function):
+    """autograd.py:249-273: the filter is symmetric, so its backward is the same filter applied to the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, order, bound, dim):
+        ctx.opt = (order, bound, dim, x.dtype)
+        return _coeff_axis_raw(x.detach().clone(), order, bound, dim).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, grad):
+        order, bound, dim, dtype = ctx.opt
+        return _coeff_axis_raw(grad.clone(), order, bound, dim).to(dtype), None, None, None
+
+
+def spline_coeff(input, interpolation="linear", bound="dct2", dim=-1, inplace=False):
+    """utils/interpol/api.py:335-383 -> coeff.py:254-310: the interpolating spline coefficients along the one dimension
+    `dim` of a tensor of any rank, for one order and one bound.  Orders 2 and 3 under the DCT-I ('zero' / 'dct1'), DCT-II
+    ('nearest' / 'dct2') or DFT ('dft') conditions, on the prefilter kernels of spline_coeff_nd (fp32 arithmetic; the
+    result has the input's dtype); orders 0 and 1 return the input (a clone unless `inplace`).  'dst1' / 'dst2' and
+    orders 4 to 7 raise as in spline_coeff_nd.  Differentiable (autograd.py:249-273); `inplace` holds only for a tensor
+    that needs no gradient."""
+    orders = interpolation if isinstance(interpolation, (list, tuple)) else [interpolation]
+    bounds = bound if isinstance(bound, (list, tuple)) else [bound]
+    if len(orders) != 1 or len(bounds) != 1:
+        raise ValueError("spline_coeff takes one interpolation order and one bound (spline_coeff_nd takes one per dimension)")
+    order = _order_list(orders[0])[0]
+    b = _bound_list(bounds[0])[0]
+    if not -input.dim() <= dim < input.dim():
+        raise IndexError("Dimension out of range (expected to be in range of [%d, %d], but got %d)"
+                         % (-input.dim(), input.dim() - 1, dim))
+    dim = dim % input.dim()
+    _check_prefilter_bounds((order,), (b,), (input.shape[dim],))
+    if input.device.type != "cuda":
+        raise L.BfmError("spline_coeff runs on a HIP device only")
+    if order < 2:
+        return input if inplace else input.clone()
+    if not input.dtype.is_floating_point:
+        input, inplace = input.to(torch.float32), False
+    if torch.is_grad_enabled() and input.requires_grad:
+        return _SplineCoeff.apply(input, order, b, dim)
+    if not inplace:
+        return _coeff_axis_raw(input.clone(), order, b, dim).to(input.dtype)
+    res = _coeff_axis_raw(input, order, b, dim)
+    if res.data_ptr() != input.data_ptr():                        # not contiguous fp32: filtered in a copy
+        input.copy_(res)
+    return input
+
+
+# ----------------------------------------------------------------------------- grid builders (api.py:455-560)
+def _builder_dtype(dtype):
+    dtype = torch.get_default_dtype() if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("grid builders: float32 or float64, not %s" % dtype)
+    return dtype
+
+
+def _affine_raw(mat, nb, shape, dtype, device):
+    """mat (nb,3,4) contiguous on the device, or None for the identity -> (nb,*shape,3)"""
+    out = torch.empty((nb,) + tuple(shape) + (3,), dtype=dtype, device=device)
+    if out.numel():
+        L.check(L.load().bfm_affine_grid3d(L.ptr(mat), int(dtype == torch.float64), nb, shape[0], shape[1], shape[2],
+                                           L.ptr(out), L.stream_ptr()), "affine_grid3d")
+    return out
+
+
+def identity_grid(shape, dtype=None, device=None):
+    """api.py:455-476: the (*shape, dim) grid of voxel indices, dim = len(shape).  3-D shapes are written by one kernel
+    (no meshgrid); 1-D and 2-D shapes, which no kernel of this package reads, are built with torch on the device."""
+    shape = tuple(int(s) for s in shape)
+    dtype = _builder_dtype(dtype)
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise L.BfmError("identity_grid runs on a HIP device only; there is no CPU fallback in the product path")
+    if len(shape) != 3:
+        mesh = torch.meshgrid(*[torch.arange(s, dtype=dtype, device=device) for s in shape], indexing="ij")
+        return torch.stack(mesh, dim=-1)
+    with torch.cuda.device(device):
+        return _affine_raw(None, 1, shape, dtype, device)[0]
+
+
+def add_identity_grid_(disp):
+    """api.py:479-503: adds the voxel index to a displacement field (..., *spatial, dim) in place and returns it."""
+    dim = disp.shape[-1]
+    if disp.dim() < dim + 1:
+        raise ValueError("add_identity_grid_: a (..., *spatial, %d) field has at least %d dimensions" % (dim, dim + 1))
+    _require_cuda(disp, "add_identity_grid_")
+    if dim != 3:
+        for i, s in enumerate(disp.shape[-dim - 1:-1]):
+            view = [1] * dim
+            view[i] = s
+            disp[..., i].add_(torch.arange(s, dtype=disp.dtype, device=disp.device).reshape(view))
+        return disp
+    _builder_dtype(disp.dtype)
+    work = disp if disp.is_contiguous() else disp.contiguous()
+    if work.numel():
+        nx, ny, nz = work.shape[-4:-1]
+        L.check(L.load().bfm_add_identity_grid3d(L.ptr(work), int(work.dtype == torch.float64), work.numel() // (nx * ny * nz * 3),
+                                                 nx, ny, nz, L.stream_ptr()), "add_identity_grid3d")
+    if work is not disp:
+        disp.copy_(work)
+    return disp
+
+
+def add_identity_grid(disp):
+    """api.py:506-521: add_identity_grid_ on a copy."""
+    _require_cuda(disp, "add_identity_grid")
+    return add_identity_grid_(disp.clone(memory_format=torch.contiguous_format))
+
+
+def affine_grid(mat, shape):
+    """api.py:524-560: the dense grid (..., *shape, D) of an affine matrix (..., D[+1], D+1): lin @ index + offset per
+    voxel, in the reference's summation order.  Batched matrices give one grid per matrix (the reference means to, its
+    docstring says so, but raises on them).  3-D on one kernel, 1-D / 2-D with torch on the device."""
+    mat = torch.as_tensor(mat)
+    shape = [int(s) for s in shape]
+    nb_dim = mat.shape[-1] - 1
+    if nb_dim != len(shape):
+        raise ValueError("Dimension of the affine matrix ({}) and shape ({}) are not the same.".format(nb_dim, len(shape)))
+    if mat.dim() < 2 or mat.shape[-2] not in (nb_dim, nb_dim + 1):
+        raise ValueError("First argument should be matrices of shape (..., {0}, {1}) or (..., {1}, {1}) but got {2}."
+                         .format(nb_dim, nb_dim + 1, tuple(mat.shape)))
+    _require_cuda(mat, "affine_grid")
+    batch = tuple(mat.shape[:-2])
+    if nb_dim != 3:
+        grid = identity_grid(shape, mat.dtype, mat.device)
+        lin = mat[..., :nb_dim, :nb_dim].reshape(batch + (1,) * nb_dim + (nb_dim, nb_dim))
+        off = mat[..., :nb_dim, -1].reshape(batch + (1,) * nb_dim + (nb_dim,))
+        return torch.matmul(lin, grid[..., None])[..., 0] + off
+    dtype = _builder_dtype(mat.dtype)
+    m = mat[..., :3, :].reshape(-1, 3, 4).contiguous()
+    if m.shape[0] == 0:
+        return torch.empty(batch + tuple(shape) + (3,), dtype=dtype, device=mat.device)
+    with torch.cuda.device(mat.device):
+        return _affine_raw(m, m.shape[0], shape, dtype, mat.device).reshape(batch + tuple(shape) + (3,))
 
 
 def _make_list(x, n=None):

@@ -680,6 +680,36 @@ int bfm_spline_axis_table(const float* coord, int m, int n, int order, int bound
                           size_t workspace_bytes, bfm_stream_t stream);
 int bfm_spline_axis_pass(const float* in, int64_t lead, int nx, int ny, int nz, int axis, const int32_t* rowptr,
                          const int32_t* col, const float* val, int n_out, float* out, bfm_stream_t stream);
+/* interpol.grid_pull on an integer image, the label branch of utils/interpol/api.py:182-193: the reference pulls the
+ * indicator of every label of unique() and keeps per output voxel the label with the largest interpolated weight.  Here
+ * in one pass over the output: w_L = the sum over the taps of the voxel's footprint that hold L of weight * bound sign
+ * (nodes, signs, weights, mask and argument checks of the _spline exports above; fp32, fixed tap order), out = the label
+ * with the largest w_L > 0, the smallest label among equal sums (the reference walks the labels in ascending order and
+ * replaces on a strict >), 0 where no sum is positive (outside the field of view without extrapolation, outside a `zero`
+ * bound, a footprint of negative `dst1` / `dst2` taps).  The cost does not depend on the number of labels.
+ * inp (Bi,C,nx,ny,nz) and out (max(Bi,Bg),C,ox,oy,oz) have the element type `dtype`; grid (Bg,ox,oy,oz,3) fp32.
+ * variant: how the thread keeps its (label, sum) table -- AUTO: REGS for the all-nearest / all-linear footprints (1 / 8
+ * taps), PASSES otherwise; LDS (a per-thread LDS slice), REGS (the footprint in registers, rescanned per tap) and PASSES
+ * (four register slots, the footprint walked again while labels are left) force one for every order (measurements).
+ * All give the same bits. */
+#define BFM_LABEL_U8 0
+#define BFM_LABEL_I16 1
+#define BFM_LABEL_I32 2
+#define BFM_LABEL_I64 3
+#define BFM_LABEL_PULL_AUTO 0
+#define BFM_LABEL_PULL_LDS 1
+#define BFM_LABEL_PULL_REGS 2
+#define BFM_LABEL_PULL_PASSES 3
+int bfm_label_pull3d(const void* inp, int dtype, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox,
+                     int oy, int oz, const int* bound, const int* order, int extrapolate, int variant, void* out,
+                     bfm_stream_t stream);
+/* interpol.identity_grid / affine_grid / add_identity_grid_ in 3-D -- utils/interpol/api.py:455-560.
+ * affine_grid3d: out (nb,nx,ny,nz,3), out[b,x,y,z,r] = ((m[r][0] * x + m[r][1] * y) + m[r][2] * z) + m[r][3] with m =
+ *   mat[b] (nb,3,4 row-major, device), the summation order of the reference's matvec(lin, idx) + off, every product and
+ *   sum rounded on its own; mat NULL: the identity grid (x, y, z).  add_identity_grid3d: disp (nb,nx,ny,nz,3) += (x, y, z)
+ *   in place.  is_f64 0: fp32, otherwise fp64.  Bit-equal to the reference in both. */
+int bfm_affine_grid3d(const void* mat, int is_f64, int64_t nb, int nx, int ny, int nz, void* out, bfm_stream_t stream);
+int bfm_add_identity_grid3d(void* disp, int is_f64, int64_t nb, int nx, int ny, int nz, bfm_stream_t stream);
 /* BaseGen.deform_grid -- Generator/datasets.py:264-303: (xc+F) -> A*. + c2, clamp to the source shape, and the
  * six global min/max (minmax = {min x,y,z, max x,y,z}, device).  F is [n][3] or NULL. */
 size_t bfm_deform_grid_workspace(int sx, int sy, int sz);
