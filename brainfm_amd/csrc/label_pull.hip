@@ -3,7 +3,7 @@
 // weight is the largest (strict >, labels in ascending order, so the smallest label wins a tie; 0 where no weight is
 // positive).  The weight of a label at a voxel is the sum, over the taps of the voxel's footprint that hold the label, of
 // the separable spline weight times the bound sign -- it depends on the at most 64 taps only.  So: one pass, one thread per
-// output voxel, nodes / signs / weights of axis_nodes (spline_nodes.h) exactly as in spline_grid.hip, the labels of the
+// output voxel, prologue and nodes / signs / weights (grid_kernels.h, spline_nodes.h) those of spline_grid.hip, the labels of the
 // footprint gathered with ld_tex loads of the label's own width (an int64 label as two 4-byte halves), and the per-label
 // sums and the winner formed inside the thread.  No one-hot, no per-label volume, no unique(): the cost does not depend on
 // the number of labels of the image.
@@ -27,23 +27,9 @@
 //           cubic footprint, 12 passes) it is still 1.9 times slower at 64 taps and 0.82 times as slow at 27.
 // `variant` of the export forces one for measurements (scripts/bench_label_pull.py, profiles/label_pull.txt, where the
 // choice of AUTO comes from).  All give the same bits.
-#include "bfm_common.h"
-#include "gather3d.h"
-#include "interp_bounds.h"
-#include "spline_nodes.h"
+#include "grid_kernels.h"
 
 namespace {
-
-inline int grid_for(int64_t n, int tpb, int cap) {
-    int64_t b = bfm_cdiv64(n, tpb);
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-#define GRID_STRIDE(i, n) \
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-struct Orders { int o[3]; };
-struct Bounds { int b[3]; };
 
 // label loads under the texel policy of gather3d.h (agent scope: past the vector L1); K is the type labels are compared in
 template <typename LT> struct Key { typedef int32_t type; };
@@ -64,45 +50,27 @@ __device__ __forceinline__ int64_t ld_label(const int64_t* p) {
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
-// node k of one axis for a run-time k: axis_nodes (spline_nodes.h) one node at a time, the same arithmetic and the same
-// bits.  The kernels that walk the footprint slab by slab in a rolled loop take their x nodes from here: an array of
-// nodes read at a run-time index would go to scratch.
-__device__ __forceinline__ void axis_node(float g, int order, int n, int b, int k, int& idx, float& w) {
-    const float g0f = floorf(g - 0.5f * (float)(order - 1));
-    const float dist0 = g - g0f;
-    const int g0 = (int)fminf(fmaxf(g0f, -1073741824.f), 1073741824.f);
-    const bool used = k <= order;
-    const int node = used ? g0 + k : g0;
-    const float s = used ? (float)bound_sign(node, n, b) : 0.f;
-    idx = bound_index(node, n, b);
-    w = spline_weight(order, dist0 - (float)k) * s;
-}
-
-// O = 0, 1, 2, 3: isotropic order O with O + 1 taps per axis; O < 0: per-axis orders from `ord`, 4 taps per axis
+// O = 0, 1, 2, 3: isotropic order O with O + 1 taps per axis; O < 0: per-axis orders from `op`, 4 taps per axis
 template <int O, typename LT>
 __global__ void __launch_bounds__(256) label_pull3d_regs(const LT* __restrict__ inp, int Bi, int C, int nx, int ny, int nz,
-                                                         const float* __restrict__ grid, int Bg, int64_t nout, Bounds bd,
-                                                         Orders ord, int extrap, int B, LT* __restrict__ out) {
+                                                         const float* __restrict__ grid, int Bg, int64_t nout,
+                                                         GridOpts op, int B, LT* __restrict__ out) {
     typedef typename Key<LT>::type K;
-    constexpr int T = O < 0 ? 4 : O + 1, N = T * T * T;
-    const int ox = O < 0 ? ord.o[0] : O, oy = O < 0 ? ord.o[1] : O, oz = O < 0 ? ord.o[2] : O;
+    constexpr int T = grid_taps(O), N = T * T * T;
+    const int ox = axis_order<O>(op, 0), oy = axis_order<O>(op, 1), oz = axis_order<O>(op, 2);
     const int64_t n = (int64_t)B * nout;
     const int64_t vol = (int64_t)nx * ny * nz;
     GRID_STRIDE(i, n) {
-        const int b = (int)(i / nout);
-        const int64_t v = i - (int64_t)b * nout;
-        const float* g = grid + ((int64_t)(Bg == 1 ? 0 : b) * nout + v) * 3;
-        const float gx = ld_tex(g), gy = ld_tex(g + 1), gz = ld_tex(g + 2);
-        const float mask = inbounds(gx, gy, gz, nx, ny, nz, extrap);
+        const GridVoxel p = grid_voxel(i, nout, grid, Bg, nx, ny, nz, op.extrap);
         int ix[T], iy[T], iz[T];
-        float wx[T], wy[T], wz[T], unused[T];
-        axis_nodes<T, false>(gx, ox, nx, bd.b[0], ix, wx, unused);
-        axis_nodes<T, false>(gy, oy, ny, bd.b[1], iy, wy, unused);
-        axis_nodes<T, false>(gz, oz, nz, bd.b[2], iz, wz, unused);
+        float wx[T], wy[T], wz[T];
+        axis_nodes<T>(p.gx, ox, nx, op.bound[0], ix, wx);
+        axis_nodes<T>(p.gy, oy, ny, op.bound[1], iy, wy);
+        axis_nodes<T>(p.gz, oz, nz, op.bound[2], iz, wz);
         for (int c = 0; c < C; ++c) {
-            LT* dst = out + ((int64_t)b * C + c) * nout + v;
-            if (mask == 0.f) { *dst = (LT)0; continue; }
-            const LT* src = inp + ((int64_t)(Bi == 1 ? 0 : b) * C + c) * vol;
+            LT* dst = out + ((int64_t)p.b * C + c) * nout + p.v;
+            if (p.mask == 0.f) { *dst = (LT)0; continue; }
+            const LT* src = inp + ((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * vol;
             K lab[N];
             float w[N];
 #pragma unroll
@@ -133,36 +101,32 @@ __global__ void __launch_bounds__(256) label_pull3d_regs(const LT* __restrict__ 
 
 template <int O, typename LT>
 __global__ void __launch_bounds__(64) label_pull3d_lds(const LT* __restrict__ inp, int Bi, int C, int nx, int ny, int nz,
-                                                       const float* __restrict__ grid, int Bg, int64_t nout, Bounds bd,
-                                                       Orders ord, int extrap, int B, LT* __restrict__ out) {
+                                                       const float* __restrict__ grid, int Bg, int64_t nout,
+                                                       GridOpts op, int B, LT* __restrict__ out) {
     typedef typename Key<LT>::type K;
-    constexpr int T = O < 0 ? 4 : O + 1, N = T * T * T;
+    constexpr int T = grid_taps(O), N = T * T * T;
     __shared__ K keys[N * 64];
     __shared__ float sums[N * 64];
     const int lane = threadIdx.x;
-    const int ox = O < 0 ? ord.o[0] : O, oy = O < 0 ? ord.o[1] : O, oz = O < 0 ? ord.o[2] : O;
+    const int ox = axis_order<O>(op, 0), oy = axis_order<O>(op, 1), oz = axis_order<O>(op, 2);
     const int64_t n = (int64_t)B * nout;
     const int64_t vol = (int64_t)nx * ny * nz;
     GRID_STRIDE(i, n) {
-        const int b = (int)(i / nout);
-        const int64_t v = i - (int64_t)b * nout;
-        const float* g = grid + ((int64_t)(Bg == 1 ? 0 : b) * nout + v) * 3;
-        const float gx = ld_tex(g), gy = ld_tex(g + 1), gz = ld_tex(g + 2);
-        const float mask = inbounds(gx, gy, gz, nx, ny, nz, extrap);
+        const GridVoxel p = grid_voxel(i, nout, grid, Bg, nx, ny, nz, op.extrap);
         int iy[T], iz[T];                                          // the x nodes: axis_node, slab by slab
-        float wy[T], wz[T], unused[T];
-        axis_nodes<T, false>(gy, oy, ny, bd.b[1], iy, wy, unused);
-        axis_nodes<T, false>(gz, oz, nz, bd.b[2], iz, wz, unused);
+        float wy[T], wz[T];
+        axis_nodes<T>(p.gy, oy, ny, op.bound[1], iy, wy);
+        axis_nodes<T>(p.gz, oz, nz, op.bound[2], iz, wz);
         for (int c = 0; c < C; ++c) {
-            LT* dst = out + ((int64_t)b * C + c) * nout + v;
-            if (mask == 0.f) { *dst = (LT)0; continue; }
-            const LT* src = inp + ((int64_t)(Bi == 1 ? 0 : b) * C + c) * vol;
+            LT* dst = out + ((int64_t)p.b * C + c) * nout + p.v;
+            if (p.mask == 0.f) { *dst = (LT)0; continue; }
+            const LT* src = inp + ((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * vol;
             int cnt = 0;                                           // entries of this thread's table, at most N
 #pragma unroll 1
             for (int a = 0; a < T; ++a) {                          // rolled: one x-slab of the footprint at a time
                 int ixa;
                 float wxa;
-                axis_node(gx, ox, nx, bd.b[0], a, ixa, wxa);
+                axis_node(p.gx, ox, nx, op.bound[0], a, ixa, wxa);
                 K lab[T * T];                                      // its loads go out together
 #pragma unroll
                 for (int bb = 0; bb < T; ++bb) {
@@ -211,27 +175,23 @@ __global__ void __launch_bounds__(64) label_pull3d_lds(const LT* __restrict__ in
 // 16 for the 64 distinct labels of the worst case.  Slots are addressed by constants (selects), never by a run-time index.
 template <int O, typename LT>
 __global__ void __launch_bounds__(256) label_pull3d_passes(const LT* __restrict__ inp, int Bi, int C, int nx, int ny, int nz,
-                                                           const float* __restrict__ grid, int Bg, int64_t nout, Bounds bd,
-                                                           Orders ord, int extrap, int B, LT* __restrict__ out) {
+                                                           const float* __restrict__ grid, int Bg, int64_t nout,
+                                                           GridOpts op, int B, LT* __restrict__ out) {
     typedef typename Key<LT>::type K;
-    constexpr int T = O < 0 ? 4 : O + 1, S = 4;
-    const int ox = O < 0 ? ord.o[0] : O, oy = O < 0 ? ord.o[1] : O, oz = O < 0 ? ord.o[2] : O;
+    constexpr int T = grid_taps(O), S = 4;
+    const int ox = axis_order<O>(op, 0), oy = axis_order<O>(op, 1), oz = axis_order<O>(op, 2);
     const int64_t n = (int64_t)B * nout;
     const int64_t vol = (int64_t)nx * ny * nz;
     GRID_STRIDE(i, n) {
-        const int b = (int)(i / nout);
-        const int64_t v = i - (int64_t)b * nout;
-        const float* g = grid + ((int64_t)(Bg == 1 ? 0 : b) * nout + v) * 3;
-        const float gx = ld_tex(g), gy = ld_tex(g + 1), gz = ld_tex(g + 2);
-        const float mask = inbounds(gx, gy, gz, nx, ny, nz, extrap);
+        const GridVoxel p = grid_voxel(i, nout, grid, Bg, nx, ny, nz, op.extrap);
         int iy[T], iz[T];                                          // the x nodes: axis_node, slab by slab
-        float wy[T], wz[T], unused[T];
-        axis_nodes<T, false>(gy, oy, ny, bd.b[1], iy, wy, unused);
-        axis_nodes<T, false>(gz, oz, nz, bd.b[2], iz, wz, unused);
+        float wy[T], wz[T];
+        axis_nodes<T>(p.gy, oy, ny, op.bound[1], iy, wy);
+        axis_nodes<T>(p.gz, oz, nz, op.bound[2], iz, wz);
         for (int c = 0; c < C; ++c) {
-            LT* dst = out + ((int64_t)b * C + c) * nout + v;
-            if (mask == 0.f) { *dst = (LT)0; continue; }
-            const LT* src = inp + ((int64_t)(Bi == 1 ? 0 : b) * C + c) * vol;
+            LT* dst = out + ((int64_t)p.b * C + c) * nout + p.v;
+            if (p.mask == 0.f) { *dst = (LT)0; continue; }
+            const LT* src = inp + ((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * vol;
             K best_l = 0;
             float best = 0.f;
             bool have_floor = false;
@@ -247,7 +207,7 @@ __global__ void __launch_bounds__(256) label_pull3d_passes(const LT* __restrict_
                 for (int a = 0; a < T; ++a) {                      // rolled: one x-slab of the footprint at a time
                     int ixa;
                     float wxa;
-                    axis_node(gx, ox, nx, bd.b[0], a, ixa, wxa);
+                    axis_node(p.gx, ox, nx, op.bound[0], a, ixa, wxa);
                     K lab[T * T];
 #pragma unroll
                     for (int bb = 0; bb < T; ++bb) {
@@ -311,30 +271,29 @@ __global__ void __launch_bounds__(256) label_pull3d_passes(const LT* __restrict_
 
 template <int O, typename LT>
 void launch_one(int how, int64_t n, hipStream_t s, const LT* inp, int Bi, int C, int nx, int ny, int nz, const float* grid,
-                int Bg, int64_t nout, Bounds bd, Orders od, int extrap, int B, LT* out) {
+                int Bg, int64_t nout, GridOpts op, int B, LT* out) {
     if (how == BFM_LABEL_PULL_LDS)
         hipLaunchKernelGGL((label_pull3d_lds<O, LT>), dim3(grid_for(n, 64, 32768)), dim3(64), 0, s, inp, Bi, C, nx, ny, nz, grid,
-                           Bg, nout, bd, od, extrap, B, out);
+                           Bg, nout, op, B, out);
     else if (how == BFM_LABEL_PULL_REGS)
-        hipLaunchKernelGGL((label_pull3d_regs<O, LT>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, inp, Bi, C, nx, ny, nz,
-                           grid, Bg, nout, bd, od, extrap, B, out);
+        hipLaunchKernelGGL((label_pull3d_regs<O, LT>), dim3(grid_for(n)), dim3(256), 0, s, inp, Bi, C, nx, ny, nz, grid, Bg,
+                           nout, op, B, out);
     else
-        hipLaunchKernelGGL((label_pull3d_passes<O, LT>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, inp, Bi, C, nx, ny,
-                           nz, grid, Bg, nout, bd, od, extrap, B, out);
+        hipLaunchKernelGGL((label_pull3d_passes<O, LT>), dim3(grid_for(n)), dim3(256), 0, s, inp, Bi, C, nx, ny, nz, grid, Bg,
+                           nout, op, B, out);
 }
 
+// every isotropic order has its own instantiation; AUTO: regs for 1 and 8 taps, passes for 27 and 64
 template <typename LT>
-void launch_dtype(int iso, int variant, int64_t n, hipStream_t s, const void* inp, int Bi, int C, int nx, int ny, int nz,
-                  const float* grid, int Bg, int64_t nout, Bounds bd, Orders od, int extrap, int B, void* out) {
-    const LT* in = static_cast<const LT*>(inp);
-    LT* o = static_cast<LT*>(out);
-    const int how = variant != BFM_LABEL_PULL_AUTO ? variant
-                                                   : ((iso == 0 || iso == 1) ? BFM_LABEL_PULL_REGS : BFM_LABEL_PULL_PASSES);
-    if (iso == 0) launch_one<0, LT>(how, n, s, in, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrap, B, o);
-    else if (iso == 1) launch_one<1, LT>(how, n, s, in, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrap, B, o);
-    else if (iso == 2) launch_one<2, LT>(how, n, s, in, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrap, B, o);
-    else if (iso == 3) launch_one<3, LT>(how, n, s, in, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrap, B, o);
-    else launch_one<-1, LT>(how, n, s, in, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrap, B, o);
+void launch_dtype(int variant, hipStream_t s, const void* inp, int Bi, int C, int nx, int ny, int nz, const float* grid,
+                  int Bg, int64_t nout, GridOpts op, int B, void* out) {
+    dispatch_order<0, 1, 2, 3>(op.order, [&](auto o) {
+        constexpr int O = decltype(o)::value;
+        const int how = variant != BFM_LABEL_PULL_AUTO ? variant
+                                                       : ((O == 0 || O == 1) ? BFM_LABEL_PULL_REGS : BFM_LABEL_PULL_PASSES);
+        launch_one<O, LT>(how, B * nout, s, static_cast<const LT*>(inp), Bi, C, nx, ny, nz, grid, Bg, nout, op, B,
+                          static_cast<LT*>(out));
+    });
 }
 
 }  // namespace
@@ -342,25 +301,19 @@ void launch_dtype(int iso, int variant, int64_t n, hipStream_t s, const void* in
 extern "C" int bfm_label_pull3d(const void* inp, int dtype, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg,
                                 int ox, int oy, int oz, const int* bound, const int* order, int extrapolate, int variant,
                                 void* out, bfm_stream_t stream) {
-    if (!inp || !grid || !out || !bound || !order || Bi <= 0 || Bg <= 0 || C <= 0 || nx <= 0 || ny <= 0 || nz <= 0 ||
-        ox <= 0 || oy <= 0 || oz <= 0)
-        return BFM_E_ARG;
-    if (Bi != Bg && Bi != 1 && Bg != 1) return BFM_E_SHAPE;
-    for (int a = 0; a < 3; ++a) if (bound[a] < 0 || bound[a] > 6 || order[a] < 0 || order[a] > 3) return BFM_E_ARG;
-    if (extrapolate < 0 || extrapolate > 2 || dtype < BFM_LABEL_U8 || dtype > BFM_LABEL_I64) return BFM_E_ARG;
+    const int rc = grid_check_args(inp, grid, out, bound, order, Bi, Bg, C, nx, ny, nz, ox, oy, oz, extrapolate);
+    if (rc != BFM_OK) return rc;
+    if (dtype < BFM_LABEL_U8 || dtype > BFM_LABEL_I64) return BFM_E_ARG;
     if (variant < BFM_LABEL_PULL_AUTO || variant > BFM_LABEL_PULL_PASSES) return BFM_E_ARG;
     const int B = Bi > Bg ? Bi : Bg;
     const int64_t nout = (int64_t)ox * oy * oz;
-    const Bounds bd{{bound[0], bound[1], bound[2]}};
-    const Orders od{{order[0], order[1], order[2]}};
-    const int iso = (order[0] == order[1] && order[1] == order[2]) ? order[0] : -1;
-    const int64_t n = B * nout;
+    const GridOpts op = grid_opts(bound, order, extrapolate);
     hipStream_t s = bfm_s(stream);
     switch (dtype) {
-        case BFM_LABEL_U8: launch_dtype<uint8_t>(iso, variant, n, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrapolate, B, out); break;
-        case BFM_LABEL_I16: launch_dtype<int16_t>(iso, variant, n, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrapolate, B, out); break;
-        case BFM_LABEL_I32: launch_dtype<int32_t>(iso, variant, n, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrapolate, B, out); break;
-        default: launch_dtype<int64_t>(iso, variant, n, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, bd, od, extrapolate, B, out); break;
+        case BFM_LABEL_U8: launch_dtype<uint8_t>(variant, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, op, B, out); break;
+        case BFM_LABEL_I16: launch_dtype<int16_t>(variant, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, op, B, out); break;
+        case BFM_LABEL_I32: launch_dtype<int32_t>(variant, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, op, B, out); break;
+        default: launch_dtype<int64_t>(variant, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, op, B, out); break;
     }
     return bfm_launch_status();
 }

@@ -39,10 +39,10 @@ __global__ void __launch_bounds__(256) axis_table_kernel(const float* __restrict
         const float g = coord[i];
         const float mask = inbounds(g, 0.f, 0.f, n, 1, 1, extrap);          // this axis alone: 0 is inside a length of 1
         int idx[4];
-        float w[4], unused[4];
-        axis_nodes<4, false>(g, order, n, bound, idx, w, unused);
+        float w[4];
+        axis_nodes<4>(g, order, n, bound, idx, w);
         if (ties_even && order == 0) {               // iso0.py:12: g.round(), a tie to the even node
-            const int node = (int)fminf(fmaxf(rintf(g), -1073741824.f), 1073741824.f);
+            const int node = node_int(rintf(g));
             idx[0] = bound_index(node, n, bound);
             w[0] = (float)bound_sign(node, n, bound);
         }

@@ -1,7 +1,8 @@
-// Per-axis spline nodes of the interpol grid kernels (utils/interpol/nd.py:44-75, splines.py:30-43 and :90-103), shared by
-// the voxel-wise kernels of spline_grid.hip and grid_hess.hip and the separable axis tables of restrict.hip: the weight and
-// its first and second derivative (splines.py:149-157), the nodes of one axis (index, weight * sign, derivative * sign) and
-// the inbounds mask (extrapolate 0 no / 1 yes / 2 hist).
+// Per-axis spline nodes of the interpol grid kernels (utils/interpol/nd.py:44-75 and :368-391, splines.py:30-43, :90-103
+// and :149-157), shared by the voxel-wise kernels of spline_grid.hip, grid_hess.hip and label_pull.hip (through
+// grid_kernels.h) and the separable axis tables of restrict.hip: the weight and its first and second derivative, node k
+// of one axis (index, weight * sign, derivatives * sign) in one definition, and the inbounds mask (extrapolate 0 no /
+// 1 yes / 2 hist).
 #pragma once
 #include "bfm_common.h"
 #include "interp_bounds.h"
@@ -34,25 +35,6 @@ __device__ __forceinline__ float spline_dweight(int order, float x) {
     return g * s;
 }
 
-// nodes of one axis (nd.py:44-75): off[k] = bound_index * stride, w[k] = weight * sign, dw[k] = fastgrad * sign
-template <int T, bool GRAD>
-__device__ __forceinline__ void axis_nodes(float g, int order, int n, int b, int (&idx)[T], float (&w)[T], float (&dw)[T]) {
-    const float g0f = floorf(g - 0.5f * (float)(order - 1));
-    const float dist0 = g - g0f;
-    // coordinates beyond +-2^30 voxels have no meaning; the clamp keeps grid0 + k inside what bound_index maps to [0, n-1]
-    const int g0 = (int)fminf(fmaxf(g0f, -1073741824.f), 1073741824.f);
-#pragma unroll
-    for (int k = 0; k < T; ++k) {
-        const bool used = k <= order;
-        const int node = used ? g0 + k : g0;
-        const float s = used ? (float)bound_sign(node, n, b) : 0.f;
-        idx[k] = bound_index(node, n, b);
-        const float d = dist0 - (float)k;
-        w[k] = spline_weight(order, d) * s;
-        dw[k] = GRAD ? spline_dweight(order, d) * s : 0.f;
-    }
-}
-
 // splines.py:149-157: fasthess, even in x (no sign factor); 0 for orders 0 and 1
 __device__ __forceinline__ float spline_d2weight(int order, float x) {
     if (order < 2) return 0.f;
@@ -61,26 +43,39 @@ __device__ __forceinline__ float spline_d2weight(int order, float x) {
     return x < 1.f ? 3.f * x - 2.f : 2.f - x;
 }
 
-// axis_nodes with the second derivative as well (nd.py:368-391): d2w[k] = fasthess * sign.  ISO1 (order 1 only, T = 2):
-// the slope of iso1.py (-1 at the lower node, +1 at the upper), not the sign(x) of the generic path's fastgrad.  A sibling
-// of axis_nodes, whose instantiations stay as they are.
-template <int T, bool ISO1>
-__device__ __forceinline__ void axis_nodes2(float g, int order, int n, int b, int (&idx)[T], float (&w)[T], float (&dw)[T],
-                                            float (&d2w)[T]) {
+// coordinates beyond +-2^30 voxels have no meaning; the clamp keeps grid0 + k inside what bound_index maps to [0, n-1]
+__device__ __forceinline__ int node_int(float f) { return (int)fminf(fmaxf(f, -1073741824.f), 1073741824.f); }
+
+// Node k of one axis (nd.py:44-75 and :368-391), the one definition every kernel of the family takes its nodes from: the
+// label pull's tie rule and every bit-for-bit comparison between kernels rest on that.  idx = bound_index(grid0 + k),
+// w = weight * sign, and with D >= 1 *dw = fastgrad * sign, with D == 2 *d2w = fasthess * sign; a derivative that D does
+// not ask for is not written and its pointer may be left out.  ISO1 (order 1 only): the slope of iso1.py (-1 at the
+// lower node, +1 at the upper), not the sign(x) of the generic path's fastgrad.  k > order: a padded tap, weight 0 and
+// the index of tap 0.  k may be a run-time value: the kernels that walk the footprint slab by slab in a rolled loop call
+// this directly, since an array of nodes read at a run-time index would go to scratch.
+template <int D = 0, bool ISO1 = false>
+__device__ __forceinline__ void axis_node(float g, int order, int n, int b, int k, int& idx, float& w, float* dw = nullptr,
+                                          float* d2w = nullptr) {
     const float g0f = floorf(g - 0.5f * (float)(order - 1));
     const float dist0 = g - g0f;
-    const int g0 = (int)fminf(fmaxf(g0f, -1073741824.f), 1073741824.f);
+    const int g0 = node_int(g0f);
+    const bool used = k <= order;
+    const int node = used ? g0 + k : g0;
+    const float s = used ? (float)bound_sign(node, n, b) : 0.f;
+    idx = bound_index(node, n, b);
+    const float d = dist0 - (float)k;
+    w = spline_weight(order, d) * s;
+    if (D >= 1) *dw = (ISO1 ? (k == 0 ? -1.f : 1.f) : spline_dweight(order, d)) * s;
+    if (D >= 2) *d2w = spline_d2weight(order, d) * s;
+}
+
+// the T nodes of one axis in registers
+template <int T, int D = 0, bool ISO1 = false>
+__device__ __forceinline__ void axis_nodes(float g, int order, int n, int b, int (&idx)[T], float (&w)[T],
+                                           float* dw = nullptr, float* d2w = nullptr) {
 #pragma unroll
-    for (int k = 0; k < T; ++k) {
-        const bool used = k <= order;
-        const int node = used ? g0 + k : g0;
-        const float s = used ? (float)bound_sign(node, n, b) : 0.f;
-        idx[k] = bound_index(node, n, b);
-        const float d = dist0 - (float)k;
-        w[k] = spline_weight(order, d) * s;
-        dw[k] = (ISO1 ? (k == 0 ? -1.f : 1.f) : spline_dweight(order, d)) * s;
-        d2w[k] = spline_d2weight(order, d) * s;
-    }
+    for (int k = 0; k < T; ++k)
+        axis_node<D, ISO1>(g, order, n, b, k, idx[k], w[k], D >= 1 ? dw + k : nullptr, D >= 2 ? d2w + k : nullptr);
 }
 
 __device__ __forceinline__ float inbounds(float gx, float gy, float gz, int nx, int ny, int nz, int extrap) {

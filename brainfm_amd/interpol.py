@@ -71,83 +71,96 @@ def _bound_list(bound):
     return out[:3]
 
 
-def _prep(input, grid, dim=3):
-    """api.py:81-118 _preproc: broadcast batch dims, default channel of 1.  Returns (x (B,C,*in), g (B,*out,3), info)."""
+def _prep(input, grid, dim=3, tail=(), cast=True):
+    """api.py:81-118 _preproc: broadcast batch dims, default channel of 1.  Returns (x (B,C,*in,*tail), g (B,*out,3), info).
+    tail: trailing dimensions of `input` behind the spatial ones (grid_pushgrad: (3,)); cast=False keeps the dtype of
+    `input` (a label map) where the default computes in float32."""
     grid_spatial = tuple(grid.shape[-dim - 1:-1])
     grid_batch = tuple(grid.shape[:-dim - 1])
-    in_spatial = tuple(input.shape[-dim:])
-    channel = 0 if input.dim() == dim else input.shape[-dim - 1]
-    in_batch = tuple(input.shape[:-dim - 1]) if input.dim() > dim else ()
+    lead = tuple(input.shape[:input.dim() - len(tail)])
+    in_spatial = lead[-dim:]
+    channel = 0 if len(lead) == dim else lead[-dim - 1]
+    in_batch = lead[:-dim - 1] if len(lead) > dim else ()
     batch = torch.broadcast_shapes(grid_batch, in_batch)
     g = grid.to(torch.float32).expand(*batch, *grid_spatial, dim).reshape(-1, *grid_spatial, dim).contiguous()
-    x = input.to(torch.float32).expand(*batch, channel or 1, *in_spatial).reshape(-1, channel or 1, *in_spatial).contiguous()
+    x = input.to(torch.float32) if cast else input
+    x = x.expand(*batch, channel or 1, *in_spatial, *tail).reshape(-1, channel or 1, *in_spatial, *tail).contiguous()
     return x, g, (batch, channel, in_spatial, grid_spatial)
 
 
+def _unprep(out, batch, channel, *trailing):
+    """(B,C,*trailing) back to the caller's batch dims and channel: no channel dim for a channel-less, unbatched call"""
+    out_channel = [channel] if channel else ([1] if batch else [])
+    return out.reshape(*batch, *out_channel, *trailing)
+
+
+def _extrap(extrapolate):
+    """False / 'no' -> 0, True / 'yes' -> 1, 'hist' -> 2; an integer as it is"""
+    return int({False: 0, True: 1, "no": 0, "yes": 1, "hist": 2}.get(extrapolate, extrapolate))
+
+
 def _opts(interpolation, bound, extrapolate):
-    ext = {False: 0, True: 1, "no": 0, "yes": 1, "hist": 2}.get(extrapolate, extrapolate)
-    return (C.c_int * 3)(*_bound_list(bound)), _order_list(interpolation, high_names=False), int(ext)
+    return (C.c_int * 3)(*_bound_list(bound)), _order_list(interpolation, high_names=False), _extrap(extrapolate)
+
+
+_LABEL_DTYPE = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}      # BFM_LABEL_* of include/brainfm_hip.h
+LABEL_PULL_AUTO, LABEL_PULL_LDS, LABEL_PULL_REGS, LABEL_PULL_PASSES = 0, 1, 2, 3         # BFM_LABEL_PULL_*
+
+
+def _export(name, x, g, dims, b, o, ext, extra, out):
+    """One call of an export of the grid family, which all take (inp[, label dtype], Bi, C, *in, grid, Bg, *dims, bound[,
+    order], extrapolate, *extra, out, stream): x (Bi,C,*in[,3]) and g (Bg,*,3) contiguous, `dims` the other spatial shape
+    of the call (the grid's for a pull, the volume's for a push), o None for a _linear export, which takes no order.
+    Returns `out`."""
+    args = [L.ptr(x)] + ([] if x.dtype.is_floating_point else [_LABEL_DTYPE[x.dtype]])
+    args += [x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.shape[4], L.ptr(g), g.shape[0], dims[0], dims[1], dims[2], b]
+    args += [] if o is None else [(C.c_int * 3)(*o)]
+    L.check(getattr(L.load(), "bfm_" + name)(*args, ext, *extra, L.ptr(out), L.stream_ptr()), name)
+    return out
+
+
+def _linear_or_spline(op, o):
+    """all-linear calls run iso1 on the kernels of synth_interp.hip, every other combination the generic path"""
+    return ("grid_%s3d_linear" % op, None) if o == _LINEAR else ("grid_%s3d_spline" % op, o)
+
+
+def _out(x, g, *trailing, fill=torch.empty):
+    return fill((max(x.shape[0], g.shape[0]), x.shape[1]) + trailing, dtype=x.dtype, device=x.device)
 
 
 def _pull_raw(x, g, b, o, ext):
-    B, Cc = x.shape[0], x.shape[1]
     gs = tuple(g.shape[1:4])
-    out = torch.empty((B, Cc) + gs, dtype=torch.float32, device=x.device)
-    if o == _LINEAR:
-        L.check(L.load().bfm_grid_pull3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
-                                                gs[1], gs[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_pull3d_linear")
-    else:
-        L.check(L.load().bfm_grid_pull3d_spline(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
-                                                gs[1], gs[2], b, (C.c_int * 3)(*o), ext, L.ptr(out), L.stream_ptr()),
-                "grid_pull3d_spline")
-    return out
+    name, o = _linear_or_spline("pull", o)
+    return _export(name, x, g, gs, b, o, ext, (), _out(x, g, *gs))
 
 
 def _push_raw(x, g, shape, b, o, ext):
-    B, Cc = x.shape[0], x.shape[1]
-    out = torch.zeros((B, Cc) + tuple(shape), dtype=torch.float32, device=x.device)
-    if o == _LINEAR:
-        L.check(L.load().bfm_grid_push3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, shape[0],
-                                                shape[1], shape[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_push3d_linear")
-    else:
-        L.check(L.load().bfm_grid_push3d_spline(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, shape[0],
-                                                shape[1], shape[2], b, (C.c_int * 3)(*o), ext, L.ptr(out), L.stream_ptr()),
-                "grid_push3d_spline")
-    return out
+    name, o = _linear_or_spline("push", o)
+    return _export(name, x, g, shape, b, o, ext, (), _out(x, g, *shape, fill=torch.zeros))
 
 
 def _grad_raw(x, g, b, o, ext):
-    B, Cc = x.shape[0], x.shape[1]
     gs = tuple(g.shape[1:4])
-    out = torch.empty((B, Cc) + gs + (3,), dtype=torch.float32, device=x.device)
-    if o == _LINEAR:
-        L.check(L.load().bfm_grid_grad3d_linear(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
-                                                gs[1], gs[2], b, ext, L.ptr(out), L.stream_ptr()), "grid_grad3d_linear")
-    else:
-        L.check(L.load().bfm_grid_grad3d_spline(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0],
-                                                gs[1], gs[2], b, (C.c_int * 3)(*o), ext, L.ptr(out), L.stream_ptr()),
-                "grid_grad3d_spline")
-    return out
+    name, o = _linear_or_spline("grad", o)
+    return _export(name, x, g, gs, b, o, ext, (), _out(x, g, *gs, 3))
 
 
 def _hess_raw(x, g, b, o, ext, cot=None):
     """cot None: the Hessian (B,C,*out,3,3); cot (B,C,*out,3): its contraction with cot over channel and row, (B,*out,3)"""
-    B, Cc = x.shape[0], x.shape[1]
     gs = tuple(g.shape[1:4])
-    out = torch.empty(((B, Cc) + gs + (3, 3)) if cot is None else ((B,) + gs + (3,)), dtype=torch.float32, device=x.device)
-    L.check(L.load().bfm_grid_hess3d(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, gs[0], gs[1], gs[2],
-                                     b, (C.c_int * 3)(*o), ext, L.ptr(cot), L.ptr(out), L.stream_ptr()), "grid_hess3d")
-    return out
+    out = _out(x, g, *gs, 3, 3) if cot is None else torch.empty((cot.shape[0],) + gs + (3,), dtype=x.dtype, device=x.device)
+    return _export("grid_hess3d", x, g, gs, b, o, ext, (L.ptr(cot),), out)
 
 
 def _pushgrad_raw(x, g, shape, b, o, ext):
     """x (B,C,*in,3) -> (B,C,*shape)"""
-    B, Cc = x.shape[0], x.shape[1]
-    out = torch.zeros((B, Cc) + tuple(shape), dtype=torch.float32, device=x.device)
-    L.check(L.load().bfm_grid_pushgrad3d(L.ptr(x), B, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), B, shape[0],
-                                         shape[1], shape[2], b, (C.c_int * 3)(*o), ext, L.ptr(out), L.stream_ptr()),
-            "grid_pushgrad3d")
-    return out
+    return _export("grid_pushgrad3d", x, g, shape, b, o, ext, (), _out(x, g, *shape, fill=torch.zeros))
+
+
+def _label_pull_raw(x, g, b, o, ext, variant=LABEL_PULL_AUTO):
+    """x (Bi,C,*in) uint8 / int16 / int32 / int64, g (Bg,*out,3) fp32, both contiguous -> (B,C,*out) of x's dtype"""
+    gs = tuple(g.shape[1:4])
+    return _export("label_pull3d", x, g, gs, b, o, ext, (variant,), _out(x, g, *gs))
 
 
 class _GridGrad(torch.autograd.Function):
@@ -243,8 +256,7 @@ def grid_push(input, grid, shape=None, interpolation="linear", bound="zero", ext
     out = _GridPush.apply(x, g, shape, b, o, ext)
     if prefilter:
         out = spline_coeff_nd(out, interpolation=list(o), bound=bound, dim=3, inplace=True)
-    out_channel = [channel] if channel else ([1] if batch else [])
-    return out.reshape(*batch, *out_channel, *shape)
+    return _unprep(out, batch, channel, *shape)
 
 
 def grid_count(grid, shape=None, interpolation="linear", bound="zero", extrapolate=False):
@@ -271,8 +283,7 @@ def grid_grad(input, grid, interpolation="linear", bound="zero", extrapolate=Fal
         input = spline_coeff_nd(input, interpolation=list(o), bound=bound, dim=3)
     x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid)
     out = _GridGrad.apply(x, g, b, o, ext)
-    out_channel = [channel] if channel else ([1] if batch else [])
-    return out.reshape(*batch, *out_channel, *grid_spatial, 3)
+    return _unprep(out, batch, channel, *grid_spatial, 3)
 
 
 def grid_hess(input, grid, interpolation="linear", bound="zero", extrapolate=False):
@@ -286,8 +297,7 @@ def grid_hess(input, grid, interpolation="linear", bound="zero", extrapolate=Fal
     _require_cuda(input, "grid_hess")
     x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input.detach(), grid.detach())
     out = _hess_raw(x, g, b, o, ext)
-    out_channel = [channel] if channel else ([1] if batch else [])
-    return out.reshape(*batch, *out_channel, *grid_spatial, 3, 3)
+    return _unprep(out, batch, channel, *grid_spatial, 3, 3)
 
 
 def grid_pushgrad(input, grid, shape=None, interpolation="linear", bound="zero", extrapolate=False):
@@ -303,33 +313,9 @@ def grid_pushgrad(input, grid, shape=None, interpolation="linear", bound="zero",
         raise ValueError("Input and grid should have the same spatial shape")
     shape = tuple(int(v) for v in (shape if shape is not None else input.shape[-4:-1]))
     _require_cuda(input, "grid_pushgrad")
-    # the batch and channel conventions of _prep, with the three components behind the spatial dimensions
-    in_spatial = tuple(input.shape[-4:-1])
-    channel = 0 if input.dim() == 4 else input.shape[-5]
-    in_batch = tuple(input.shape[:-5]) if input.dim() > 4 else ()
-    batch = torch.broadcast_shapes(tuple(grid.shape[:-4]), in_batch)
-    g = grid.detach().to(torch.float32).expand(*batch, *in_spatial, 3).reshape(-1, *in_spatial, 3).contiguous()
-    x = input.detach().to(torch.float32).expand(*batch, channel or 1, *in_spatial, 3)
-    x = x.reshape(-1, channel or 1, *in_spatial, 3).contiguous()
+    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input.detach(), grid.detach(), tail=(3,))
     out = _pushgrad_raw(x, g, shape, b, o, ext)
-    out_channel = [channel] if channel else ([1] if batch else [])
-    return out.reshape(*batch, *out_channel, *shape)
-
-
-_LABEL_DTYPE = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}      # BFM_LABEL_* of include/brainfm_hip.h
-LABEL_PULL_AUTO, LABEL_PULL_LDS, LABEL_PULL_REGS, LABEL_PULL_PASSES = 0, 1, 2, 3         # BFM_LABEL_PULL_*
-
-
-def _label_pull_raw(x, g, b, o, ext, variant=LABEL_PULL_AUTO):
-    """x (Bi,C,*in) uint8 / int16 / int32 / int64, g (Bg,*out,3) fp32, both contiguous -> (B,C,*out) of x's dtype"""
-    Bi, Cc = x.shape[0], x.shape[1]
-    Bg = g.shape[0]
-    gs = tuple(g.shape[1:4])
-    out = torch.empty((max(Bi, Bg), Cc) + gs, dtype=x.dtype, device=x.device)
-    L.check(L.load().bfm_label_pull3d(L.ptr(x), _LABEL_DTYPE[x.dtype], Bi, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g),
-                                      Bg, gs[0], gs[1], gs[2], b, (C.c_int * 3)(*o), ext, variant, L.ptr(out),
-                                      L.stream_ptr()), "label_pull3d")
-    return out
+    return _unprep(out, batch, channel, *shape)
 
 
 def _label_pull(input, grid, b, o, ext, prefilter):
@@ -347,17 +333,9 @@ def _label_pull(input, grid, b, o, ext, prefilter):
                                   "reference overwrites its own input with the first label's coefficients there and has "
                                   "no defined result")
     _require_cuda(input, "grid_pull")
-    dim = 3
-    grid_spatial = tuple(grid.shape[-dim - 1:-1])
-    in_spatial = tuple(input.shape[-dim:])
-    channel = 0 if input.dim() == dim else input.shape[-dim - 1]
-    in_batch = tuple(input.shape[:-dim - 1]) if input.dim() > dim else ()
-    batch = torch.broadcast_shapes(tuple(grid.shape[:-dim - 1]), in_batch)
-    g = grid.detach().to(torch.float32).expand(*batch, *grid_spatial, dim).reshape(-1, *grid_spatial, dim).contiguous()
-    x = input.expand(*batch, channel or 1, *in_spatial).reshape(-1, channel or 1, *in_spatial).contiguous()
+    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid.detach(), cast=False)
     out = _label_pull_raw(x, g, b, o, ext)
-    out_channel = [channel] if channel else ([1] if batch else [])
-    return out.reshape(*batch, *out_channel, *grid_spatial)
+    return _unprep(out, batch, channel, *grid_spatial)
 
 
 def grid_pull(input, grid, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):
@@ -379,8 +357,7 @@ def grid_pull(input, grid, interpolation="linear", bound="zero", extrapolate=Fal
         input = spline_coeff_nd(input, interpolation=list(o), bound=bound, dim=3)
     x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid)
     out = _GridPull.apply(x, g, b, o, ext)                       # differentiable w.r.t. input and grid (first order)
-    out_channel = [channel] if channel else ([1] if batch else [])
-    return out.reshape(*batch, *out_channel, *grid_spatial)
+    return _unprep(out, batch, channel, *grid_spatial)
 
 
 # ----------------------------------------------------------------------------- resize (bspline_zooming)
@@ -641,6 +618,22 @@ def _make_list(x, n=None):
     return x
 
 
+def _anchor_coords(anchor, f, n_src, n_dst):
+    """resize.py:86-104 / restrict.py:81-104: the coordinates of the n_dst samples of a resampled axis in the lattice of
+    its n_src samples, for the anchors 'c' (centers of the corner voxels aligned), 'e' (edges aligned), 'f' / 'l' (first /
+    last voxel aligned, spacing 1 / f).  fp32 on the host: the same values as torch on the CPU."""
+    if anchor == "c":
+        return torch.linspace(0, n_src - 1, n_dst, dtype=torch.float32)
+    if anchor == "e":
+        scale = n_src / n_dst
+        return torch.arange(0., n_dst, dtype=torch.float32) * scale + 0.5 * (scale - 1)
+    if anchor == "f":
+        return torch.arange(0., n_dst, dtype=torch.float32) / f
+    if anchor == "l":
+        return torch.arange(0., n_dst, dtype=torch.float32) / f + ((n_src - 1) - (n_dst - 1) / f)
+    raise ValueError("Unknown anchor {}".format(anchor))
+
+
 def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilter=True, **kwargs):
     """utils/interpol/resize.py:13-119.  image: (..., X, Y, Z).  Cubic (interpolation=3) with extrapolation under the
     'nearest' / 'dct2' bounds runs as prefilter + three separable 4-tap passes; every other case (orders 0 to 3, any
@@ -666,21 +659,7 @@ def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilte
         shape = [int(i * f) for i, f in zip(inshape, factor)]
     if not factor:
         factor = [o / i for o, i in zip(shape, inshape)]
-    lin = []
-    for anch, f, inshp, outshp in zip(anchor, factor, inshape, shape):         # fp32 on the host: same values as torch CPU
-        if anch == "c":
-            lin.append(torch.linspace(0, inshp - 1, outshp, dtype=torch.float32))
-        elif anch == "e":
-            scale = inshp / outshp
-            shift = 0.5 * (scale - 1)
-            lin.append(torch.arange(0., outshp, dtype=torch.float32) * scale + shift)
-        elif anch == "f":
-            lin.append(torch.arange(0., outshp, dtype=torch.float32) / f)
-        elif anch == "l":
-            shift = (inshp - 1) - (outshp - 1) / f
-            lin.append(torch.arange(0., outshp, dtype=torch.float32) / f + shift)
-        else:
-            raise ValueError("Unknown anchor {}".format(anch))
+    lin = [_anchor_coords(anch, f, inshp, outshp) for anch, f, inshp, outshp in zip(anchor, factor, inshape, shape)]
     bound = kwargs.get("bound", "nearest")
     prefilter = kwargs.get("prefilter", prefilter)
     if orders == _LINEAR:
@@ -809,24 +788,9 @@ def _restrict_geometry(image_shape, factor=None, shape=None, anchor="c"):
         factor = [i / o for o, i in zip(shape, inshape)]
     lin = []
     fullscale = 1
-    for anch, f, inshp, outshp in zip(anchor, factor, inshape, shape):         # fp32 on the host: same values as torch CPU
-        if anch == "c":
-            lin.append(torch.linspace(0, outshp - 1, inshp, dtype=torch.float32))
-            fullscale *= (inshp - 1) / (outshp - 1)
-        elif anch == "e":
-            scale = outshp / inshp
-            shift = 0.5 * (scale - 1)
-            fullscale *= scale
-            lin.append(torch.arange(0., inshp, dtype=torch.float32) * scale + shift)
-        elif anch == "f":
-            fullscale *= 1 / f
-            lin.append(torch.arange(0., inshp, dtype=torch.float32) / f)
-        elif anch == "l":
-            shift = (outshp - 1) - (inshp - 1) / f
-            fullscale *= 1 / f
-            lin.append(torch.arange(0., inshp, dtype=torch.float32) / f + shift)
-        else:
-            raise ValueError("Unknown anchor {}".format(anch))
+    for anch, f, inshp, outshp in zip(anchor, factor, inshape, shape):
+        lin.append(_anchor_coords(anch, f, outshp, inshp))                     # resize's lattice, input and output swapped
+        fullscale *= (inshp - 1) / (outshp - 1) if anch == "c" else (outshp / inshp if anch == "e" else 1 / f)
     return tuple(int(v) for v in shape), lin, fullscale
 
 
@@ -843,8 +807,7 @@ def restrict(image, factor=None, shape=None, anchor="c", interpolation=1, reduce
     shape, lin, fullscale = _restrict_geometry(tuple(image.shape), factor, shape, anchor)
     bound = kwargs.get("bound", "nearest")
     b = _bound_list(bound)
-    extrapolate = kwargs.get("extrapolate", True)
-    ext = int({False: 0, True: 1, "no": 0, "yes": 1, "hist": 2}.get(extrapolate, extrapolate))
+    ext = _extrap(kwargs.get("extrapolate", True))
     if any(not 0 <= v <= 6 for v in b) or not 0 <= ext <= 2:
         raise ValueError("Unknown bound or extrapolate value")
     prefilter = _needs_prefilter(kwargs.get("prefilter", False), orders, b, shape)
