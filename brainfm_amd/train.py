@@ -7,9 +7,13 @@ Mirrors the reference's iteration -- Trainer/engine.py:96-147:
     loss_dict = criterion(outputs, target, samples)   -> bfm_loss_l1_multi / bfm_loss_grad_l1_multi / bfm_loss_seg / ...
     losses = sum(loss_dict[k] * weight_dict[k])
     scaler.scale(losses).backward()                   -> bfm_head_bwd, bfm_normalize_bwd, backward.backbone_backward
-    scaler.unscale_(optimizer); clip_gradients(...)   -> bfm_grad_sumsq (+ non-finite flag), per-parameter coefficient
-    scaler.step(optimizer); scaler.update()           -> bfm_adamw_step, LossScaler.update   (optimizer='adam' | 'sgd' | 'lars':
-                                                         bfm_adam_step_multi / bfm_sgd_step_multi / bfm_lars_step_multi)
+    scaler.unscale_(optimizer); clip_gradients(...)   -> bfm_grad_sumsq_multi (+ non-finite flag; LARS: bfm_lars_sums_multi),
+                                                         per-parameter coefficient                      (TrainStep._measure)
+    scaler.step(optimizer); scaler.update()           -> bfm_adamw_step_multi | bfm_adam_step_multi | bfm_sgd_step_multi |
+                                                         bfm_lars_step_multi, LossScaler.update         (TrainStep._update)
+
+The four optimisers share one path: one descriptor per parameter (bfm_optim_tensor_t), one chunk map, one measuring launch and
+one update launch over all tensors, whatever the kind.
 
 with the criterion of Trainer/models/criterion.py (SetMultiCriterion: sum over the samples / all_samples) restricted to
 the supervised dense heads: T1 T2 FLAIR CT (+_grad, optional <key>_DM weights), SR(+_grad), distance, registration
@@ -313,16 +317,11 @@ class GradStore:
         self.works = []
 
 
-# bfm_adam_tensor_t (include/brainfm_hip.h): p, g, m, v, n, grad_scale, bias1, bias2_sqrt, first_chunk, reserved
-_ADAM_DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("grad_scale", "<f4"),
-                       ("bias1", "<f4"), ("bias2_sqrt", "<f4"), ("first_chunk", "<i4"), ("reserved", "<i8")])
-assert _ADAM_DESC.itemsize == 64
-# bfm_optim_tensor_t (Adam, SGD, LARS): s0 = exp_avg | momentum_buffer | mu, s1 = exp_avg_sq (Adam alone, else 0); q and wd
-# are LARS' per-tensor trust ratio and decay.  Every field bfm_grad_sumsq_multi reads (g, n, first_chunk) sits where
-# bfm_adam_tensor_t has it, so the clip norms of Adam and SGD come from that launch on these descriptors.
+# bfm_optim_tensor_t (include/brainfm_hip.h), the one descriptor of every multi-tensor launch: s0 = exp_avg | momentum_buffer
+# | mu, s1 = exp_avg_sq (Adam and AdamW, else 0); q and wd are LARS' per-tensor trust ratio and decay.
 _OPT_DESC = np.dtype([("p", "<u8"), ("g", "<u8"), ("s0", "<u8"), ("s1", "<u8"), ("n", "<i8"), ("grad_scale", "<f4"),
                       ("bias1", "<f4"), ("bias2_sqrt", "<f4"), ("first_chunk", "<i4"), ("q", "<f4"), ("wd", "<f4")])
-assert _OPT_DESC.itemsize == 64 and all(_OPT_DESC.fields[k][1] == _ADAM_DESC.fields[k][1] for k in ("g", "n", "first_chunk"))
+assert _OPT_DESC.itemsize == 64
 # how a checkpoint's optimiser state names its buffers, per kind (torch.optim.Adam / AdamW / SGD, utils.LARS)
 _STATE_KEYS = {"adam": ("exp_avg", "exp_avg_sq"), "adamw": ("exp_avg", "exp_avg_sq"), "sgd": ("momentum_buffer",),
                "lars": ("mu",)}
@@ -476,24 +475,20 @@ class TrainStep:
         return OrderedDict((k, v.detach().reshape(self._ref_shape(k, v)).cpu().clone()) for k, v in self.parameters().items())
 
     def optimizer_state_dict(self, lr=None, weight_decay=None):
-        """torch.optim.AdamW.state_dict() layout for the single parameter group of scripts/train.py:46-53 (parameters in
-        model.named_parameters() order == self.parameters() order); with another optimiser, that one's layout."""
-        names = list(self.parameters().keys())
-        if self.opt_kind != "adamw":
-            return self._other_optimizer_state_dict(names, lr, weight_decay)
-        if self.opt_spec is not None:
-            lr, weight_decay = self._hyper(lr, weight_decay)
+        """state_dict() layout of this step's optimiser (torch.optim.AdamW / Adam / SGD, utils.LARS) for the single parameter
+        group of scripts/train.py:46-53 (parameters in model.named_parameters() order == self.parameters() order)."""
+        lr, wd = self._hyper(lr, weight_decay)
+        params = self.parameters()
         state = {}
-        for i, k in enumerate(names):
+        for i, (k, p) in enumerate(params.items()):
             if k in self.state:
-                m, v = self.state[k]
-                shp = self._ref_shape(k, self.parameters()[k])
-                state[i] = {"step": torch.tensor(float(self.steps.get(k, self.t))), "exp_avg": m.reshape(shp).cpu().clone(),
-                            "exp_avg_sq": v.reshape(shp).cpu().clone()}
-        group = {"lr": self.lr if lr is None else lr, "betas": tuple(self.betas), "eps": self.eps,
-                 "weight_decay": self.wd if weight_decay is None else weight_decay, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "params": list(range(len(names)))}
+                shp = self._ref_shape(k, p)
+                st = {key: buf.reshape(shp).cpu().clone() for key, buf in zip(_STATE_KEYS[self.opt_kind], self.state[k])}
+                if self.opt_kind in ("adam", "adamw"):
+                    st = dict(step=torch.tensor(float(self.steps.get(k, self.t))), **st)
+                state[i] = st
+        group = self._param_group(lr, wd)
+        group["params"] = list(range(len(params)))
         return {"state": state, "param_groups": [group]}
 
     def _hyper(self, lr=None, weight_decay=None):
@@ -503,31 +498,23 @@ class TrainStep:
         wd = group.get("weight_decay", self.wd) if weight_decay is None else weight_decay
         return float(lr), float(wd)
 
-    def _other_optimizer_state_dict(self, names, lr=None, weight_decay=None):
-        """state_dict() layout of torch.optim.Adam / torch.optim.SGD as the installed torch writes it (the param-group keys
-        are read off a throw-away instance), or of utils.LARS (utils/misc.py:1283-1289), for the single parameter group."""
-        lr, wd = self._hyper(lr, weight_decay)
-        params = self.parameters()
-        state = {}
-        for i, k in enumerate(names):
-            if k in self.state:
-                shp = self._ref_shape(k, params[k])
-                st = {key: buf.reshape(shp).cpu().clone() for key, buf in zip(_STATE_KEYS[self.opt_kind], self.state[k])}
-                if self.opt_kind == "adam":
-                    st = dict(step=torch.tensor(float(self.steps.get(k, self.t))), **st)
-                state[i] = st
+    def _param_group(self, lr, wd):
+        """The optimiser's param group without 'params'.  AdamW's is spelled out (the checkpoints written so far hold these
+        keys, whatever the installed torch writes); Adam's and SGD's keys are read off a throw-away instance of the installed
+        torch; LARS' are those of utils/misc.py:1283-1289."""
+        if self.opt_kind == "adamw":
+            return {"lr": lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": wd, "amsgrad": False,
+                    "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None}
         if self.opt_kind == "lars":
-            group = {"lr": lr, "weight_decay": wd, "momentum": self.momentum, "eta": self.eta, "weight_decay_filter": None,
-                     "lars_adaptation_filter": None}
-        else:
-            dummy = [torch.nn.Parameter(torch.zeros(1))]
-            opt = torch.optim.Adam(dummy) if self.opt_kind == "adam" else torch.optim.SGD(dummy, lr=0.0, momentum=self.momentum)
-            group = dict(opt.state_dict()["param_groups"][0])
-            group.update(lr=lr, weight_decay=wd)
-            if self.opt_kind == "adam":
-                group.update(betas=tuple(self.betas), eps=self.eps)
-        group["params"] = list(range(len(names)))
-        return {"state": state, "param_groups": [group]}
+            return {"lr": lr, "weight_decay": wd, "momentum": self.momentum, "eta": self.eta, "weight_decay_filter": None,
+                    "lars_adaptation_filter": None}
+        dummy = [torch.nn.Parameter(torch.zeros(1))]
+        opt = torch.optim.Adam(dummy) if self.opt_kind == "adam" else torch.optim.SGD(dummy, lr=0.0, momentum=self.momentum)
+        group = dict(opt.state_dict()["param_groups"][0])
+        group.update(lr=lr, weight_decay=wd)
+        if self.opt_kind == "adam":
+            group.update(betas=tuple(self.betas), eps=self.eps)
+        return group
 
     def save_checkpoint(self, path, epoch=0, **extra):
         """torch.save of {'model', 'optimizer', 'epoch', ...}: what utils.save_on_master writes in scripts/train.py, and
@@ -1015,13 +1002,11 @@ class TrainStep:
 
     def _measure(self, grads, grad_div=1.0):
         """First half of apply: the optimiser state of every parameter with a gradient, each gradient's norm (unscaled) and
-        whether any is non-finite.  Nothing is updated; the scaler is not touched."""
+        whether any is non-finite, from one launch over all tensors: bfm_grad_sumsq_multi, or for LARS bfm_lars_sums_multi,
+        whose sum p^2 and sum p g the update's trust ratio needs.  Nothing is updated; the scaler is not touched."""
         lib, st = self.lib, L.stream_ptr()
         params = self.parameters()
         names = [k for k in params if k in grads]
-        sums = torch.zeros(len(names), dtype=torch.float64, device=self.dev)
-        flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        multi = os.environ.get("BFM_ADAM_MULTI", "1") != "0"
         for k in names:
             grads[k] = grads[k].contiguous()
             if not params[k].is_contiguous():
@@ -1029,39 +1014,29 @@ class TrainStep:
             if k not in self.state:
                 self.state[k] = tuple(torch.zeros(params[k].numel(), dtype=torch.float32, device=self.dev)
                                       for _ in _STATE_KEYS[self.opt_kind])
-        if self.opt_kind != "adamw":
-            return self._measure_other(grads, params, names, sums, flag, grad_div)
-        if multi:
-            # every tensor's sum of squares in one launch (+ a fold): descriptors and chunk map in device memory
-            CH = 65536
-            desc = np.zeros(len(names), dtype=_ADAM_DESC)
-            first, cmap = 0, []
-            for i, k in enumerate(names):
-                n = params[k].numel()
-                m, v = self.state[k]
-                desc[i] = (params[k].data_ptr(), grads[k].data_ptr(), m.data_ptr(), v.data_ptr(), n, 0.0, 1.0, 1.0, first, 0)
-                nch = (n + CH - 1) // CH
-                cmap.extend([i] * nch)
-                first += nch
-            key = tuple(params[k].numel() for k in names)
-            if getattr(self, "_chunk_key", None) != key:
-                self._chunk_key = key
-                self._chunk_map = torch.tensor(cmap, dtype=torch.int32, device=self.dev)
-                self._chunk_ws = torch.empty(len(cmap), dtype=torch.float64, device=self.dev)
-            tdev = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(self.dev)
-            L.check(lib.bfm_grad_sumsq_multi(L.ptr(tdev), len(names), L.ptr(self._chunk_map), len(cmap), CH, L.ptr(sums),
-                                             L.ptr(flag), L.ptr(self._chunk_ws), self._chunk_ws.numel() * 8, st), "grad_sumsq_multi")
-        else:
-            for i, k in enumerate(names):
-                g = grads[k]
-                L.check(lib.bfm_grad_sumsq(L.ptr(g), g.numel(), C.c_void_p(sums.data_ptr() + 8 * i), L.ptr(flag),
-                                           L.ptr(self._ws), self._ws.numel(), st), "grad_sumsq " + k)
+        CH = 65536
+        firsts, nchunks = self._chunks(names, params, CH)
+        desc = np.zeros(len(names), dtype=_OPT_DESC)
+        for i, k in enumerate(names):
+            bufs = self.state[k]
+            desc[i] = (params[k].data_ptr(), grads[k].data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr() if len(bufs) > 1 else 0,
+                       params[k].numel(), 0.0, 1.0, 1.0, firsts[i], 1.0, 0.0)
+        tdev = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(self.dev)
+        lars = self.opt_kind == "lars"
+        width = 3 if lars else 1
+        sums = torch.zeros(len(names) * width, dtype=torch.float64, device=self.dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        ws = torch.empty(nchunks * 3, dtype=torch.float64, device=self.dev) if lars else self._chunk_ws
+        fn = lib.bfm_lars_sums_multi if lars else lib.bfm_grad_sumsq_multi
+        L.check(fn(L.ptr(tdev), len(names), L.ptr(self._chunk_map), nchunks, CH, L.ptr(sums), L.ptr(flag), L.ptr(ws),
+                   ws.numel() * 8, st), "lars_sums_multi" if lars else "grad_sumsq_multi")
+        sums = sums.cpu().reshape(-1, width)
         inv = 1.0 / (self.scaler.scale * grad_div)
         found_inf = bool(flag.item())
-        norms = [math.sqrt(v) * inv if math.isfinite(v) else float("inf") for v in sums.cpu().tolist()]
+        norms = [math.sqrt(v) * inv if math.isfinite(v) else float("inf") for v in sums[:, 0].tolist()]
         found_inf = found_inf or any(not math.isfinite(v) for v in norms)
-        return dict(grads=grads, params=params, names=names, norms=norms, inv=inv, found_inf=found_inf, multi=multi,
-                    desc=desc if multi else None, CH=CH if multi else 0)
+        return dict(grads=grads, params=params, names=names, norms=norms, inv=inv, found_inf=found_inf, desc=desc, CH=CH,
+                    sums3=sums if lars else None)
 
     def _chunks(self, names, params, CH):
         """The chunk map (device) of these tensors and each one's first chunk; kept while the sizes stay the same."""
@@ -1078,41 +1053,10 @@ class TrainStep:
             self._chunk_ws = torch.empty(len(cmap), dtype=torch.float64, device=self.dev)
         return firsts, len(cmap)
 
-    def _measure_other(self, grads, params, names, sums, flag, grad_div):
-        """_measure for Adam, SGD and LARS (multi-tensor kernels only): bfm_optim_tensor_t descriptors; the clip norms from
-        bfm_grad_sumsq_multi, or for LARS from bfm_lars_sums_multi, whose sum p^2 and sum p g the update's trust ratio needs."""
-        lib, st = self.lib, L.stream_ptr()
-        CH = 65536
-        firsts, nchunks = self._chunks(names, params, CH)
-        desc = np.zeros(len(names), dtype=_OPT_DESC)
-        for i, k in enumerate(names):
-            bufs = self.state[k]
-            desc[i] = (params[k].data_ptr(), grads[k].data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr() if len(bufs) > 1 else 0,
-                       params[k].numel(), 0.0, 1.0, 1.0, firsts[i], 1.0, 0.0)
-        tdev = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(self.dev)
-        sums3 = None
-        if self.opt_kind == "lars":
-            sums3 = torch.zeros(len(names) * 3, dtype=torch.float64, device=self.dev)
-            ws = torch.empty(nchunks * 3, dtype=torch.float64, device=self.dev)
-            L.check(lib.bfm_lars_sums_multi(L.ptr(tdev), len(names), L.ptr(self._chunk_map), nchunks, CH, L.ptr(sums3),
-                                            L.ptr(flag), L.ptr(ws), ws.numel() * 8, st), "lars_sums_multi")
-            sums3 = sums3.cpu().reshape(-1, 3)
-            sumsq = sums3[:, 0].tolist()
-        else:
-            L.check(lib.bfm_grad_sumsq_multi(L.ptr(tdev), len(names), L.ptr(self._chunk_map), nchunks, CH, L.ptr(sums),
-                                             L.ptr(flag), L.ptr(self._chunk_ws), self._chunk_ws.numel() * 8, st),
-                    "grad_sumsq_multi")
-            sumsq = sums.cpu().tolist()
-        inv = 1.0 / (self.scaler.scale * grad_div)
-        found_inf = bool(flag.item())
-        norms = [math.sqrt(v) * inv if math.isfinite(v) else float("inf") for v in sumsq]
-        found_inf = found_inf or any(not math.isfinite(v) for v in norms)
-        return dict(grads=grads, params=params, names=names, norms=norms, inv=inv, found_inf=found_inf, multi=True, desc=desc,
-                    CH=CH, sums3=sums3)
-
-    def _update_other(self, plan, lr, wd):
-        """_update for Adam, SGD and LARS: the per-tensor numbers into the descriptors, then one launch."""
-        lib, st = self.lib, L.stream_ptr()
+    def _update(self, plan, lr=None, weight_decay=None):
+        """Second half of apply: the per-tensor numbers (clip coefficient, bias corrections, LARS' decay and trust ratio) into
+        the descriptors _measure prepared, one launch of the optimiser over all tensors, then the packed weights."""
+        lr, wd = self._hyper(lr, weight_decay)
         params, names, norms, inv, desc, CH = (plan[k] for k in ("params", "names", "norms", "inv", "desc", "CH"))
         self.t += 1
         for i, (k, nrm) in enumerate(zip(names, norms)):
@@ -1123,8 +1067,8 @@ class TrainStep:
                 if c < 1:
                     coef *= c
             desc[i]["grad_scale"] = coef
-            if self.opt_kind == "adam":
-                # bias corrections in float32, as _update forms them for AdamW
+            if self.opt_kind in ("adam", "adamw"):
+                # bias corrections in float32 as bfm_adamw_step forms them (powf, sqrtf)
                 desc[i]["bias1"] = np.float32(1.0) - np.power(np.float32(self.betas[0]), np.float32(self.steps[k]), dtype=np.float32)
                 desc[i]["bias2_sqrt"] = np.sqrt(np.float32(1.0) - np.power(np.float32(self.betas[1]), np.float32(self.steps[k]),
                                                                           dtype=np.float32), dtype=np.float32)
@@ -1134,49 +1078,13 @@ class TrainStep:
                 desc[i]["wd"] = wd
                 desc[i]["q"] = lars_trust_ratio(sgg, spp, spg, float(np.float32(coef)), float(np.float32(wd)), self.eta)
         tdev = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(self.dev)
-        head = (L.ptr(tdev), len(names), L.ptr(self._chunk_map), int(self._chunk_map.numel()), CH)
-        if self.opt_kind == "adam":
-            rc = lib.bfm_adam_step_multi(*head, lr, self.betas[0], self.betas[1], self.eps, wd, st)
-        elif self.opt_kind == "sgd":
-            rc = lib.bfm_sgd_step_multi(*head, lr, self.momentum, wd, st)
-        else:
-            rc = lib.bfm_lars_step_multi(*head, lr, self.momentum, st)
-        L.check(rc, self.opt_kind + "_step_multi")
+        fn, tail = {"adamw": (self.lib.bfm_adamw_step_multi, (lr, self.betas[0], self.betas[1], self.eps, wd)),
+                    "adam": (self.lib.bfm_adam_step_multi, (lr, self.betas[0], self.betas[1], self.eps, wd)),
+                    "sgd": (self.lib.bfm_sgd_step_multi, (lr, self.momentum, wd)),
+                    "lars": (self.lib.bfm_lars_step_multi, (lr, self.momentum))}[self.opt_kind]
+        L.check(fn(L.ptr(tdev), len(names), L.ptr(self._chunk_map), int(self._chunk_map.numel()), CH, *tail, L.stream_ptr()),
+                self.opt_kind + "_step_multi")
         self._keep_desc = tdev
-        self._weights_changed()
-
-    def _update(self, plan, lr=None, weight_decay=None):
-        """Second half of apply: per-parameter clip and the optimiser on what _measure prepared, then the packed weights."""
-        lib, st = self.lib, L.stream_ptr()
-        lr, wd = self._hyper(lr, weight_decay)
-        if self.opt_kind != "adamw":
-            return self._update_other(plan, lr, wd)
-        grads, params, names, norms, inv = plan["grads"], plan["params"], plan["names"], plan["norms"], plan["inv"]
-        multi, desc, CH = plan["multi"], plan["desc"], plan["CH"]
-        self.t += 1
-        for i, (k, nrm) in enumerate(zip(names, norms)):
-            p, g = params[k], grads[k]
-            self.steps[k] = self.steps.get(k, 0) + 1        # torch.optim.AdamW keeps one step count per parameter
-            coef = inv
-            if self.clip > 0:
-                c = self.clip / (nrm + 1e-6)
-                if c < 1:
-                    coef *= c
-            m, v = self.state[k]
-            if multi:
-                # bias corrections in float32 as bfm_adamw_step forms them (powf, sqrtf)
-                b1 = np.float32(1.0) - np.power(np.float32(self.betas[0]), np.float32(self.steps[k]), dtype=np.float32)
-                b2 = np.sqrt(np.float32(1.0) - np.power(np.float32(self.betas[1]), np.float32(self.steps[k]), dtype=np.float32),
-                             dtype=np.float32)
-                desc[i]["grad_scale"], desc[i]["bias1"], desc[i]["bias2_sqrt"] = coef, b1, b2
-            else:
-                L.check(lib.bfm_adamw_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, self.betas[0], self.betas[1],
-                                           self.eps, wd, self.steps[k], coef, st), "adamw " + k)
-        if multi:
-            tdev = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(self.dev)
-            L.check(lib.bfm_adamw_step_multi(L.ptr(tdev), len(names), L.ptr(self._chunk_map), int(self._chunk_map.numel()), CH, lr,
-                                             self.betas[0], self.betas[1], self.eps, wd, st), "adamw_multi")
-            self._keep_desc = tdev
         self._weights_changed()
 
     @L.on_device(lambda self, *a, **k: self.dev)

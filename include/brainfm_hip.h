@@ -1085,41 +1085,20 @@ int bfm_head_bwd_rows(const float* dRaw_rows, int64_t row_stride, const float* F
                       bfm_stream_t stream);
 int bfm_normalize_bwd(const float* feat, const float* dFn, int C, int64_t nvox, float eps, float* dfeat,
                       bfm_stream_t stream);
-/* One descriptor per parameter tensor for the multi-tensor forms below (device memory, 64 bytes).  bias1 = 1 - beta1^t,
- * bias2_sqrt = sqrt(1 - beta2^t) of the tensor's own step count t (torch.optim.AdamW keeps one per parameter); first_chunk =
- * index of the tensor's first chunk in chunk_tensor. */
-typedef struct bfm_adam_tensor {
-    float* p; const float* g; float* m; float* v;
-    int64_t n;
-    float grad_scale, bias1, bias2_sqrt;
-    int32_t first_chunk;
-    int64_t reserved;
-} bfm_adam_tensor_t;
-/* utils/misc.py:1329-1338 clip_gradients' per-parameter norms and Trainer/models/__init__.py:362-366's AdamW over ALL
- * parameters in one launch each: a block owns one chunk (chunk_elems elements, a multiple of 4) of one tensor;
- * chunk_tensor[c] = tensor of chunk c (device).  sums_out[t] = sum of squares of tensors[t].g (fp64, fixed order);
- * workspace >= nchunks * 8 bytes. */
-int bfm_grad_sumsq_multi(const bfm_adam_tensor_t* tensors, int ntensors, const int32_t* chunk_tensor, int nchunks,
-                         int64_t chunk_elems, double* sums_out, int32_t* nonfinite, void* workspace, size_t workspace_bytes,
-                         bfm_stream_t stream);
-int bfm_adamw_step_multi(const bfm_adam_tensor_t* tensors, int ntensors, const int32_t* chunk_tensor, int nchunks,
-                         int64_t chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay,
-                         bfm_stream_t stream);
-/* torch.optim.AdamW step t (1-based) on one flat parameter; g is multiplied by grad_scale first (unscale * clip) */
-int bfm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                   float eps, float weight_decay, int step, float grad_scale, bfm_stream_t stream);
 /* out[0] = sum g^2 (fp64); nonfinite[0] |= 1 when g holds inf/nan (GradScaler.unscale_ / clip_grad_norm_) */
 int bfm_grad_sumsq(const float* g, int64_t n, double* out, int32_t* nonfinite, void* workspace, size_t workspace_bytes,
                    bfm_stream_t stream);
 
-/* ---- the other optimisers of build_optimizer (Trainer/models/__init__.py:360-372; optim.hip) ---------------------------
- * One descriptor per parameter tensor (device memory, 64 bytes), in the multi-tensor form of bfm_adamw_step_multi: a block
- * owns one chunk (chunk_elems elements, a multiple of 4) of one tensor, chunk_tensor[c] = tensor of chunk c, first_chunk =
- * index of the tensor's first chunk.  s0 = exp_avg (Adam) | momentum_buffer (SGD) | mu (LARS); s1 = exp_avg_sq (Adam; not
- * read by the others, may be NULL).  g is multiplied by grad_scale first (unscale * clip).  bias1 / bias2_sqrt as in
- * bfm_adam_tensor_t (Adam alone).  q and wd are LARS' per-tensor trust ratio and weight decay (1 and 0 for a parameter the
- * reference sees as 1-D, utils/misc.py:1299-1310).  16-byte accesses where p, g, s0 (and s1) are all 16-byte aligned and the
- * chunk's length is a multiple of 4, element by element otherwise.  No float atomics: the same bits on every run. */
+/* ---- the optimisers of build_optimizer (Trainer/models/__init__.py:360-372; optim.hip) ----------------------------------
+ * AdamW, Adam, SGD and LARS over ALL parameters in one launch each, and the clip norms that precede them.  One descriptor per
+ * parameter tensor (device memory, 64 bytes): a block owns one chunk (chunk_elems elements, a multiple of 4) of one tensor,
+ * chunk_tensor[c] = tensor of chunk c (device), first_chunk = index of the tensor's first chunk.  s0 = exp_avg (Adam, AdamW) |
+ * momentum_buffer (SGD) | mu (LARS); s1 = exp_avg_sq (Adam, AdamW; not read by the others, may be NULL).  g is multiplied by
+ * grad_scale first (unscale * clip).  bias1 = 1 - beta1^t, bias2_sqrt = sqrt(1 - beta2^t) of the tensor's own step count t
+ * (torch's optimisers keep one per parameter; Adam and AdamW alone).  q and wd are LARS' per-tensor trust ratio and weight
+ * decay (1 and 0 for a parameter the reference sees as 1-D, utils/misc.py:1299-1310; LARS alone).  16-byte accesses where
+ * p, g, s0 (and s1) are all 16-byte aligned and the chunk's length is a multiple of 4, element by element otherwise.  No float
+ * atomics: the same bits on every run. */
 typedef struct bfm_optim_tensor {
     float* p; const float* g; float* s0; float* s1;
     int64_t n;
@@ -1127,6 +1106,20 @@ typedef struct bfm_optim_tensor {
     int32_t first_chunk;
     float q, wd;
 } bfm_optim_tensor_t;
+/* utils/misc.py:1329-1338 clip_gradients' per-parameter norms: sums_out[t] = sum of squares of tensors[t].g (fp64, fixed
+ * order); nonfinite[0] |= 1 when some g holds inf / nan.  Reads g, n and first_chunk alone.  workspace >= nchunks * 8 bytes. */
+int bfm_grad_sumsq_multi(const bfm_optim_tensor_t* tensors, int ntensors, const int32_t* chunk_tensor, int nchunks,
+                         int64_t chunk_elems, double* sums_out, int32_t* nonfinite, void* workspace, size_t workspace_bytes,
+                         bfm_stream_t stream);
+/* torch.optim.AdamW of Trainer/models/__init__.py:362-366 (amsgrad off, maximize off; decoupled decay):
+ * g = grad_scale g;  p *= 1 - lr wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g g;  p -= (lr / bias1) m / (sqrt(v) / bias2_sqrt
+ * + eps), with 1 - beta formed in fp32. */
+int bfm_adamw_step_multi(const bfm_optim_tensor_t* tensors, int ntensors, const int32_t* chunk_tensor, int nchunks,
+                         int64_t chunk_elems, float lr, float beta1, float beta2, float eps, float weight_decay,
+                         bfm_stream_t stream);
+/* The same step t (1-based) on one flat parameter, bias1 and bias2_sqrt formed here (powf, sqrtf) */
+int bfm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                   float eps, float weight_decay, int step, float grad_scale, bfm_stream_t stream);
 /* torch.optim.Adam(params_groups) of Trainer/models/__init__.py:361-362 (amsgrad off, maximize off; coupled decay):
  * g = grad_scale g + wd p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g g;  p -= (lr / bias1) m / (sqrt(v) / bias2_sqrt + eps).
  * The betas are doubles so that 1 - beta is rounded to fp32 once, as torch forms it. */

@@ -1,9 +1,10 @@
 """One optimiser step of each kind over the parameter list of the shipped 64-wide 6-level net (264 M parameters, 1.06 GB;
 heads as views into head_w / head_b as TrainStep holds them), one launch per phase, candidates alternated in one process:
 
-  update    bfm_adamw_step_multi (train_heads.hip, the baseline), bfm_adam_step_multi, bfm_sgd_step_multi,
-            bfm_lars_step_multi (optim.hip)
+  update    bfm_adamw_step_multi (the baseline), bfm_adam_step_multi, bfm_sgd_step_multi, bfm_lars_step_multi
   measure   bfm_grad_sumsq_multi (AdamW, Adam, SGD), bfm_lars_sums_multi (LARS)
+
+all of optim.hip, on one descriptor table (bfm_optim_tensor_t).
 
 Algorithmic bytes per parameter byte: Adam / AdamW update 7 (p, g, m, v read; p, m, v written), SGD / LARS update 5,
 grad sumsq 1, the LARS measure 2.  Cold by size: every stream of a launch is 1.06 GB, four times the 256 MiB Infinity Cache,
@@ -78,15 +79,12 @@ class BufferSet:
             first += nch
         self.nchunks = len(cmap)
         self.cmap = torch.tensor(cmap, dtype=torch.int32, device=dev)
-        adam = np.zeros(len(self.views), dtype=TR._ADAM_DESC)
         opt = np.zeros(len(self.views), dtype=TR._OPT_DESC)
         b1 = np.float32(1.0) - np.float32(0.9) ** np.float32(10)
         b2 = np.sqrt(np.float32(1.0) - np.float32(0.999) ** np.float32(10))
         for i, (_, nd, v) in enumerate(self.views):
             ptrs = tuple(v[k].data_ptr() for k in ("p", "g", "s0", "s1"))
-            adam[i] = ptrs + (v["p"].numel(), 1.0, b1, b2, firsts[i], 0)
             opt[i] = ptrs + (v["p"].numel(), 1.0, b1, b2, firsts[i], 1.0 if nd == 1 else 1e-3, 0.0 if nd == 1 else 0.04)
-        self.adam = torch.from_numpy(adam.view(np.uint8).reshape(-1)).to(dev)
         self.opt = torch.from_numpy(opt.view(np.uint8).reshape(-1)).to(dev)
         self.sums = torch.zeros(3 * len(self.views), dtype=torch.float64, device=dev)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -123,27 +121,24 @@ def main():
     nbytes = 4.0 * sets[0].n_params
     lr, wd, mom = 1e-4, 0.04, 0.9
 
-    def head(s, desc):
-        return (L.ptr(desc), len(s.views), L.ptr(s.cmap), s.nchunks, CH)
-
-    def call(fn_name, desc_name, *tail, measure=False):
+    def call(fn_name, *tail, measure=False):
         fn = getattr(lib, fn_name)
 
         def run(i):
             s = sets[i % len(sets)]
-            args = head(s, getattr(s, desc_name))
+            args = (L.ptr(s.opt), len(s.views), L.ptr(s.cmap), s.nchunks, CH)
             if measure:
                 args += (L.ptr(s.sums), L.ptr(s.flag), L.ptr(s.ws), s.ws.numel() * 8)
             L.check(fn(*args, *tail, L.stream_ptr()), fn_name)
         return run
 
     cands = [
-        ("adamw update (baseline)", 7, call("bfm_adamw_step_multi", "adam", lr, 0.9, 0.999, 1e-8, wd)),
-        ("adam update", 7, call("bfm_adam_step_multi", "opt", lr, 0.9, 0.999, 1e-8, wd)),
-        ("sgd update", 5, call("bfm_sgd_step_multi", "opt", lr, mom, wd)),
-        ("lars update", 5, call("bfm_lars_step_multi", "opt", lr, mom)),
-        ("grad sumsq (measure)", 1, call("bfm_grad_sumsq_multi", "adam", measure=True)),
-        ("lars sums (measure)", 2, call("bfm_lars_sums_multi", "opt", measure=True)),
+        ("adamw update (baseline)", 7, call("bfm_adamw_step_multi", lr, 0.9, 0.999, 1e-8, wd)),
+        ("adam update", 7, call("bfm_adam_step_multi", lr, 0.9, 0.999, 1e-8, wd)),
+        ("sgd update", 5, call("bfm_sgd_step_multi", lr, mom, wd)),
+        ("lars update", 5, call("bfm_lars_step_multi", lr, mom)),
+        ("grad sumsq (measure)", 1, call("bfm_grad_sumsq_multi", measure=True)),
+        ("lars sums (measure)", 2, call("bfm_lars_sums_multi", measure=True)),
     ]
     res = {}
     for _ in range(2):                                     # alternate the kinds, keep the better pass of each

@@ -799,23 +799,39 @@ def test_weight_gradient_of_a_decoder_join_vs_float64(ca, cb, cout, dims):
     assert err <= 2e-5, err
 
 
-def test_multi_tensor_clip_norms_and_adamw_equal_the_per_tensor_kernels(monkeypatch):
-    """TrainStep.apply with all parameters in one launch each (bfm_grad_sumsq_multi, bfm_adamw_step_multi; round 4) against
-    the per-tensor kernels (BFM_ADAM_MULTI=0): same clipping norms to fp64 rounding of a different fold order, same
-    parameters after two steps to one float32 rounding of the bias corrections."""
+def test_multi_tensor_clip_norms_and_adamw_equal_the_per_tensor_kernels():
+    """TrainStep.apply with all parameters in one launch each (bfm_grad_sumsq_multi, bfm_adamw_step_multi) against the
+    per-tensor kernels of the C ABI, run here on clones of the parameters with the gradients apply consumed (bfm_grad_sumsq,
+    the coefficient of optim_refs.clip_coef on its norm, bfm_adamw_step): same clipping norms to fp64 rounding of a different
+    fold order, same parameters after two steps to one float32 rounding of the bias corrections."""
+    import math
+    import optim_refs as R
+    from brainfm_amd import _lib as L
     c = load_case()
-    outs = []
-    for multi in ("1", "0"):
-        monkeypatch.setenv("BFM_ADAM_MULTI", multi)
-        step, xs, target, samples = _build(c)
-        norms_all = []
-        for _ in range(2):
-            _, _, grads = step.loss_and_grads(xs, target, samples)
-            ok, norms = step.apply(grads)
-            assert ok
-            norms_all.append(norms)
-        outs.append((norms_all, {k: v.clone() for k, v in step.parameters().items()}))
-    (na, pa), (nb, pb) = outs
+    lib = L.load()
+    step, xs, target, samples = _build(c)
+    pb = {k: v.clone() for k, v in step.parameters().items()}
+    mv = {k: (torch.zeros(v.numel(), device=v.device), torch.zeros(v.numel(), device=v.device)) for k, v in pb.items()}
+    ws = torch.empty(lib.bfm_loss_workspace(0), dtype=torch.uint8, device=_dev())
+    na, nb = [], []
+    for t in (1, 2):
+        _, _, grads = step.loss_and_grads(xs, target, samples)
+        ok, norms = step.apply(grads)
+        assert ok
+        na.append(norms)
+        nb.append([])
+        for k in (k for k in pb if k in grads):
+            g = grads[k].contiguous()
+            out = torch.zeros(1, dtype=torch.float64, device=_dev())
+            flag = torch.zeros(1, dtype=torch.int32, device=_dev())
+            L.check(lib.bfm_grad_sumsq(L.ptr(g), g.numel(), L.ptr(out), L.ptr(flag), L.ptr(ws), ws.numel(), L.stream_ptr()), k)
+            assert int(flag.item()) == 0
+            nb[-1].append(math.sqrt(float(out.item())))
+            coef = R.clip_coef(g, c["clip"], norm=nb[-1][-1])
+            L.check(lib.bfm_adamw_step(L.ptr(pb[k]), L.ptr(g), L.ptr(mv[k][0]), L.ptr(mv[k][1]), g.numel(), c["lr"], c["b1"],
+                                       c["b2"], c["eps"], c["wd"], t, coef, L.stream_ptr()), k)
+    pa = step.parameters()
+    assert c["clip"] > 0 and len(nb[0]) == len(na[0]) == len(pa)
     assert np.allclose(na[0], nb[0], rtol=1e-12, atol=0)
     assert np.allclose(na[1], nb[1], rtol=1e-5, atol=1e-12)
     for k in pa:

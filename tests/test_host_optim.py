@@ -44,6 +44,19 @@ def test_adam_ref_equals_torch_adam_float64(wd):
 
 
 @pytest.mark.parametrize("wd", [0.0, 0.1])
+def test_adamw_ref_equals_torch_adamw_float64(wd):
+    p0, grads, ps, opt = _torch_run(lambda ps, wd: torch.optim.AdamW(ps, lr=3e-3, weight_decay=wd), wd)
+    for i in range(len(SHAPES) - 1):
+        p, m, v = p0[i], torch.zeros_like(p0[i]), torch.zeros_like(p0[i])
+        for t, gs in enumerate(grads, 1):
+            p, m, v = R.adamw_step(p, gs[i], m, v, t, 3e-3, weight_decay=wd)
+        assert float((p - ps[i].detach()).abs().max()) <= 1e-12
+        assert float((m - opt.state[ps[i]]["exp_avg"]).abs().max()) <= 1e-12
+        assert float((v - opt.state[ps[i]]["exp_avg_sq"]).abs().max()) <= 1e-12
+    assert torch.equal(ps[-1].detach(), p0[-1]) and ps[-1] not in opt.state     # no gradient: no step, no state
+
+
+@pytest.mark.parametrize("wd", [0.0, 0.1])
 def test_sgd_ref_equals_torch_sgd_float64(wd):
     p0, grads, ps, opt = _torch_run(lambda ps, wd: torch.optim.SGD(ps, lr=3e-3, momentum=0.9, weight_decay=wd), wd)
     for i in range(len(SHAPES) - 1):
