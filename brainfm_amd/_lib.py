@@ -226,6 +226,9 @@ SIGNATURES = {
     "bfm_head_bwd": (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _P, _P, _Z, _P]),
     "bfm_tail_raw_rows": (_I, [_P, _L, C.POINTER(TailDesc), _P, _P, _L, _P]),
     "bfm_head_bwd_rows": (_I, [_P, _L, _P, _P, _I, _I, _L, _P, _P, _P, _P, _Z, _P]),
+    "bfm_head_wgrad_workspace": (_Z, [_I, _I, _L]),
+    "bfm_head_wgrad": (_I, [_P, _P, _I, _I, _L, _P, _P, _P, _Z, _P]),
+    "bfm_head_wgrad_rows": (_I, [_P, _L, _P, _I, _I, _L, _P, _P, _P, _Z, _P]),
     "bfm_normalize_bwd": (_I, [_P, _P, _I, _L, _F, _P, _P]),
     "bfm_adamw_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P]),
     "bfm_grad_sumsq": (_I, [_P, _L, _P, _P, _P, _Z, _P]),

@@ -1039,6 +1039,26 @@ extern "C" size_t bfm_head_bwd_workspace(int n_out, int C, int64_t nvox) {
     return std::max(unfused, fused);
 }
 
+// dW and db of channels-last dRaw at any width: the split-K wave kernel and the column sums, each folded in order
+static void wgrad_colsum_launch(const float* dRaw, const float* Fn, int n_out, int C, int64_t nvox, float* dW, float* db,
+                                void* workspace, hipStream_t st) {
+    const int S = (int)std::min<int64_t>(256, std::max<int64_t>(1, nvox / 4096));
+    int64_t vps = bfm_cdiv64(nvox, S);
+    vps += vps & 1;                                              // even: the K pair never straddles two splits
+    const int S2 = (int)bfm_cdiv64(nvox, vps);
+    float* part = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(head_wgrad_kernel, dim3(S2, bfm_cdiv(n_out, 32), bfm_cdiv(C, 32)), dim3(64), 0, st, dRaw, Fn, n_out, C,
+                       nvox, vps, part);
+    hipLaunchKernelGGL(fold_splits_kernel, dim3(grid_for((int64_t)n_out * C)), dim3(256), 0, st, part, S2,
+                       (int64_t)n_out * C, dW);
+    double* cpart = reinterpret_cast<double*>(static_cast<char*>(workspace) + (((size_t)S * n_out * C * sizeof(float) + 255) & ~(size_t)255));
+    const int nb = grid_for(nvox, RB);
+    const int64_t vpb = bfm_cdiv64(nvox, nb);
+    const int nb2 = (int)bfm_cdiv64(nvox, vpb);
+    hipLaunchKernelGGL(colsum_kernel, dim3(nb2), dim3(256), 0, st, dRaw, n_out, nvox, vpb, cpart);
+    hipLaunchKernelGGL(colsum_fold_kernel, dim3(n_out), dim3(64), 0, st, cpart, nb2, n_out, db);
+}
+
 static int head_bwd_launch(const float* dRaw, int64_t row_stride, const float* Fn, const float* head_w, int n_out, int C,
                            int64_t nvox, float* dW, float* db, float* dFn, void* workspace, size_t workspace_bytes,
                            bfm_stream_t stream) {
@@ -1080,21 +1100,7 @@ static int head_bwd_launch(const float* dRaw, int64_t row_stride, const float* F
     }
     hipLaunchKernelGGL(head_dfeat_kernel, dim3(grid_for(nvox * C)), dim3(256), (size_t)n_out * C * sizeof(float), st, dRaw,
                        head_w, n_out, C, nvox, dFn);
-    const int S = (int)std::min<int64_t>(256, std::max<int64_t>(1, nvox / 4096));
-    int64_t vps = bfm_cdiv64(nvox, S);
-    vps += vps & 1;                                              // even: the K pair never straddles two splits
-    const int S2 = (int)bfm_cdiv64(nvox, vps);
-    float* part = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(head_wgrad_kernel, dim3(S2, bfm_cdiv(n_out, 32), bfm_cdiv(C, 32)), dim3(64), 0, st, dRaw, Fn, n_out, C,
-                       nvox, vps, part);
-    hipLaunchKernelGGL(fold_splits_kernel, dim3(grid_for((int64_t)n_out * C)), dim3(256), 0, st, part, S2,
-                       (int64_t)n_out * C, dW);
-    double* cpart = reinterpret_cast<double*>(static_cast<char*>(workspace) + (((size_t)S * n_out * C * sizeof(float) + 255) & ~(size_t)255));
-    const int nb = grid_for(nvox, RB);
-    const int64_t vpb = bfm_cdiv64(nvox, nb);
-    const int nb2 = (int)bfm_cdiv64(nvox, vpb);
-    hipLaunchKernelGGL(colsum_kernel, dim3(nb2), dim3(256), 0, st, dRaw, n_out, nvox, vpb, cpart);
-    hipLaunchKernelGGL(colsum_fold_kernel, dim3(n_out), dim3(64), 0, st, cpart, nb2, n_out, db);
+    wgrad_colsum_launch(dRaw, Fn, n_out, C, nvox, dW, db, workspace, st);
     return bfm_launch_status();
 }
 
@@ -1109,6 +1115,205 @@ extern "C" int bfm_head_bwd_rows(const float* dRaw_rows, int64_t row_stride, con
                                  size_t workspace_bytes, bfm_stream_t stream) {
     if (row_stride < nvox) return BFM_E_ARG;
     return head_bwd_launch(dRaw_rows, row_stride, Fn, head_w, n_out, C, nvox, dW, db, dFn, workspace, workspace_bytes, stream);
+}
+
+// ----------------------------------------------------------------------------- heads on a frozen backbone
+// dW and db alone (head-only fine-tuning: nothing behind the heads needs dFn).  Without the dFn product there is no W tile
+// and no [nvox][64] store, and what is left per 64-voxel tile is <= 6 blocks of 32 x 32 x 64 on the exact-fp32 matrix core.
+// Dealt by block to four waves (head_bwd_fused_kernel) two waves would carry two blocks and two one; here the TILE is cut
+// instead: wave w takes voxels 16 w .. 16 w + 15 into all 2 NOB blocks (accumulators in registers), so the four SIMDs run
+// the same number of MFMAs, and the column sums of dRaw (fp64) are spread the same way, a column per lane.  At the end the
+// four waves' accumulators are added through LDS in wave order and the workgroup leaves one dW / db partial; the dW
+// partials are folded by fold_splits_chunked_kernel, the db partials by colsum_fold_kernel: fixed order throughout, no
+// atomics.
+template <int NOB, bool ROWS>
+__global__ void __launch_bounds__(256, 2) head_wgrad_tile_kernel(const float* __restrict__ dRaw, const float* __restrict__ Fn,
+                                                              int n_out, int64_t nvox,
+                                                              int64_t rs /* ROWS: dRaw as [n_out] rows of pitch rs */,
+                                                              float* __restrict__ wpart, double* __restrict__ bpart) {
+    extern __shared__ float hsm[];
+    __shared__ double cs[4][HB_MAXO];
+    const int ldr = n_out | 1;                                    // odd stride: the per-voxel rows start on distinct banks
+    float* sR = hsm;                                              // [HB_TV][ldr]
+    float* sF = sR + HB_TV * ldr;                                 // [HB_TV][HB_C]
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, l32 = lane & 31, lh = lane >> 5;
+    floatx16 acc[NOB][2];
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[ob][cb][i] = 0.f;
+    double colsum[2] = {0.0, 0.0};                                // columns lane and lane + 64
+    const int64_t ntile = (nvox + HB_TV - 1) / HB_TV;
+    // A tile comes through registers: every load of the NEXT tile is issued before this tile's MFMAs and written to LDS
+    // after them, so the memory latency runs under the arithmetic.  A thread holds elements t, t + 256, ... of the tile's
+    // HB_TV * n_out values of dRaw (NR = 8 NOB of them cover 32 NOB rows) and four float4 of its Fn rows; voxels past the
+    // end are zeros.
+    constexpr int NR = 8 * NOB;
+    float rR[NR];
+    float4 rF[4];
+    // element i = t + 256 it of a channels-last tile is (voxel i / n_out, column i % n_out): stepped, not divided
+    const int cl_v = t / n_out, cl_o = t - cl_v * n_out, cl_dv = 256 / n_out, cl_do = 256 - cl_dv * n_out;
+    auto load_tile = [&](int64_t tb) {
+        const int64_t v0 = tb * HB_TV;
+        const int nv = (int)min<int64_t>(HB_TV, nvox - v0);
+        if (ROWS) {                                               // one 256-byte segment of a row per wave
+            const bool in = (t & (HB_TV - 1)) < nv;
+            const float* src = dRaw + (int64_t)(t >> 6) * rs + v0 + (t & (HB_TV - 1));
+#pragma unroll
+            for (int it = 0; it < NR; ++it, src += 4 * rs) rR[it] = (in && (t >> 6) + 4 * it < n_out) ? *src : 0.f;
+        } else {                                                  // the tile's rows are one contiguous run of dRaw
+            const float* src = dRaw + v0 * n_out + t;
+#pragma unroll
+            for (int it = 0; it < NR; ++it) rR[it] = t + 256 * it < nv * n_out ? src[256 * it] : 0.f;
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int i = t + 256 * it;
+            rF[it] = (i * 4) / HB_C < nv ? reinterpret_cast<const float4*>(Fn + v0 * HB_C)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto store_tile = [&]() {
+        if (ROWS) {
+            float* dst = sR + (t & (HB_TV - 1)) * ldr + (t >> 6);
+#pragma unroll
+            for (int it = 0; it < NR; ++it)
+                if ((t >> 6) + 4 * it < n_out) dst[4 * it] = rR[it];
+        } else {
+            int vl = cl_v, o = cl_o;
+#pragma unroll
+            for (int it = 0; it < NR; ++it) {
+                if (vl < HB_TV) sR[vl * ldr + o] = rR[it];
+                vl += cl_dv;
+                o += cl_do;
+                if (o >= n_out) { o -= n_out; ++vl; }
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) reinterpret_cast<float4*>(sF)[t + 256 * it] = rF[it];
+    };
+    load_tile(blockIdx.x);
+    for (int64_t tb = blockIdx.x; tb < ntile; tb += gridDim.x) {
+        __syncthreads();                                          // the previous tile's reads of sR / sF are over
+        store_tile();
+        __syncthreads();
+        if (tb + gridDim.x < ntile) load_tile(tb + gridDim.x);
+        const float* ap = sR + (w * 16 + lh) * ldr;
+        const float* bp = sF + (w * 16 + lh) * HB_C + l32;
+#pragma unroll 2
+        for (int v = 0; v < 16; v += 2) {
+            const float b0 = bp[v * HB_C], b1 = bp[v * HB_C + 32];
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob) {
+                const int o = ob * 32 + l32;
+                const bool ok = o < n_out;
+                const float a = ok ? ap[v * ldr + o] : 0.f;
+                acc[ob][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc[ob][0], 0, 0, 0);
+                acc[ob][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc[ob][1], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int o = lane + 64 * j;
+            if (o < n_out) {
+                double s_ = 0.0;
+                for (int v = 0; v < 16; ++v) s_ += (double)sR[(w * 16 + v) * ldr + o];
+                colsum[j] += s_;
+            }
+        }
+    }
+    // the four waves' sums, added in wave order over the tile buffers ([n_out][HB_C] fits in sR: ldr >= n_out)
+    float* red = hsm;
+    for (int ww = 0; ww < 4; ++ww) {
+        __syncthreads();
+        if (w == ww) {
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int row = ob * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh;
+                        if (row < n_out) {
+                            float* r = red + row * HB_C + cb * 32 + l32;
+                            *r = ww ? *r + acc[ob][cb][i] : acc[ob][cb][i];
+                        }
+                    }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        if (lane + 64 * j < n_out) cs[w][lane + 64 * j] = colsum[j];
+    __syncthreads();
+    float* wout = wpart + (int64_t)blockIdx.x * n_out * HB_C;
+    for (int i = t; i < n_out * HB_C; i += 256) wout[i] = red[i];
+    if (t < n_out) bpart[(int64_t)blockIdx.x * n_out + t] = ((cs[0][t] + cs[1][t]) + cs[2][t]) + cs[3][t];
+}
+
+// out[i] = sum_k part[k][i] over S workgroup partials, in a fixed order that keeps many loads in flight: a block takes 32
+// elements, thread (i, c) adds partials c S/8 .. (c + 1) S/8 - 1 in order, the eight chunk sums are then added in chunk
+// order.  (One thread walking all S partials of an element is a chain of S dependent-latency loads on 18 workgroups.)
+__global__ void __launch_bounds__(256) fold_splits_chunked_kernel(const float* __restrict__ part, int S, int64_t n,
+                                                                  float* __restrict__ out) {
+    __shared__ float red[8][32];
+    const int e = threadIdx.x & 31, c = threadIdx.x >> 5;
+    const int64_t i = (int64_t)blockIdx.x * 32 + e;
+    const int per = (S + 7) / 8, k0 = c * per, k1 = min(S, k0 + per);
+    float s = 0.f;
+    if (i < n) {
+#pragma unroll 8
+        for (int k = k0; k < k1; ++k) s += part[i + (int64_t)k * n];
+    }
+    red[c][e] = s;
+    __syncthreads();
+    if (c == 0 && i < n) {
+        float r = red[0][e];
+#pragma unroll
+        for (int j = 1; j < 8; ++j) r += red[j][e];
+        out[i] = r;
+    }
+}
+
+extern "C" size_t bfm_head_wgrad_workspace(int n_out, int C, int64_t nvox) { return bfm_head_bwd_workspace(n_out, C, nvox); }
+
+static int head_wgrad_launch(const float* dRaw, int64_t row_stride, const float* Fn, int n_out, int C, int64_t nvox, float* dW,
+                             float* db, void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+    if (!dRaw || !Fn || !dW || !db || !workspace || n_out <= 0 || C <= 0 || nvox <= 0) return BFM_E_ARG;
+    if (workspace_bytes < bfm_head_wgrad_workspace(n_out, C, nvox)) return BFM_E_WORKSPACE;
+    hipStream_t st = bfm_s(stream);
+    const bool tiled = C == HB_C && n_out <= HB_MAXO && (reinterpret_cast<uintptr_t>(Fn) & 15) == 0;
+    if (row_stride > 0 && !tiled) return BFM_E_SHAPE;             // as bfm_head_bwd_rows: rows feed the tile kernel only
+    if (!tiled) {
+        wgrad_colsum_launch(dRaw, Fn, n_out, C, nvox, dW, db, workspace, st);
+        return bfm_launch_status();
+    }
+    const int64_t ntile = (nvox + HB_TV - 1) / HB_TV;
+    const int nb = (int)std::min<int64_t>(HB_BLOCKS, ntile);
+    const size_t smem = ((size_t)HB_TV * (n_out | 1) + (size_t)HB_TV * HB_C) * sizeof(float);   // <= 41 KB
+    float* wpart = static_cast<float*>(workspace);
+    double* bpart = reinterpret_cast<double*>(static_cast<char*>(workspace) +
+                                              (((size_t)HB_BLOCKS * n_out * C * sizeof(float) + 255) & ~(size_t)255));
+    const bool rows = row_stride > 0;
+    auto kernel = n_out <= 32 ? (rows ? head_wgrad_tile_kernel<1, true> : head_wgrad_tile_kernel<1, false>)
+                : n_out <= 64 ? (rows ? head_wgrad_tile_kernel<2, true> : head_wgrad_tile_kernel<2, false>)
+                              : (rows ? head_wgrad_tile_kernel<3, true> : head_wgrad_tile_kernel<3, false>);
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), smem, st, dRaw, Fn, n_out, nvox, row_stride, wpart, bpart);
+    hipLaunchKernelGGL(fold_splits_chunked_kernel, dim3(bfm_cdiv(n_out * C, 32)), dim3(256), 0, st, wpart, nb,
+                       (int64_t)n_out * C, dW);
+    hipLaunchKernelGGL(colsum_fold_kernel, dim3(n_out), dim3(64), 0, st, bpart, nb, n_out, db);
+    return bfm_launch_status();
+}
+
+extern "C" int bfm_head_wgrad(const float* dRaw, const float* Fn, int n_out, int C, int64_t nvox, float* dW, float* db,
+                              void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+    return head_wgrad_launch(dRaw, 0, Fn, n_out, C, nvox, dW, db, workspace, workspace_bytes, stream);
+}
+
+extern "C" int bfm_head_wgrad_rows(const float* dRaw_rows, int64_t row_stride, const float* Fn, int n_out, int C, int64_t nvox,
+                                   float* dW, float* db, void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+    if (row_stride < nvox) return BFM_E_ARG;
+    return head_wgrad_launch(dRaw_rows, row_stride, Fn, n_out, C, nvox, dW, db, workspace, workspace_bytes, stream);
 }
 
 extern "C" int bfm_normalize_bwd(const float* feat, const float* dFn, int C, int64_t nvox, float eps, float* dfeat,

@@ -351,11 +351,13 @@ class UNetEngine:
                                                       L.ptr(buf), C.byref(wexp), st), "pack_upfold " + ly.name)
         ly.packs["upfold"] = (buf, wexp.value)
 
-    def repack_all(self, refresh=None):
+    def repack_all(self, refresh=None, backbone=True):
         """The weights changed in place (training): rebuild, into the same buffers, every packed form a layer launched in
         the last pass (forward variants, skip half, up-folded form, the transposed data-gradient layer that backward.py
         hangs on it), so that nothing is packed lazily inside the next pass; forms only the autotune trials used are
-        dropped.  All max |w| come to the host in ONE copy.  `refresh(ly, dg)` re-derives a data-gradient layer's weights."""
+        dropped.  All max |w| come to the host in ONE copy.  `refresh(ly, dg)` re-derives a data-gradient layer's weights.
+        backbone=False: only the hidden head layers changed (training on a frozen backbone); the encoder and decoder layers
+        keep their packed forms and their record of what the last pass used."""
         jobs = []                                          # (layer, layout, max|w| tensor)
         self.weights_epoch += 1
 
@@ -403,7 +405,7 @@ class UNetEngine:
                 ly.skip.w_raw.copy_(ly.w_raw[:, :ly.skip.cin])
                 visit(ly.skip)
 
-        for pair in self.enc + self.dec + [hidden]:
+        for pair in (self.enc + self.dec if backbone else []) + [hidden]:
             for ly in pair:
                 visit(ly)
         host = slots[:nslot[0]].cpu().tolist() if nslot[0] else []

@@ -12,6 +12,10 @@ Mirrors the reference's iteration -- Trainer/engine.py:96-147:
     scaler.step(optimizer); scaler.update()           -> bfm_adamw_step_multi | bfm_adam_step_multi | bfm_sgd_step_multi |
                                                          bfm_lars_step_multi, LossScaler.update         (TrainStep._update)
 
+With train_args.freeze_feat (TrainStep(trainable='head')) the backbone is frozen: model(samples) runs on the inference kernels
+without a tape, backward() ends at the heads (bfm_head_wgrad: dW and db, no feature gradient) and the optimiser sees the
+`head.` tensors alone.
+
 The four optimisers share one path: one descriptor per parameter (bfm_optim_tensor_t), one chunk map, one measuring launch and
 one update launch over all tensors, whatever the kind.
 
@@ -44,6 +48,27 @@ SUPPORTED = set(IMAGE_KEYS) | {k + "_grad" for k in IMAGE_KEYS} | {
     "SR", "SR_grad", "distance", "surface", "registration", "registration_grad", "registration_smooth",
     "registration_hessian", "bias_field_log", "seg_ce", "seg_dice", "pathol_ce", "pathol_dice", "age"}
 REG_REGULARISERS = ("registration_smooth", "registration_hessian")
+TRAINABLE = ("all", "head")
+
+
+def trainable_names(names, trainable):
+    """The parameter names a step with TrainStep(trainable=...) trains, in the order given: 'all' keeps every name, 'head'
+    the task head's (`head.`: the 1x1x1 heads, hidden head layers, the pooled scalar head) -- what scripts/train.py:46-53
+    get_params_groups keeps of a model whose backbone has requires_grad = False."""
+    if trainable == "all":
+        return list(names)
+    if trainable == "head":
+        return [n for n in names if n.startswith("head.")]
+    raise ValueError("trainable=%r: one of %s" % (trainable, ", ".join(repr(t) for t in TRAINABLE)))
+
+
+def freeze_feat_of(train_args):
+    """train_args.freeze_feat (cfgs/trainer/default_train.yaml:77) as a bool; a missing key is False.  The `feat_opt` block
+    beside it (default_train.yaml:90-92, always present) is not read: no line of the reference reads it either, every
+    trained tensor is in the one parameter group of scripts/train.py:46-53, and a frozen backbone has no group at all."""
+    if isinstance(train_args, dict):
+        return bool(train_args.get("freeze_feat", False))
+    return bool(getattr(train_args, "freeze_feat", False))
 
 
 def criterion_losses(train_args, tasks, exclude_keys=()):
@@ -337,12 +362,21 @@ def lars_trust_ratio(sum_gg, sum_pp, sum_pg, coef, weight_decay, eta):
 
 class TrainStep:
     """Parameters live in the engine (layer .w_raw / .gamma / .beta) and the tail (head_w / head_b); `step` updates
-    them in place and drops the packed-weight caches so that the next forward repacks."""
+    them in place and drops the packed-weight caches so that the next forward repacks.
+
+    trainable='head' is head-only fine-tuning on a frozen backbone (train_args.freeze_feat; the reference sets
+    requires_grad = False on the backbone and get_params_groups, scripts/train.py:46-53, leaves it out of the optimiser):
+    the backbone runs on the inference kernels without a tape, the backward pass ends at the heads (bfm_head_wgrad: no
+    feature gradient), gradients, optimiser state, clip norms and the scaler's check cover the `head.` tensors alone, and
+    nothing of the backbone is touched or repacked.  One rank only."""
     hidden = ()                 # the hidden head layers' records (steps without a task head have none)
+    trainable = "all"
 
     def __init__(self, engine, tail, loss_names, loss_weights, weights_ce, all_samples, max_surf_distance=3.0,
                  bias_field_log_type="l2", lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, clip_max_norm=0.0,
-                 scaler=None, age_head=None, optimizer="adamw"):
+                 scaler=None, age_head=None, optimizer="adamw", trainable="all"):
+        trainable_names((), trainable)                     # an unknown value raises here
+        self.trainable = trainable
         if "contrastive" in loss_names:
             # the reference never mixes it with other losses (get_criterion returns early, Trainer/models/__init__.py:169-178)
             raise L.BfmError("loss 'contrastive' is the head-less pre-training mode: use ContrastiveStep, not TrainStep")
@@ -439,6 +473,8 @@ class TrainStep:
 
     def grad_store(self):
         """The persistent gradient buffer (GradStore), slots in the order the backward pass completes them."""
+        if self.trainable != "all":
+            raise L.BfmError("TrainStep(trainable=%r) runs on one rank: it has no bucketed gradient all-reduce" % self.trainable)
         st = self.__dict__.get("_grad_store")
         if st is None:
             named = [("head.weight_all", (self.tail.n_out, self.tail.c_feat)), ("head.bias_all", (self.tail.n_out,))]
@@ -457,8 +493,10 @@ class TrainStep:
 
     def _weights_changed(self):
         """Right after the optimiser: every packed form a layer holds (forward variants, skip half, up-folded, transposed
-        data-gradient layer) is rebuilt in place, so the next pass packs nothing lazily."""
-        self.eng.repack_all(refresh=BW.refresh_dgrad)
+        data-gradient layer) is rebuilt in place, so the next pass packs nothing lazily.  A step on a frozen backbone
+        rebuilds the hidden head layers' forms alone and leaves every backbone layer as it is: its optimiser cannot have
+        moved one."""
+        self.eng.repack_all(refresh=BW.refresh_dgrad, backbone=self.trainable == "all")
         hw = torch.zeros(1, dtype=torch.float32, device=self.dev)
         L.check(self.lib.bfm_absmax_f32(L.ptr(self.tail.head_w), 1, self.tail.head_w.numel(), self.tail.head_w.numel(),
                                         L.ptr(hw), L.stream_ptr()), "absmax head_w")
@@ -476,9 +514,12 @@ class TrainStep:
 
     def optimizer_state_dict(self, lr=None, weight_decay=None):
         """state_dict() layout of this step's optimiser (torch.optim.AdamW / Adam / SGD, utils.LARS) for the single parameter
-        group of scripts/train.py:46-53 (parameters in model.named_parameters() order == self.parameters() order)."""
+        group of scripts/train.py:46-53 (parameters in model.named_parameters() order == self.parameters() order).  On a
+        frozen backbone the group indexes the trainable tensors alone, in that order: get_params_groups skips a parameter
+        with requires_grad = False, so torch numbers what is left."""
         lr, wd = self._hyper(lr, weight_decay)
         params = self.parameters()
+        params = OrderedDict((k, params[k]) for k in trainable_names(list(params), self.trainable))
         state = {}
         for i, (k, p) in enumerate(params.items()):
             if k in self.state:
@@ -520,15 +561,20 @@ class TrainStep:
         """torch.save of {'model', 'optimizer', 'epoch', ...}: what utils.save_on_master writes in scripts/train.py, and
         what brainfm_amd.models.load_checkpoint / the reference's load_checkpoint read back."""
         ckp = {"model": self.state_dict(), "optimizer": self.optimizer_state_dict(), "epoch": int(epoch),
-               "scaler_scale": self.scaler.scale, "optimizer_kind": self.opt_kind}
+               "scaler_scale": self.scaler.scale, "optimizer_kind": self.opt_kind, "trainable": self.trainable}
         ckp.update(extra)
         torch.save(ckp, path)
 
     def load_checkpoint(self, path):
         """Parameters (matched by name suffix, as utils/checkpoint.py:558-571) and the optimiser's buffers back into the
         engine.  Optimiser state of another kind than this step's raises: 'optimizer_kind' decides, or the state's keys for a
-        checkpoint the reference wrote (exp_avg is never read as a momentum buffer)."""
+        checkpoint the reference wrote (exp_avg is never read as a momentum buffer).  So does a checkpoint whose 'trainable'
+        entry (absent: 'all') is not this step's: its optimiser state numbers another list of tensors."""
         ckp = M.read_checkpoint_file(path)
+        wrote = ckp.get("trainable", "all") if isinstance(ckp, dict) else "all"
+        if wrote != self.trainable:
+            raise L.BfmError("checkpoint %s was written by a step with trainable=%r; this step has trainable=%r and does not "
+                             "renumber its optimiser state" % (path, wrote, self.trainable))
         opt = ckp.get("optimizer")
         if opt and opt.get("state"):
             keys = set().union(*(set(st.keys()) for st in opt["state"].values()))
@@ -559,9 +605,11 @@ class TrainStep:
             if src.numel() != p.numel():
                 raise ValueError("shape mismatch for %s: %s vs %s" % (k, tuple(src.shape), tuple(p.shape)))
             p.copy_(src.reshape(p.shape).to(device=self.dev, dtype=torch.float32))
+        if self.trainable != "all":
+            self.eng.repack_all(refresh=BW.refresh_dgrad)      # the file's backbone replaced the frozen one, this once
         self._weights_changed()
         if opt and opt.get("state"):
-            names = list(params.keys())
+            names = trainable_names(list(params.keys()), self.trainable)
             self.state = {}
             for i, st in opt["state"].items():
                 k = names[int(i)]
@@ -774,7 +822,10 @@ class TrainStep:
         elif tuple(x_cl.shape) != dims + (eng.in_channels,) or x_cl.dtype != torch.float32 or not x_cl.is_contiguous():
             raise L.BfmError("conditioned input %s %s: the network reads contiguous fp32 %s"
                              % (tuple(x_cl.shape), x_cl.dtype, dims + (eng.in_channels,)))
-        feats, tape = BW.backbone_forward_train(eng, x_cl, dims)
+        if self.trainable == "head":
+            feats, tape = eng.backbone_cl(x_cl, dims), None        # frozen: the inference path, nothing taped or kept
+        else:
+            feats, tape = BW.backbone_forward_train(eng, x_cl, dims)
         feat_last = feats[-1][0]
         head_in, hid_tape = feat_last, None
         if self.hidden:
@@ -791,6 +842,8 @@ class TrainStep:
         if fn is None:
             fn = head_in
         dRaw = torch.zeros_like(raw)
+        if tape is None:
+            feats = feat_last = None                       # frozen: only fn (and the hidden layers' tape) is read again
         return dict(dims=dims, feats=feats, tape=tape, feat_last=feat_last, rows=rows, raw=raw, fn=fn, dRaw=dRaw,
                     hid_tape=hid_tape)
 
@@ -806,6 +859,11 @@ class TrainStep:
         pre_heads: called with the context first; it may add into ctx['dRaw'] before the heads' backward reads it, and may
         run the sample's criterion itself (two-stage training: the stage-1 gradient through the mask).
         input_grad: a backward.InputGrad for the first layer."""
+        if self.trainable == "head":
+            if pre_heads is not None or input_grad is not None:
+                raise L.BfmError("a step on a frozen backbone has no gradient in front of its heads to hand on (two-stage "
+                                 "training is not built with freeze_feat)")
+            return self._sample_backward_heads(ctx, target, scale)
         if pre_heads is not None:
             pre_heads(ctx)
         eng, tail, lib = self.eng, self.tail, self.lib
@@ -833,25 +891,8 @@ class TrainStep:
             sink.done("head.bias_all")
         age_grads = None
         if age_tape is not None:
-            # criterion.py loss_age; its pooled gradient joins dFn after the dense heads' and before normalize_bwd
-            age_t = self._age_target(target)
-            on = "age" in self.loss_names and age_t is not None
-            coef = self._coef("age", scale) if on else 0.0
-            loss_ptr = None
-            if on:
-                slots["age"] = [(k_used, 1)]
-                loss_ptr = C.c_void_p(vals.data_ptr() + 8 * k_used)
-                self._touched_heads.add("age")
-            age_grads = OrderedDict()
-            for k_, v_ in self.age.params.items():
-                name = "head." + k_
-                age_grads[name] = (sink.out(name, tuple(v_.shape)) if sink is not None else
-                                   torch.empty(v_.shape, dtype=torch.float32, device=self.dev))
-            self.age.backward(age_tape, age_t if on else 0.0, coef, loss_ptr,
-                              {k_[5:]: v_ for k_, v_ in age_grads.items()}, dFn)
-            if sink is not None:
-                for name in age_grads:
-                    sink.done(name)
+            # its pooled gradient joins dFn after the dense heads' and before normalize_bwd
+            age_grads = self._age_backward(age_tape, target, scale, slots, k_used, vals, dFn, sink)
         hid_grads = OrderedDict()
         for hl, x_in, x_bound, y in reversed(ctx.get("hid_tape") or []):
             # the hidden layers, last to first: dFn is the gradient of the layer's output on the way in, of its input after
@@ -875,6 +916,82 @@ class TrainStep:
         self._touched_heads.update(task for task, (r0, n) in tail.row_of.items()
                                    if any(r in ctx["active"] for r in range(r0, r0 + n)))
         return g, slots, vals
+
+    def _age_backward(self, age_tape, target, scale, slots, k_used, vals, dFn, sink=None):
+        """criterion.py loss_age of one sample and the pooled head's backward: the loss value into the sample's next fp64
+        slot, the parameter gradients returned as {name: tensor}, the gradient of the normalised feature ADDED into dFn."""
+        age_t = self._age_target(target)
+        on = "age" in self.loss_names and age_t is not None
+        coef = self._coef("age", scale) if on else 0.0
+        loss_ptr = None
+        if on:
+            slots["age"] = [(k_used, 1)]
+            loss_ptr = C.c_void_p(vals.data_ptr() + 8 * k_used)
+            self._touched_heads.add("age")
+        age_grads = OrderedDict()
+        for k_, v_ in self.age.params.items():
+            name = "head." + k_
+            age_grads[name] = (sink.out(name, tuple(v_.shape)) if sink is not None else
+                               torch.empty(v_.shape, dtype=torch.float32, device=self.dev))
+        self.age.backward(age_tape, age_t if on else 0.0, coef, loss_ptr,
+                          {k_[5:]: v_ for k_, v_ in age_grads.items()}, dFn)
+        if sink is not None:
+            for name in age_grads:
+                sink.done(name)
+        return age_grads
+
+    def _sample_backward_heads(self, ctx, target, scale):
+        """Backward of one sample on a frozen backbone: it ends where the last trainable tensor is reached.  Without hidden
+        head layers that is the 1x1x1 heads themselves, whose dW / db come from bfm_head_wgrad[_rows] with no feature
+        gradient formed; with hidden layers bfm_head_bwd[_rows] hands dFn down to the first of them, which forms no input
+        gradient.  The pooled scalar head's backward adds into a scratch feature gradient nobody reads (hidden layers and the
+        pooled head together never get here: __init__ refuses the pair)."""
+        eng, tail, lib = self.eng, self.tail, self.lib
+        dims, rows, fn, dRaw = ctx["dims"], ctx["rows"], ctx["fn"], ctx["dRaw"]
+        slots, k_used, vals = ctx["slots"], ctx["k_used"], ctx["vals"]
+        nvox = dims[0] * dims[1] * dims[2]
+        n_out, cf = tail.n_out, tail.c_feat
+        st = L.stream_ptr()
+        dW = torch.empty((n_out, cf), dtype=torch.float32, device=self.dev)
+        db = torch.empty(n_out, dtype=torch.float32, device=self.dev)
+        hid_tape = ctx.get("hid_tape") or []
+        g = OrderedDict()
+        if hid_tape:
+            dFn = torch.empty((nvox, cf), dtype=torch.float32, device=self.dev)
+            wsb = torch.empty(lib.bfm_head_bwd_workspace(n_out, cf, nvox), dtype=torch.uint8, device=self.dev)
+            if rows:
+                L.check(lib.bfm_head_bwd_rows(L.ptr(dRaw), nvox, L.ptr(fn), L.ptr(tail.head_w), n_out, cf, nvox, L.ptr(dW),
+                                              L.ptr(db), L.ptr(dFn), L.ptr(wsb), wsb.numel(), st), "head_bwd_rows")
+            else:
+                L.check(lib.bfm_head_bwd(L.ptr(dRaw), L.ptr(fn), L.ptr(tail.head_w), n_out, cf, nvox, L.ptr(dW), L.ptr(db),
+                                         L.ptr(dFn), L.ptr(wsb), wsb.numel(), st), "head_bwd")
+            for i, (hl, x_in, x_bound, y) in enumerate(reversed(hid_tape)):
+                first = i + 1 == len(hid_tape)                 # the first hidden layer: nothing trainable in front of it
+                dX, gr = BW.backward_head_layer(eng, hl, x_in, x_bound, y, dFn.view(dims + (hl.cout,)), dims,
+                                                need_input_grad=not first)
+                g.update(gr)
+                if not first:
+                    dFn = dX.reshape(nvox, hl.cin)
+        else:
+            wsb = torch.empty(lib.bfm_head_wgrad_workspace(n_out, cf, nvox), dtype=torch.uint8, device=self.dev)
+            if rows:
+                L.check(lib.bfm_head_wgrad_rows(L.ptr(dRaw), nvox, L.ptr(fn), n_out, cf, nvox, L.ptr(dW), L.ptr(db),
+                                                L.ptr(wsb), wsb.numel(), st), "head_wgrad_rows")
+            else:
+                L.check(lib.bfm_head_wgrad(L.ptr(dRaw), L.ptr(fn), n_out, cf, nvox, L.ptr(dW), L.ptr(db), L.ptr(wsb),
+                                           wsb.numel(), st), "head_wgrad")
+        heads = OrderedDict()
+        for task, (r0, n) in tail.row_of.items():
+            heads["head.final_conv_%s.weight" % task] = dW[r0:r0 + n]
+            heads["head.final_conv_%s.bias" % task] = db[r0:r0 + n]
+        if self.age is not None:
+            _, age_tape = self.age.forward(fn, dims)
+            scratch = torch.zeros((nvox, cf), dtype=torch.float32, device=self.dev)
+            heads.update(self._age_backward(age_tape, target, scale, slots, k_used, vals, scratch))
+        heads.update(g)
+        self._touched_heads.update(task for task, (r0, n) in tail.row_of.items()
+                                   if any(r in ctx["active"] for r in range(r0, r0 + n)))
+        return heads, slots, vals
 
     @staticmethod
     def _age_target(target):
@@ -1007,6 +1124,11 @@ class TrainStep:
         lib, st = self.lib, L.stream_ptr()
         params = self.parameters()
         names = [k for k in params if k in grads]
+        if self.trainable != "all":
+            frozen = sorted(set(names) - set(trainable_names(names, self.trainable)))
+            if frozen:
+                raise L.BfmError("gradients for %d tensors a step with trainable=%r keeps frozen (%s, ...)"
+                                 % (len(frozen), self.trainable, frozen[0]))
         for k in names:
             grads[k] = grads[k].contiguous()
             if not params[k].is_contiguous():
@@ -1093,8 +1215,13 @@ class TrainStep:
         the loss dictionary is averaged over the ranks first (utils.reduce_dict, engine.py:124-130) and the skip decision
         is taken on that reduced value, so every rank skips -- or enters the gradient all-reduce -- together."""
         import torch.distributed as dist
+        if self.trainable != "all":
+            world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+            if group is not None or world > 1:
+                raise L.BfmError("TrainStep(trainable=%r) is single-rank in this version: the step on a frozen backbone has "
+                                 "no gradient all-reduce (group given or world size %d)" % (self.trainable, world))
         self._group = group
-        self._store_next = True
+        self._store_next = self.trainable == "all"         # a frozen step never touches the GradStore
         loss_dict, total, grads = self.loss_and_grads(xs, target, samples, cond=cond)
         store = self.__dict__.pop("_store_live", None)
         touched = set(self._touched_heads)
@@ -1185,6 +1312,20 @@ def conditioned_train_step(gen_args, train_args, model, weights_ce, all_samples,
         raise L.BfmError("condition %r needs %d input channels, the backbone has %d"
                          % (train_args.condition, 1 + n_cond, eng.in_channels))
     kw.setdefault("max_surf_distance", float(gen_args.max_surf_distance))
+    kw.setdefault("trainable", "head" if freeze_feat_of(train_args) else "all")
+    return TrainStep(eng, model.head.tail(eng), names, weights, weights_ce, all_samples, **kw)
+
+
+def train_step(gen_args, train_args, model, weights_ce, all_samples, **kw):
+    """The TrainStep of the plain model: (gen_args, train_args, model) as build_model returns them, losses as its
+    get_criterion(gen_args, train_args, gen_args.tasks) builds them.  train_args.freeze_feat (cfgs/trainer/default_train.yaml)
+    gives trainable='head': the reference's requires_grad = False on the backbone."""
+    eng = model.backbone.engine(model.head)
+    names, weights = criterion_losses(train_args, gen_args.tasks)
+    kw.setdefault("max_surf_distance", float(gen_args.max_surf_distance))
+    kw.setdefault("trainable", "head" if freeze_feat_of(train_args) else "all")
+    if model.head.age_task is not None:
+        kw.setdefault("age_head", model.head.age_head())
     return TrainStep(eng, model.head.tail(eng), names, weights, weights_ce, all_samples, **kw)
 
 
@@ -1212,6 +1353,9 @@ class TwoStageTrainStep:
     def __init__(self, pathol_step, task_step, loss_names=None):
         s0, s1 = pathol_step, task_step
         for s_ in (s0, s1):
+            if s_.trainable != "all":
+                raise L.BfmError("TwoStageTrainStep takes steps with trainable='all': a frozen backbone (freeze_feat) is not "
+                                 "built for the two coupled models")
             if torch.device(s_.dev).type != "cuda":
                 raise L.BfmError("TwoStageTrainStep runs on a HIP device only; there is no CPU fallback in the product path")
         if torch.device(s0.dev) != torch.device(s1.dev):
@@ -1367,6 +1511,9 @@ def twostage_train_step(gen_args, train_args, pathol_model, task_model, weights_
     name to stage 1, and the merged dictionary keeps the criterion's order.  train_args.condition None or 'mask' is the
     loop's runnable path; with 'flip' the reference concatenates three channels into a backbone built with num_cond=1
     (engine.py:240-242 against models/__init__.py:451), which cannot run, so it is refused here."""
+    if freeze_feat_of(train_args) or kw.get("trainable", "all") != "all":
+        raise L.BfmError("freeze_feat: two-stage training couples two backbones through the predicted mask (stage 0 learns "
+                         "from stage 1's input gradient); a frozen backbone is not built for twostage_train_step")
     cond = getattr(train_args, "condition", None)
     if cond and "flip" in str(cond):
         raise L.BfmError("condition %r: the reference's two-stage loop builds a 3-channel input with 'flip' for a stage-1 "
@@ -1530,3 +1677,18 @@ class ContrastiveStep(TrainStep):
             raise L.BfmError("ContrastiveStep runs on one rank: the gradient all-reduce of the contrastive step is not "
                              "built (world size %d)" % dist.get_world_size(group))
         return super().step(xs, target, samples, lr=lr, weight_decay=weight_decay, group=group)
+
+
+def contrastive_train_step(gen_args, train_args, model, **kw):
+    """The ContrastiveStep of the head-less model: (gen_args, train_args, model) as build_model returns them for
+    gen_args.task.contrastive, the loss weight as get_criterion reads it (train_args.weights.contrastive) and the temperatures
+    from train_args.contrastive_temperatures.{alpha, beta, gamma} (criterion.py:45-48).  train_args.freeze_feat is refused by
+    name: the backbone is all this model trains."""
+    if freeze_feat_of(train_args):
+        raise L.BfmError("freeze_feat: ContrastiveStep trains the backbone alone (the contrastive model has no head); with a "
+                         "frozen backbone nothing is left to train")
+    names, weights = criterion_losses(train_args, gen_args.tasks)
+    if names != ["contrastive"]:
+        raise L.BfmError("contrastive_train_step builds the step of task 'contrastive'; the tasks are %s" % (list(gen_args.tasks),))
+    t = train_args.contrastive_temperatures
+    return ContrastiveStep(model.backbone.engine(model.head), weights, (t.alpha, t.beta, t.gamma), **kw)

@@ -1083,6 +1083,17 @@ int bfm_tail_raw_rows(const float* feat, int64_t nvox, const bfm_tail_desc_t* de
 int bfm_head_bwd_rows(const float* dRaw_rows, int64_t row_stride, const float* Fn, const float* head_w, int n_out, int C,
                       int64_t nvox, float* dW, float* db, float* dFn, void* workspace, size_t workspace_bytes,
                       bfm_stream_t stream);
+/* The heads' backward on a frozen backbone (train.TrainStep(trainable="head")): dW [n_out][C] = dRaw^T . Fn and db [n_out] =
+ * the column sums of dRaw, both written; no head weights are read, no dRaw . W product is formed and no [nvox][C] tensor is
+ * stored.  Widths as bfm_head_bwd / bfm_head_bwd_rows: the rows form takes C == 64 and n_out <= 96 (BFM_E_SHAPE otherwise;
+ * row_stride < nvox: BFM_E_ARG), the channels-last form every C and n_out >= 1.  Exact-fp32 products (fp32-input matrix
+ * core), the sum over nvox in a fixed order in two stages through the workspace, no atomics: the same bits on every run, and
+ * the same bits from both layouts at C == 64, n_out <= 96.  The bits are not those of bfm_head_bwd's dW. */
+size_t bfm_head_wgrad_workspace(int n_out, int C, int64_t nvox);
+int bfm_head_wgrad(const float* dRaw, const float* Fn, int n_out, int C, int64_t nvox, float* dW, float* db, void* workspace,
+                   size_t workspace_bytes, bfm_stream_t stream);
+int bfm_head_wgrad_rows(const float* dRaw_rows, int64_t row_stride, const float* Fn, int n_out, int C, int64_t nvox, float* dW,
+                        float* db, void* workspace, size_t workspace_bytes, bfm_stream_t stream);
 int bfm_normalize_bwd(const float* feat, const float* dFn, int C, int64_t nvox, float eps, float* dfeat,
                       bfm_stream_t stream);
 /* out[0] = sum g^2 (fp64); nonfinite[0] |= 1 when g holds inf/nan (GradScaler.unscale_ / clip_grad_norm_) */
