@@ -200,6 +200,7 @@ SIGNATURES = {
     "bfm_lrelu_bwd": (_I, [_P, _P, _L, _F, _P, _P]),
     "bfm_lrelu_bwd_ex": (_I, [_P, _P, _L, _F, _P, _P, _P]),
     "bfm_conv3x3x3_wgrad_workspace": (_Z, [_I, _I, _I, _I, _I]),
+    "bfm_conv3x3x3_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(_Z)]),
     "bfm_conv3x3x3_wgrad": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _P, _P, _Z, _P]),
     "bfm_conv3x3x3_wgrad_ex": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _P]),
     "bfm_stem_mc_bwd_workspace": (_Z, [_I, _I, _I, _I, _I]),

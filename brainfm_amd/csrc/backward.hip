@@ -10,7 +10,7 @@
 //   GroupNorm:  dbeta_c = sum_v dXn,  dgamma_c = sum_v dXn*xhat,
 //               dx = rstd_g * (gamma_c*dXn - m1_g - xhat*m2_g),   m1 = mean_g(gamma*dXn), m2 = mean_g(gamma*dXn*xhat)
 //   nearest upsample: the gradient of a low-res voxel is the sum over the box of its replicas.
-#include "bfm_common.h"
+#include "conv_shared.h"
 
 #define GRID_STRIDE(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)(n); i += (int64_t)gridDim.x * blockDim.x)
@@ -1368,86 +1368,164 @@ extern "C" int bfm_lrelu_bwd(const float* dY, const float* Y, int64_t n, float s
     return bfm_lrelu_bwd_ex(dY, Y, n, slope, dP, nullptr, stream);
 }
 
+// ----------------------------------------------------------------------------- weight gradient: route plan and launchers
 namespace {
-struct WgPlan { int kind; int S; int rows_per_split; int nbz, nby, nbx, ntiles; };    // kind 0 tiled (fp32 or f16 tiles), 1 columns
-WgPlan wgrad_plan(int CA, int Cin, int Cout, int D, int H, int W, bool f16 = false) {
-    WgPlan pl{};
-    if (Cout % 64 == 0 && Cin % 32 == 0 && CA % 32 == 0) {
-        pl.kind = 0;
-        pl.nbz = bfm_cdiv(D, f16 ? HT_Z : WT_Z); pl.nby = bfm_cdiv(H, f16 ? HT_Y : WT_Y); pl.nbx = bfm_cdiv(W, f16 ? HT_X : WT_X);
-        pl.ntiles = pl.nbz * pl.nby * pl.nbx;
-        const int cols = (Cin / 32) * (Cout / 64);
-        int S = 512 / cols;                               // two full rounds of one workgroup per CU, never a third
-        if (S > pl.ntiles) S = pl.ntiles;
-        if (S < 1) S = 1;
-        const int per = bfm_cdiv(pl.ntiles, S);
-        pl.S = bfm_cdiv(pl.ntiles, per);                  // every workgroup gets `per` tiles, the last maybe fewer
-    } else {
-        pl.kind = 1;
-        const int nrows = D * H;
-        const int blocks = bfm_cdiv(Cout, 32) * bfm_cdiv(Cin * 27, 32);
-        int S = bfm_cdiv(2048, blocks);
-        if (S > nrows) S = nrows;
-        if (S < 1) S = 1;
-        pl.rows_per_split = bfm_cdiv(nrows, S);
-        pl.S = bfm_cdiv(nrows, pl.rows_per_split);
-    }
-    return pl;
+constexpr int WG_BUDGET = 512;        // workgroups of a tiled launch: two full rounds of one per CU, never a third
+struct WgSplit { int S, per, cap; };  // S workgroups of `per` units each, the last maybe fewer, none empty; S <= cap
+WgSplit wgrad_split_under(int n, int cap) {
+    cap = std::max(1, std::min(n, cap));
+    const int per = bfm_cdiv(n, cap);
+    return {bfm_cdiv(n, per), per, cap};
 }
-}  // namespace
+// THE split of every tiled kernel (fp32, f16, wave-specialised, upsampled): each of `cols` workgroup columns over `ntiles`
+WgSplit wgrad_split(int ntiles, int cols) { return wgrad_split_under(ntiles, WG_BUDGET / cols); }
+// the column kernel splits the volume's (z, y) rows instead, towards 2048 blocks of 64 threads
+WgSplit wgrad_row_split(int nrows, int blocks) { return wgrad_split_under(nrows, bfm_cdiv(2048, blocks)); }
 
-namespace {
+enum WgRoute { WG_WS = 0, WG_FOLD = 1, WG_F16 = 2, WG_FP32 = 3, WG_COLS = 4 };
+// one kernel's tile grid (the column kernel: ntiles = rows), workgroup columns, split and partials region in the workspace
+struct WgLaunch { int nbz, nby, nbx, ntiles, cols; WgSplit s; size_t off, bytes; };
+// a: all channels, or a folded join's skip channels (wave-specialised kernel if skip_ws, else f16); u: its upsampled channels
+struct WgRoutePlan { WgRoute route; bool skip_ws; WgLaunch a, u; size_t total; };
+WgLaunch wgrad_tiles(int D, int H, int W, int tz, int ty, int tx, int cols, size_t split_bytes, size_t off) {
+    const int nbz = bfm_cdiv(D, tz), nby = bfm_cdiv(H, ty), nbx = bfm_cdiv(W, tx);
+    const WgSplit s = wgrad_split(nbz * nby * nbx, cols);
+    return {nbz, nby, nbx, nbz * nby * nbx, cols, s, off, s.S * split_bytes};
+}
+
+// The route of a layer and everything its launches need, from the layer alone (no HIP call).  (d, h, w): the low-res
+// extents of a join; ws_ok / fold_ok: conv_wgrad_ws_kernel / the folded form of an exact 2x join may be used.
+WgRoutePlan wgrad_route(int CA, int CB, int Cout, int D, int H, int W, int d, int h, int w, int passes, bool ws_ok,
+                        bool fold_ok) {
+    const int Cin = CA + CB;
+    const size_t chan = (size_t)Cout * 27 * sizeof(float);               // one input channel's partials of one split
+    const bool tiled = Cout % 64 == 0 && Cin % 32 == 0 && CA % 32 == 0, f16 = passes == 3 && tiled;
+    const auto ws_tiles = [&]() { return wgrad_tiles(D, H, W, 1, ST_Y, ST_X, (CA / 32) * (Cout / 32), chan * CA, 0); };
+    WgRoutePlan r{};
+    if (f16 && ws_ok && CB == 0) {
+        r.route = WG_WS; r.a = ws_tiles();
+    } else if (f16 && fold_ok && CB > 0 && CB % 32 == 0 && 2 * d == D && 2 * h == H && 2 * w == W && h >= UT_Y && w >= UT_X) {
+        r.route = WG_FOLD; r.skip_ws = ws_ok;
+        r.a = ws_ok ? ws_tiles() : wgrad_tiles(D, H, W, HT_Z, HT_Y, HT_X, (CA / 32) * (Cout / 64), chan * CA, 0);
+        // behind the skip channels' partials, 256-byte aligned (the wave-specialised kernel's: behind what its cap could take)
+        const size_t offU = ((ws_ok ? r.a.s.cap * chan * CA : r.a.bytes) + 255) & ~(size_t)255;
+        r.u = wgrad_tiles(d, h, w, 1, UT_Y, UT_X, (CB / 32) * (Cout / 32), (size_t)Cout * CB * 64 * sizeof(float), offU);
+    } else if (tiled) {
+        r.route = f16 ? WG_F16 : WG_FP32;
+        r.a = wgrad_tiles(D, H, W, f16 ? HT_Z : WT_Z, f16 ? HT_Y : WT_Y, f16 ? HT_X : WT_X, (Cin / 32) * (Cout / 64), chan * Cin, 0);
+    } else {
+        r.route = WG_COLS; r.a.ntiles = D * H; r.a.cols = bfm_cdiv(Cout, 32) * bfm_cdiv(Cin * 27, 32);
+        r.a.s = wgrad_row_split(r.a.ntiles, r.a.cols); r.a.bytes = r.a.s.S * chan * Cin;
+    }
+    r.total = r.route == WG_FOLD ? r.u.off + r.u.bytes : r.a.bytes;
+    return r;
+}
+
 // conv_wgrad_ws_kernel needs 130 KB of dynamic LDS and 768 threads: asked for once per process; where the device refuses
 // (a 64 KB-LDS part), the callers keep the 8-wave conv_wgrad_f16_kernel plan instead of failing the step
 bool wgrad_ws_available() {
-    static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ws_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, WGS_LDS) == hipSuccess;
-    return ok;
+    static bool raised = false;
+    return bfm_raise_lds_limit(raised, {bfm_kernel(&conv_wgrad_ws_kernel)}, WGS_LDS) == BFM_OK;
+}
+// what this process allows the route (bit 0 wave-specialised kernel, bit 1 fold): the environment and the device, asked once
+int wgrad_allow() {
+    static const auto on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
+    static const int allow = (on("BFM_WGRAD_UPFOLD") ? 2 : 0) | (on("BFM_WGRAD_WS") && wgrad_ws_available() ? 1 : 0);
+    return allow;
 }
 
-// skip / plain channels [0, CA) of a layer through conv_wgrad_ws_kernel + the fold of its partials into dW [Cout][Cin][27]
-int launch_wgrad_ws(const float* dP, int Cout, const float* A, int CA, int Cin, int D, int H, int W, const float* scale,
-                    const float* shift, const float* dp_bound, const float* x_bound, int G, float* part, float* dW,
-                    hipStream_t st) {
+// what the launchers take from bfm_conv3x3x3_wgrad_ex's arguments; p.part is the workspace
+struct WgCall { WgParams p; int Cin; const float *dp_bound, *x_bound; int G; float* dW; hipStream_t st; };
+float* wgrad_part(const WgCall& c, const WgLaunch& l) { return reinterpret_cast<float*>(reinterpret_cast<char*>(c.p.part) + l.off); }
+// partials [S][Cout][Cp][27] -> dW [Cout][Cin][27]: all channels, or the compact partials of the first Cp < Cin channels
+void wgrad_reduce(const WgCall& c, const WgLaunch& l, int Cp, bool compact) {
+    const int64_t n = (int64_t)c.p.Cout * Cp * 27;
+    if (compact)
+        hipLaunchKernelGGL(wgrad_reduce_cols_kernel, dim3(grid_for(n)), dim3(256), 0, c.st, wgrad_part(c, l), l.s.S, c.p.Cout,
+                           Cp, c.Cin, c.dW);
+    else
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(n)), dim3(256), 0, c.st, wgrad_part(c, l), l.s.S, n, c.dW);
+}
+// skip / plain channels [0, CA) through conv_wgrad_ws_kernel (its LDS limit: wgrad_ws_available) + the fold of its partials
+void launch_wgrad_ws(const WgCall& c, const WgLaunch& l) {
+    const WgParams& p = c.p;
     WgWsParams w{};
-    w.dP = dP; w.A = A; w.scale = scale; w.shift = shift; w.Cout = Cout; w.CA = CA; w.D = D; w.H = H; w.W = W;
-    w.part = part; w.part_cin = CA;
-    w.nby = bfm_cdiv(H, ST_Y); w.nbx = bfm_cdiv(W, ST_X); w.ntiles = D * w.nby * w.nbx;
-    w.dp_bound = dp_bound; w.x_bound = x_bound; w.G = G;
-    const int cols = (CA / 32) * (Cout / 32);
-    int S = 512 / cols;                                   // two rounds of one workgroup per CU (130 KB of LDS each)
-    if (S > w.ntiles) S = w.ntiles;
-    if (S < 1) S = 1;
-    const int per = bfm_cdiv(w.ntiles, S);
-    S = bfm_cdiv(w.ntiles, per);
-    hipLaunchKernelGGL(conv_wgrad_ws_kernel, dim3(S, CA / 32, Cout / 32), dim3(WGS_THREADS), WGS_LDS, st, w);
-    hipLaunchKernelGGL(wgrad_reduce_cols_kernel, dim3(grid_for((int64_t)Cout * CA * 27)), dim3(256), 0, st, part, S, Cout, CA,
-                       Cin, dW);
+    w.dP = p.dP; w.A = p.A; w.scale = p.scale; w.shift = p.shift; w.Cout = p.Cout; w.CA = p.CA; w.D = p.D; w.H = p.H; w.W = p.W;
+    w.part = wgrad_part(c, l); w.part_cin = p.CA; w.nby = l.nby; w.nbx = l.nbx; w.ntiles = l.ntiles;
+    w.dp_bound = c.dp_bound; w.x_bound = c.x_bound; w.G = c.G;
+    hipLaunchKernelGGL(conv_wgrad_ws_kernel, dim3(l.s.S, p.CA / 32, p.Cout / 32), dim3(WGS_THREADS), WGS_LDS, c.st, w);
+    wgrad_reduce(c, l, p.CA, true);
+}
+// channels [0, Cp) through conv_wgrad_f16_kernel: Cp = Cin, or CA when the upsampled channels of a join run folded
+int launch_wgrad_f16(const WgCall& c, const WgLaunch& l, int Cp) {
+    static bool attr = false;
+    if (const int rc = bfm_raise_lds_limit(attr, {bfm_kernel(&conv_wgrad_f16_kernel)}, WG3_LDS)) return rc;
+    Wg3Params q{};
+    q.b = c.p; q.b.S = l.s.S; q.nbz = l.nbz; q.nby = l.nby; q.nbx = l.nbx; q.ntiles = l.ntiles;
+    q.dp_bound = c.dp_bound; q.x_bound = c.x_bound; q.G = c.G; q.part_cin = Cp;
+    hipLaunchKernelGGL(conv_wgrad_f16_kernel, dim3(l.s.S, Cp / 32, c.p.Cout / 64), dim3(WG3_THREADS), WG3_LDS, c.st, q);
+    wgrad_reduce(c, l, Cp, Cp < c.Cin);
     return BFM_OK;
 }
-size_t wgrad_ws_part_bytes(int Cout, int CA, int D, int H, int W) {
-    const int ntiles = D * bfm_cdiv(H, ST_Y) * bfm_cdiv(W, ST_X);
-    const int cols = (CA / 32) * (Cout / 32);
-    int S = cols > 0 ? 512 / cols : 1;
-    if (S > ntiles) S = ntiles;
-    if (S < 1) S = 1;
-    return (((size_t)S * Cout * CA * 27 * sizeof(float)) + 255) & ~(size_t)255;
+// the upsampled channels of an exact 2x join on the low-res tensor (conv_wgrad_up_f16_kernel) + the fold into dW[.][CA ..]
+int launch_wgrad_up(const WgCall& c, const WgLaunch& l, const float* B) {
+    static bool attr = false;
+    if (const int rc = bfm_raise_lds_limit(attr, {bfm_kernel(&conv_wgrad_up_f16_kernel)}, WGU_LDS)) return rc;
+    const WgParams& p = c.p;
+    WgUpParams u{};
+    u.dP = p.dP; u.L = B; u.scale = p.scale + p.CA; u.shift = p.shift + p.CA; u.Cout = p.Cout; u.CB = p.CB;
+    u.d = p.up.d; u.h = p.up.h; u.w = p.up.w; u.nby = l.nby; u.nbx = l.nbx; u.ntiles = l.ntiles;
+    u.dp_bound = c.dp_bound; u.x_bound = c.x_bound; u.G = c.G; u.part = wgrad_part(c, l);
+    hipLaunchKernelGGL(conv_wgrad_up_f16_kernel, dim3(l.s.S, p.CB / 32, p.Cout / 32), dim3(WGU_THREADS), WGU_LDS, c.st, u);
+    hipLaunchKernelGGL(wgrad_up_fold_kernel, dim3((unsigned)std::min<int64_t>(8192, (int64_t)p.Cout * p.CB / 16)), dim3(256), 0,
+                       c.st, u.part, l.s.S, p.Cout, p.CB, c.Cin, p.CA, c.dW);
+    return BFM_OK;
+}
+int launch_wgrad_tiled(const WgCall& c, const WgLaunch& l) {               // exact fp32: conv_wgrad_tiled_kernel
+    static bool attr = false;
+    if (const int rc = bfm_raise_lds_limit(attr, {bfm_kernel(&conv_wgrad_tiled_kernel)}, WG2_LDS)) return rc;
+    Wg2Params q{};
+    q.b = c.p; q.b.S = l.s.S; q.nbz = l.nbz; q.nby = l.nby; q.nbx = l.nbx; q.ntiles = l.ntiles;
+    hipLaunchKernelGGL(conv_wgrad_tiled_kernel, dim3(l.s.S, c.Cin / 32, c.p.Cout / 64), dim3(WG2_THREADS), WG2_LDS, c.st, q);
+    wgrad_reduce(c, l, c.Cin, false);
+    return BFM_OK;
+}
+void launch_wgrad_cols(const WgCall& c, const WgLaunch& l) {                // exact fp32, any widths: conv_wgrad_cols_kernel
+    WgParams p = c.p; p.S = l.s.S; p.rows_per_split = l.s.per;
+    hipLaunchKernelGGL(conv_wgrad_cols_kernel, dim3(l.s.S, bfm_cdiv(p.Cout, 32), bfm_cdiv(c.Cin * 27, 32)), dim3(64), 0, c.st, p);
+    wgrad_reduce(c, l, c.Cin, false);
 }
 }  // namespace
 
+// An upper bound over the routes of wgrad_route, however Cin divides into skip and upsampled channels (a layer's exact need:
+// bfm_conv3x3x3_wgrad_plan).  tests/test_host_wgrad_plan.py holds every plan's total under it, and it to recorded values.
 extern "C" size_t bfm_conv3x3x3_wgrad_workspace(int Cin, int Cout, int D, int H, int W) {
     if (Cin <= 0 || Cout <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    // the split count does not depend on CA (only the kernel choice does): take the larger of the two plans
-    const WgPlan a = wgrad_plan(Cin, Cin, Cout, D, H, W), b = wgrad_plan(1, Cin, Cout, D, H, W),
-                 c = wgrad_plan(Cin, Cin, Cout, D, H, W, true);
-    int S = a.S > b.S ? a.S : b.S;
-    if (c.S > S) S = c.S;
-    // + the folded partials of the upsampled channels (conv_wgrad_up_f16_kernel): S_U x Cout x CB x 64 floats with
-    //   S_U x CB <= max(CB, 512 x 32 x 32 / Cout), CB < Cin
-    const size_t up = (size_t)256 * std::max<size_t>((size_t)Cout * Cin, (size_t)512 * 1024);
-    // (the skip channels alone split finer: S_A x CA <= 512 x 32 x 64 / Cout)
-    const size_t reg = std::max((size_t)S * Cout * Cin * 27 * sizeof(float), (size_t)512 * 32 * 64 * 27 * sizeof(float));
+    // all channels in one launch: the split does not depend on CA, so the widest of the column, fp32 and f16 splits ...
+    int S = wgrad_row_split(D * H, bfm_cdiv(Cout, 32) * bfm_cdiv(Cin * 27, 32)).S;
+    if (Cout % 64 == 0 && Cin % 32 == 0) {
+        S = std::max(S, wgrad_tiles(D, H, W, WT_Z, WT_Y, WT_X, (Cin / 32) * (Cout / 64), 0, 0).s.S);
+        S = std::max(S, wgrad_tiles(D, H, W, HT_Z, HT_Y, HT_X, (Cin / 32) * (Cout / 64), 0, 0).s.S);
+    }
+    // ... or the skip channels alone, which split finer: at most the budget x one column of the widest split (32 ci x 64 co)
+    const size_t reg = std::max((size_t)S * Cout * Cin * 27 * sizeof(float), (size_t)WG_BUDGET * 32 * 64 * 27 * sizeof(float));
+    // + a folded join's upsampled channels, [S_U][Cout][CB < Cin][64] floats: one split, or the budget x one 32 x 32 column
+    const size_t up = 64 * sizeof(float) * std::max((size_t)Cout * Cin, (size_t)WG_BUDGET * 32 * 32);
     return reg + 256 + up;
+}
+
+extern "C" int bfm_conv3x3x3_wgrad_plan(int CA, int CB, int Cout, int D, int H, int W, int d, int h, int w, int passes,
+                                        int allow, int64_t* plan, size_t* exact_bytes) {
+    if (!plan || CA <= 0 || CB < 0 || Cout <= 0 || D <= 0 || H <= 0 || W <= 0 || (passes != 0 && passes != 3)) return BFM_E_ARG;
+    if (allow < 0) allow = wgrad_allow();
+    const WgRoutePlan r = wgrad_route(CA, CB, Cout, D, H, W, d, h, w, passes, allow & 1, allow & 2);
+    *plan++ = r.route; *plan++ = r.skip_ws;
+    for (const WgLaunch* l : {&r.a, &r.u})
+        for (const int64_t v : std::initializer_list<int64_t>{l->nbz, l->nby, l->nbx, l->ntiles, l->cols, l->s.S, l->s.per,
+                                                              (int64_t)l->off, (int64_t)l->bytes})
+            *plan++ = v;
+    if (exact_bytes) *exact_bytes = r.total;
+    return BFM_OK;
 }
 
 extern "C" int bfm_conv3x3x3_wgrad_ex(const float* dP, int Cout, const float* A, int CA, const float* B, int CB, int D,
@@ -1459,105 +1537,27 @@ extern "C" int bfm_conv3x3x3_wgrad_ex(const float* dP, int Cout, const float* A,
     if (!dP || !A || !scale || !shift || !dW || !workspace || Cout <= 0 || CA <= 0 || D <= 0 || H <= 0 || W <= 0)
         return BFM_E_ARG;
     if (CB < 0 || (CB > 0 && (!B || !up || !up->mapD || !up->mapH || !up->mapW))) return BFM_E_ARG;
-    const int Cin = CA + CB;
-    if (workspace_bytes < bfm_conv3x3x3_wgrad_workspace(Cin, Cout, D, H, W)) return BFM_E_WORKSPACE;
-    WgParams p{};
-    p.dP = dP; p.Cout = Cout; p.A = A; p.B = B; p.CA = CA; p.CB = CB; p.up = make_upview(up);
-    p.scale = scale; p.shift = shift; p.D = D; p.H = H; p.W = W;
-    p.part = static_cast<float*>(workspace);
-    hipStream_t st = bfm_s(stream);
-    const int64_t n = (int64_t)Cout * Cin * 27;
-    const bool f16 = passes == 3 && Cout % 64 == 0 && Cin % 32 == 0 && CA % 32 == 0;
-    // upsampled channels of an exact 2x decoder join: folded form on the low-res tensor, the skip channels alone below
-    static const bool upfold_on = []() { const char* e = getenv("BFM_WGRAD_UPFOLD"); return !(e && e[0] == '0'); }();
-    static const bool ws_on = []() { const char* e = getenv("BFM_WGRAD_WS"); return !(e && e[0] == '0'); }() && wgrad_ws_available();
-    if (f16 && ws_on && CB == 0) {                         // plain layer: the wave-specialised kernel on all channels
-        if (wgrad_ws_part_bytes(Cout, CA, D, H, W) > workspace_bytes) return BFM_E_WORKSPACE;
-        const int rc = launch_wgrad_ws(dP, Cout, A, CA, Cin, D, H, W, scale, shift, dp_bound, x_bound, G, p.part, dW, st);
-        return rc != BFM_OK ? rc : bfm_launch_status();
+    if (workspace_bytes < bfm_conv3x3x3_wgrad_workspace(CA + CB, Cout, D, H, W)) return BFM_E_WORKSPACE;
+    WgCall c{};
+    c.p.dP = dP; c.p.Cout = Cout; c.p.A = A; c.p.B = B; c.p.CA = CA; c.p.CB = CB; c.p.up = make_upview(up);
+    c.p.scale = scale; c.p.shift = shift; c.p.D = D; c.p.H = H; c.p.W = W; c.p.part = static_cast<float*>(workspace);
+    c.Cin = CA + CB; c.dp_bound = dp_bound; c.x_bound = x_bound; c.G = G; c.dW = dW; c.st = bfm_s(stream);
+    const int allow = wgrad_allow();                       // the low-res extents are read for a join (CB > 0) only
+    const WgRoutePlan r = wgrad_route(CA, CB, Cout, D, H, W, c.p.up.d, c.p.up.h, c.p.up.w, passes, allow & 1, allow & 2);
+    if (r.total > workspace_bytes) return BFM_E_WORKSPACE;
+    int rc = BFM_OK;
+    switch (r.route) {
+        case WG_WS: launch_wgrad_ws(c, r.a); break;
+        case WG_FOLD:
+            if (r.skip_ws) launch_wgrad_ws(c, r.a);
+            else rc = launch_wgrad_f16(c, r.a, CA);
+            if (rc == BFM_OK) rc = launch_wgrad_up(c, r.u, B);
+            break;
+        case WG_F16: rc = launch_wgrad_f16(c, r.a, c.Cin); break;
+        case WG_FP32: rc = launch_wgrad_tiled(c, r.a); break;
+        case WG_COLS: launch_wgrad_cols(c, r.a); break;
     }
-    if (f16 && upfold_on && CB > 0 && CB % 32 == 0 && 2 * up->d == D && 2 * up->h == H && 2 * up->w == W &&
-        up->h >= UT_Y && up->w >= UT_X) {
-        hipStream_t st2 = st;
-        // (1) skip channels alone, compact partials
-        static bool attr3a = false, attrU = false;
-        size_t offA;
-        if (ws_on) {
-            const int rc = launch_wgrad_ws(dP, Cout, A, CA, Cin, D, H, W, scale, shift, dp_bound, x_bound, G, p.part, dW, st2);
-            if (rc != BFM_OK) return rc;
-            offA = wgrad_ws_part_bytes(Cout, CA, D, H, W);
-        } else {
-            const WgPlan pa = wgrad_plan(CA, CA, Cout, D, H, W, true);
-            Wg3Params q{};
-            q.b = p; q.b.S = pa.S; q.nbz = pa.nbz; q.nby = pa.nby; q.nbx = pa.nbx; q.ntiles = pa.ntiles;
-            q.dp_bound = dp_bound; q.x_bound = x_bound; q.G = G; q.part_cin = CA;
-            if (!attr3a) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_f16_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, WG3_LDS) != hipSuccess)
-                    return BFM_E_LAUNCH;
-                attr3a = true;
-            }
-            hipLaunchKernelGGL(conv_wgrad_f16_kernel, dim3(pa.S, CA / 32, Cout / 64), dim3(WG3_THREADS), WG3_LDS, st2, q);
-            hipLaunchKernelGGL(wgrad_reduce_cols_kernel, dim3(grid_for((int64_t)Cout * CA * 27)), dim3(256), 0, st2, p.part, pa.S,
-                               Cout, CA, Cin, dW);
-            offA = (((size_t)pa.S * Cout * CA * 27 * sizeof(float)) + 255) & ~(size_t)255;
-        }
-        // (2) upsampled channels
-        WgUpParams u{};
-        u.dP = dP; u.L = B; u.scale = scale + CA; u.shift = shift + CA; u.Cout = Cout; u.CB = CB;
-        u.d = up->d; u.h = up->h; u.w = up->w;
-        u.nby = bfm_cdiv(up->h, UT_Y); u.nbx = bfm_cdiv(up->w, UT_X); u.ntiles = up->d * u.nby * u.nbx;
-        u.dp_bound = dp_bound; u.x_bound = x_bound; u.G = G;
-        const int colsU = (CB / 32) * (Cout / 32);
-        int SU = 512 / colsU;
-        if (SU > u.ntiles) SU = u.ntiles;
-        if (SU < 1) SU = 1;
-        const int per = bfm_cdiv(u.ntiles, SU);
-        SU = bfm_cdiv(u.ntiles, per);
-        if (offA + (size_t)SU * Cout * CB * 64 * sizeof(float) > workspace_bytes) return BFM_E_WORKSPACE;
-        u.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + offA);
-        if (!attrU) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_up_f16_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, WGU_LDS) != hipSuccess)
-                return BFM_E_LAUNCH;
-            attrU = true;
-        }
-        hipLaunchKernelGGL(conv_wgrad_up_f16_kernel, dim3(SU, CB / 32, Cout / 32), dim3(WGU_THREADS), WGU_LDS, st2, u);
-        hipLaunchKernelGGL(wgrad_up_fold_kernel, dim3((unsigned)std::min<int64_t>(8192, (int64_t)Cout * CB / 16)), dim3(256), 0,
-                           st2, u.part, SU, Cout, CB, Cin, CA, dW);
-        return bfm_launch_status();
-    }
-    const WgPlan pl = wgrad_plan(CA, Cin, Cout, D, H, W, f16);
-    p.S = pl.S;
-    if (f16) {
-        Wg3Params q{};
-        q.b = p; q.nbz = pl.nbz; q.nby = pl.nby; q.nbx = pl.nbx; q.ntiles = pl.ntiles;
-        q.dp_bound = dp_bound; q.x_bound = x_bound; q.G = G; q.part_cin = Cin;
-        static bool attr3 = false;
-        if (!attr3) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_f16_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, WG3_LDS) != hipSuccess)
-                return BFM_E_LAUNCH;
-            attr3 = true;
-        }
-        hipLaunchKernelGGL(conv_wgrad_f16_kernel, dim3(pl.S, Cin / 32, Cout / 64), dim3(WG3_THREADS), WG3_LDS, st, q);
-    } else if (pl.kind == 0) {
-        Wg2Params q{};
-        q.b = p; q.nbz = pl.nbz; q.nby = pl.nby; q.nbx = pl.nbx; q.ntiles = pl.ntiles;
-        static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_tiled_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, WG2_LDS) != hipSuccess)
-                return BFM_E_LAUNCH;
-            attr = true;
-        }
-        hipLaunchKernelGGL(conv_wgrad_tiled_kernel, dim3(pl.S, Cin / 32, Cout / 64), dim3(WG2_THREADS), WG2_LDS, st, q);
-    } else {
-        p.rows_per_split = pl.rows_per_split;
-        hipLaunchKernelGGL(conv_wgrad_cols_kernel, dim3(pl.S, bfm_cdiv(Cout, 32), bfm_cdiv(Cin * 27, 32)), dim3(64), 0, st, p);
-    }
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(n)), dim3(256), 0, st, p.part, p.S, n, dW);
-    return bfm_launch_status();
+    return rc != BFM_OK ? rc : bfm_launch_status();
 }
 
 extern "C" int bfm_conv3x3x3_wgrad(const float* dP, int Cout, const float* A, int CA, const float* B, int CB, int D,

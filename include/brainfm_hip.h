@@ -936,7 +936,28 @@ int bfm_lrelu_bwd(const float* dY, const float* Y, int64_t n, float slope, float
 /* the same, also writing max |dP| (device float; the split-fp16 weight / data gradient kernels scale dP by it) */
 int bfm_lrelu_bwd_ex(const float* dY, const float* Y, int64_t n, float slope, float* dP, float* absmax,
                      bfm_stream_t stream);
+/* Workspace bytes of bfm_conv3x3x3_wgrad / _ex for a layer of Cin = CA + CB input channels: an upper bound over the routes
+ * below and over every way to divide Cin into skip and upsampled channels.  bfm_conv3x3x3_wgrad_plan gives the exact need
+ * of one layer; _ex still asks for this bound (BFM_E_WORKSPACE below it). */
 size_t bfm_conv3x3x3_wgrad_workspace(int Cin, int Cout, int D, int H, int W);
+/* The route bfm_conv3x3x3_wgrad_ex takes for a layer (CA skip / plain channels, CB channels upsampled from (d, h, w); d, h, w
+ * are not read when CB == 0), from the layer alone: no device call.  allow: bit 0 the wave-specialised kernel may be used,
+ * bit 1 an exact 2x join may run folded; negative: what _ex uses in this process (BFM_WGRAD_WS, BFM_WGRAD_UPFOLD and the
+ * device's LDS limit, asked once).  plan_out [20]:
+ *   [0] route  0 wave-specialised kernel on a plain layer (passes 3, Cout % 64, CA % 32 == 0, CB == 0, bit 0)
+ *              1 folded join (passes 3, bit 1, CB % 32 == 0, (D, H, W) == 2 (d, h, w), h >= 4, w >= 16): launch 0 runs the skip
+ *                channels, launch 1 the upsampled channels on the low-res tensor
+ *              2 f16 tiles on all channels (passes 3, Cout % 64, Cin % 32, CA % 32 == 0)
+ *              3 fp32 tiles (the same widths at passes 0)          4 fp32 columns (every other width)
+ *   [1]        route 1: 1 when the skip channels run on the wave-specialised kernel (bit 0), 0 on f16 tiles
+ *   [2..10]    launch 0: tile grid nbz, nby, nbx, tiles (route 4: the D x H rows), workgroup columns, S, per, then byte offset
+ *              and size of its partials in the workspace.  The launch runs S x columns workgroups; each takes `per`
+ *              tiles, the last maybe fewer, none is empty.  One rule for every tiled kernel: S = ceil(tiles / per) with
+ *              per = ceil(tiles / min(tiles, max(1, 512 / columns))); route 4 splits rows under ceil(2048 / columns).
+ *   [11..19]   launch 1 of route 1, the same nine; zeros on the other routes
+ * *exact_bytes_out (may be NULL): the end of the last region, <= bfm_conv3x3x3_wgrad_workspace(CA + CB, Cout, D, H, W). */
+int bfm_conv3x3x3_wgrad_plan(int CA, int CB, int Cout, int D, int H, int W, int d, int h, int w, int passes, int allow,
+                             int64_t* plan_out /*[20]*/, size_t* exact_bytes_out);
 /* The whole backward of the first SingleConv of a conditioned network (GroupNorm(1, Cin) + Conv3d(Cin, Cout, 3) on the
  * network's input; torch autograd over buildingblocks.py:31-60 for the model of Trainer/models/__init__.py:423-437) as ONE
  * correlation on the exact-fp32 matrix core.  The input is data, so no input gradient is formed: over the raw input x,

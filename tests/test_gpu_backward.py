@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import backward_refs as R
+from wgrad_cases import COLS, FOLD_JOIN, FOLD_JOINS, JOINS, PLAIN, WGRAD_TOL, _Wg
 
 pytestmark = pytest.mark.gpu
 
@@ -228,79 +229,7 @@ def test_gn_bwd_error_paths_launch_nothing():
 
 
 # ----------------------------------------------------------------------------------------------- 5. weight gradient
-WGRAD_TOL = 2e-5                        # the bound of test_weight_gradient_of_a_decoder_join_vs_float64 (split-fp16 class)
-
-PLAIN = [                               # Cin, Cout, dims, G
-    (64, 64, (5, 7, 19), 8),            # H % 4 != 0, odd W past one tile
-    (32, 128, (3, 4, 16), 4),           # exact tile
-    (96, 192, (2, 5, 9), 8),            # W below a tile
-    (256, 256, (4, 4, 4), 8),           # deep-level extents
-    (128, 64, (2, 2, 2), 8),
-    (64, 64, (1, 2, 3), 8),
-    (1024, 1024, (2, 2, 2), 8),         # 512 / cols == 0: clamped to one split
-    (48, 64, (3, 4, 5), 8),             # CA % 32 != 0: the fp32 column kernel
-]
-JOINS = [                               # CA, CB, Cout, dims, low-res dims, G: joins that cannot fold
-    (32, 64, 64, (7, 9, 18), (3, 4, 9), 8),          # non-2x
-    (512, 1024, 512, (4, 4, 4), (2, 2, 2), 8),       # low-res smaller than the tile
-]
-COLS = [                                # the column kernel: stem, narrow net, narrow join
-    (1, 0, 32, (5, 6, 7), None, 1),
-    (8, 0, 16, (4, 5, 6), None, 2),
-    (8, 8, 16, (5, 7, 9), (2, 3, 4), 2),
-]
-FOLD_JOIN = (32, 64, 64, (8, 16, 32), (4, 8, 16), 8)   # the foldable join of test_weight_gradient_of_a_decoder_join_vs_float64
-
-
-class _Wg:
-    """Inputs of one weight-gradient case on the device: A, B, scale (in [0.5, 1.5) times a per-group factor from
-    {0.1, 1, 10}), shift, the float64 GroupNorm-applied input X and its true per-group max |X|, a unit-variance dP."""
-
-    def __init__(self, ca, cb, cout, dims, lo, G, seed=0):
-        dev = _dev()
-        self.ca, self.cb, self.cout, self.dims, self.lo, self.G = ca, cb, cout, dims, lo, G
-        cin = self.cin = ca + cb
-        g = torch.Generator().manual_seed(seed + ca + 3 * cb + 7 * cout + sum(dims))
-        self.A = torch.randn(dims + (ca,), generator=g).to(dev)
-        self.B = torch.randn(lo + (cb,), generator=g).to(dev) if cb else None
-        fac = torch.tensor([0.1, 1.0, 10.0])[torch.randint(0, 3, (G,), generator=g)]
-        if G >= 3:
-            fac[:3] = torch.tensor([10.0, 0.1, 1.0])                           # all three factors occur
-        self.scale = ((torch.rand(cin, generator=g) + 0.5) * fac.repeat_interleave(cin // G)).to(dev)
-        self.shift = (torch.randn(cin, generator=g) * 0.1).to(dev)
-        self.dP = torch.randn(dims + (cout,), generator=g).to(dev)
-        self.up = None
-        if cb:
-            self.up, _ = _Tables.get(lo, dims)
-        maps = R.up_maps(lo, dims, dev) if cb else None
-        self.X = R.join(self.A, self.B, maps).double() * self.scale.double() + self.shift.double()
-        self.xb = self.X.abs().reshape(-1, G, cin // G).amax(dim=(0, 2)).float().contiguous()
-
-    def run(self, dP, passes=3, dp_bound=None, ex=True):
-        L, lib = _lib()
-        D, H, W = self.dims
-        dev = dP.device
-        if dp_bound is None:
-            dp_bound = dP.abs().max().reshape(1)
-        nws = lib.bfm_conv3x3x3_wgrad_workspace(self.cin, self.cout, D, H, W)
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        dW = torch.full((self.cout, self.cin, 27), NAN, dtype=torch.float32, device=dev)
-        upp = C.byref(self.up) if self.cb else None
-        if ex:
-            rc = lib.bfm_conv3x3x3_wgrad_ex(L.ptr(dP), self.cout, L.ptr(self.A), self.ca, L.ptr(self.B), self.cb, D, H, W, upp,
-                                            L.ptr(self.scale), L.ptr(self.shift), L.ptr(dp_bound), L.ptr(self.xb), self.G,
-                                            passes, L.ptr(dW), L.ptr(ws), nws, L.stream_ptr())
-        else:
-            rc = lib.bfm_conv3x3x3_wgrad(L.ptr(dP), self.cout, L.ptr(self.A), self.ca, L.ptr(self.B), self.cb, D, H, W, upp,
-                                         L.ptr(self.scale), L.ptr(self.shift), L.ptr(dW), L.ptr(ws), nws, L.stream_ptr())
-        L.check(rc, "wgrad")
-        return dW
-
-    def err(self, dW, dP):
-        assert bool(torch.isfinite(dW).all())
-        return R.rel_err(dW, R.wgrad_ref(self.X, dP))
-
-
+# the cases, their inputs (_Wg) and the bound are shared with the route and bits tests: tests/wgrad_cases.py
 def _ids(cases):
     return ["-".join(str(v).replace(" ", "") for v in c) for c in cases]
 
@@ -309,7 +238,9 @@ def _ids(cases):
 def test_wgrad_plain_layers_vs_float64(cin, cout, dims, G):
     """bfm_conv3x3x3_wgrad_ex, passes = 3, on plain layers: conv_wgrad_ws_kernel with extents that are no multiple of, equal
     to and below its 4 x 16 tile, the deep-level 4^3 / 2^3 / (1, 2, 3) volumes, 1024 x 1024 channels (more workgroup columns
-    than the split budget), and 48 input channels on the fp32 column kernel; eight groups whose bounds differ 100-fold."""
+    than the split budget), 48 input channels on the fp32 column kernel, and 256 x 256 channels at (6, 9, 33), where every
+    workgroup takes seven tiles and the last one five; eight groups whose bounds differ 100-fold.  The routes named here and
+    below are asserted by tests/test_host_wgrad_plan.py and tests/test_gpu_wgrad_bits.py."""
     w = _Wg(cin, 0, cout, dims, None, G)
     e = w.err(w.run(w.dP), w.dP)
     print("wgrad plain %s: %.2e" % ((cin, cout, dims, G), e))
@@ -323,6 +254,18 @@ def test_wgrad_unfolded_joins_and_column_kernel_vs_float64(ca, cb, cout, dims, l
     w = _Wg(ca, cb, cout, dims, lo, G)
     e = w.err(w.run(w.dP), w.dP)
     print("wgrad %s: %.2e" % ((ca, cb, cout, dims, lo, G), e))
+    assert e <= WGRAD_TOL, e
+
+
+@pytest.mark.parametrize("ca,cb,cout,dims,lo,G", FOLD_JOINS, ids=_ids(FOLD_JOINS))
+def test_wgrad_folded_joins_vs_float64(ca, cb, cout, dims, lo, G):
+    """Exact-2x decoder joins on the folded route (skip channels on conv_wgrad_ws_kernel, upsampled channels on
+    conv_wgrad_up_f16_kernel): one workgroup per tile, and 256 + 256 -> 256 channels where the workgroups of both halves
+    take several tiles each (12 and 2) and the upsampled half runs 6 workgroups where the budget allows 8.
+    tests/test_host_wgrad_plan.py holds the routes to what is said here."""
+    w = _Wg(ca, cb, cout, dims, lo, G)
+    e = w.err(w.run(w.dP), w.dP)
+    print("wgrad folded %s: %.2e" % ((ca, cb, cout, dims, lo, G), e))
     assert e <= WGRAD_TOL, e
 
 
