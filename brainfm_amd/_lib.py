@@ -68,6 +68,16 @@ class OdeFixedAdvect(C.Structure):
                 ("method", C.c_int), ("nt", C.c_int), ("coef", C.POINTER(C.c_float))]
 
 
+PDE_ADV, PDE_DIFF = 1, 2                             # BFM_PDE_* of include/brainfm_hip.h
+PDE_D_CONSTANT, PDE_D_SCALAR, PDE_D_DIAG, PDE_D_FULL = 1, 2, 3, 4
+
+
+class PdeTerms(C.Structure):
+    """bfm_pde_terms_t: D / G / divV are device pointers to fp32 fields."""
+    _fields_ = [("perf", C.c_int), ("d_type", C.c_int), ("v_general", C.c_int), ("D_const", C.c_float),
+                ("D", C.c_void_p * 6), ("G", C.c_void_p * 3), ("divV", C.c_void_p)]
+
+
 class AgeParams(C.Structure):
     """bfm_age_params_t: device pointers of the age head's parameters (torch layouts)."""
     _fields_ = [(n, C.c_void_p) for n in ("c1w", "c1b", "c2w", "c2b", "l1w", "l1b", "l2w", "l2b", "l3w", "l3b")]
@@ -285,6 +295,11 @@ SIGNATURES = {
     "bfm_dopri5_advect_steps": (_I, [C.POINTER(Dopri5Advect), _I, _P]),
     "bfm_ode_fixed_ncoef": (_I, [_I]),
     "bfm_ode_fixed_advect": (_I, [C.POINTER(OdeFixedAdvect), _P]),
+    "bfm_pde_central_sum": (_I, [C.POINTER(_P), C.POINTER(_I), _I, _I, _I, _I, _P, _P]),
+    "bfm_advdiff_rhs": (_I, [_P, _I, _P, _P, _P, C.POINTER(PdeTerms), _I, _I, _I, _I, _P, _I, _P]),
+    "bfm_dopri5_advdiff_init": (_I, [C.POINTER(Dopri5Advect), C.POINTER(PdeTerms), C.c_double, C.c_double, _P]),
+    "bfm_dopri5_advdiff_steps": (_I, [C.POINTER(Dopri5Advect), C.POINTER(PdeTerms), _I, _P]),
+    "bfm_ode_fixed_advdiff": (_I, [C.POINTER(OdeFixedAdvect), C.POINTER(PdeTerms), _P]),
     "bfm_randn_philox": (_I, [_P, _L, C.c_uint64, C.c_uint64, _F, _P]),
     "bfm_svf_integrate_workspace": (_Z, [_I, _I, _I]),
     "bfm_svf_integrate": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),

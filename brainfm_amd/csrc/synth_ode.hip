@@ -9,7 +9,11 @@
 //     times are computed by kernels that read and update a small state block in device memory;
 //   * the host enqueues steps in chunks and reads back one flag per chunk; kernels of steps past the end exit at once.
 // The state keeps y0's dtype (fp64 for Perlin shapes, fp32 for file maps) with fp32 stages, like the reference.
+// The right-hand side of a stage is box_rhs<T, CFG> below: the generator's upwind advection (CFG_ADV), or the diffusion
+// terms and the general velocity of pde.py:362-441, :511-524, chosen at compile time.
 #include "bfm_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -24,11 +28,17 @@ struct OdeState {
     int cur, done, next_out, nsteps, naccept, accepted, err, pad;
 };
 
+// The fields of the diffusion term and of the general-velocity term (pde.py:362-441, :511-524).  D: {D} for a scalar field,
+// {Dxx, Dyy, Dzz, Dxy, Dyz, Dxz} for a tensor; G: the time-invariant central differences of D that multiply c_x C, c_y C,
+// c_z C (pde_central_sum below); divV = c_x Vx + c_y Vy + c_z Vz.
+struct PdeTerms { const float* D[6]; const float* G[3]; const float* divV; float Dc; };
+
 struct OdeArgs {
     void* y[2]; float* f[2]; float* k[5];
     const float *Vx, *Vy, *Vz;
     int sx, sy, sz, neumann;
     OdeState* st;
+    PdeTerms P;
 };
 
 __constant__ double BETA[6][6] = {
@@ -58,7 +68,124 @@ __device__ __forceinline__ float coef(double dt, double c) { return (float)((T)d
 constexpr int TX = 8, TY = 8, TZ = 32;
 constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2;
 
-template <typename T, int STAGE>
+// ---- the right-hand side of one voxel from the boundary-conditioned state of its box in LDS -------------------------
+// CFG = VK + 4 * DK selects the terms at compile time: VK 0 no advection, 1 upwind advection by a divergence-free V
+// (Grad_div_free_vectorV), 2 by a general V (Grad_vectorV: minus C div V);  DK 0 no diffusion, 1 constant, 2 scalar,
+// 3 diagonal, 4 full tensor (Grad_constantD .. Grad_fullD).  CFG_ADV is the configuration of the generator and takes
+// none of the other code.  With f / b / c the forward / backward / central differences of pde.py:13-190 (one-sided at
+// the ends, every difference taken in the state dtype and rounded to fp32 as gradient_* stores it), a term reads the
+// 3 x 3 x 3 neighbourhood of its voxel, except b_a(f_a C) at index 0 of axis a, which is f_a[1] - f_a[0] and reads
+// index 2: inside the box of any volume with 3 voxels per axis.  At the last index b_a(f_a C) is f_a[n-1] - f_a[n-2]
+// with both equal to C[n-1] - C[n-2]: exactly 0.
+constexpr int V_NONE = 0, V_DIVFREE = 1, V_GENERAL = 2;
+constexpr int D_NONE = 0, D_CONSTANT = 1, D_SCALAR = 2, D_DIAG = 3, D_FULL = 4;
+constexpr int CFG_ADV = V_DIVFREE + 4 * D_NONE;
+
+// the reference's result dtype: C * div V promotes to the state dtype (pde.py:524); every other term is fp32
+template <typename T, int CFG>
+using rhs_t = std::conditional_t<(CFG & 3) == V_GENERAL, T, float>;
+
+template <typename T, int CFG>
+__device__ __forceinline__ rhs_t<T, CFG> box_rhs(const T* __restrict__ sU, int tx, int ty, int tz, int x, int yy, int z,
+                                                 int sx, int sy, int sz, int64_t i, const float* __restrict__ Vx,
+                                                 const float* __restrict__ Vy, const float* __restrict__ Vz,
+                                                 const PdeTerms& P) {
+    constexpr int VK = CFG & 3, DK = CFG >> 2;
+    auto U = [&](int dx, int dy, int dz) -> T { return sU[((tx + 1 + dx) * HY + (ty + 1 + dy)) * HZ + (tz + 1 + dz)]; };
+    const T u = U(0, 0, 0);
+    float kv = 0.f;
+    if constexpr (VK != V_NONE) {
+        float acc = 0.f;
+        bool first = true;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            const int pos = ax == 0 ? x : (ax == 1 ? yy : z);
+            const int len = ax == 0 ? sx : (ax == 1 ? sy : sz);
+            const int ex = ax == 0, ey = ax == 1, ez = ax == 2;
+            const int fw = pos < len - 1 ? 1 : 0, bw = pos > 0 ? 1 : 0;
+            const T up = U(ex * fw, ey * fw, ez * fw);
+            const T dn = U(-ex * bw, -ey * bw, -ez * bw);
+            const float df = pos < len - 1 ? (float)(up - u) : (float)(u - dn);
+            const float db = pos > 0 ? (float)(u - dn) : (float)(up - u);
+            const float V = ax == 0 ? Vx[i] : (ax == 1 ? Vy[i] : Vz[i]);
+            const float flag = V > 0.f ? 1.f : 0.f;
+            const float d = df * (1.f - flag) + db * flag;
+            const float term = V * d;
+            acc = first ? term : acc + term;
+            first = false;
+        }
+        kv = -acc;
+    }
+    if constexpr (CFG == CFG_ADV) {
+        return kv;
+    } else {
+        float kd = 0.f;
+        if constexpr (DK != D_NONE) {
+            const int pos[3] = {x, yy, z}, len[3] = {sx, sy, sz};
+            // b_a(f_a C)
+            auto dd = [&](int a) -> float {
+                const int e0 = a == 0, e1 = a == 1, e2 = a == 2;
+                if (pos[a] == len[a] - 1) return 0.f;
+                const float f1 = (float)(U(e0, e1, e2) - u);
+                if (pos[a] == 0) return (float)(U(2 * e0, 2 * e1, 2 * e2) - U(e0, e1, e2)) - f1;
+                return f1 - (float)(u - U(-e0, -e1, -e2));
+            };
+            // c_a C
+            auto dc = [&](int a) -> float {
+                const int e0 = a == 0, e1 = a == 1, e2 = a == 2;
+                if (pos[a] == 0) return (float)(U(e0, e1, e2) - u);
+                if (pos[a] == len[a] - 1) return (float)(u - U(-e0, -e1, -e2));
+                return (float)((U(e0, e1, e2) - U(-e0, -e1, -e2)) / (T)2);
+            };
+            // b_a(f_g C), a != g: f_g at the voxel and at its neighbour along a (an edge neighbour of the halo)
+            auto cr = [&](int a, int g) -> float {
+                const int a0 = a == 0, a1 = a == 1, a2 = a == 2, g0 = g == 0, g1 = g == 1, g2 = g == 2;
+                const bool fwd = pos[g] < len[g] - 1;
+                auto fg = [&](int s) -> float {
+                    const T c0 = U(s * a0, s * a1, s * a2);
+                    return fwd ? (float)(U(s * a0 + g0, s * a1 + g1, s * a2 + g2) - c0)
+                               : (float)(c0 - U(s * a0 - g0, s * a1 - g1, s * a2 - g2));
+                };
+                return pos[a] > 0 ? fg(0) - fg(-1) : fg(1) - fg(0);
+            };
+            if constexpr (DK == D_CONSTANT) {
+                kd = P.Dc * ((dd(0) + dd(1)) + dd(2));
+            } else if constexpr (DK == D_SCALAR) {
+                const float D = P.D[0][i];
+                kd = (P.G[0][i] * dc(0) + P.G[1][i] * dc(1)) + P.G[2][i] * dc(2);
+                kd = kd + D * dd(0);
+                kd = kd + D * dd(1);
+                kd = kd + D * dd(2);
+            } else if constexpr (DK == D_DIAG) {
+                kd = P.G[0][i] * dc(0) + P.D[0][i] * dd(0);
+                kd = kd + P.G[1][i] * dc(1);
+                kd = kd + P.D[1][i] * dd(1);
+                kd = kd + P.G[2][i] * dc(2);
+                kd = kd + P.D[2][i] * dd(2);
+            } else {
+                kd = P.G[0][i] * dc(0) + P.G[1][i] * dc(1);
+                kd = kd + P.G[2][i] * dc(2);
+                kd = kd + P.D[0][i] * dd(0);
+                kd = kd + P.D[1][i] * dd(1);
+                kd = kd + P.D[2][i] * dd(2);
+                kd = kd + P.D[3][i] * (cr(0, 1) + cr(1, 0));
+                kd = kd + P.D[4][i] * (cr(1, 2) + cr(2, 1));
+                kd = kd + P.D[5][i] * (cr(2, 0) + cr(0, 2));
+            }
+        }
+        if constexpr (VK == V_GENERAL) {
+            T r = (T)kv - u * (T)P.divV[i];
+            if constexpr (DK != D_NONE) r = r + (T)kd;
+            return r;
+        } else if constexpr (VK == V_DIVFREE) {
+            return kv + kd;
+        } else {
+            return kd;
+        }
+    }
+}
+
+template <typename T, int STAGE, int CFG>
 __global__ void __launch_bounds__(256) ode_stage(OdeArgs A, double atol, double rtol, double* __restrict__ part) {
     const OdeState* st = A.st;
     if (st->done) return;
@@ -118,28 +245,9 @@ __global__ void __launch_bounds__(256) ode_stage(OdeArgs A, double atol, double 
             const int x = x0 + tx;
             if (x >= sx) break;
             const int64_t i = x * stx + yy * sty + z;
-            auto U = [&](int dx, int dy, int dz) -> T { return sU[((tx + 1 + dx) * HY + (ty + 1 + dy)) * HZ + (tz + 1 + dz)]; };
-            const T u = U(0, 0, 0);
-            float acc = 0.f;
-            bool first = true;
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                const int pos = ax == 0 ? x : (ax == 1 ? yy : z);
-                const int len = ax == 0 ? sx : (ax == 1 ? sy : sz);
-                const int ex = ax == 0, ey = ax == 1, ez = ax == 2;
-                const int fw = pos < len - 1 ? 1 : 0, bw = pos > 0 ? 1 : 0;
-                const T up = U(ex * fw, ey * fw, ez * fw);
-                const T dn = U(-ex * bw, -ey * bw, -ez * bw);
-                const float df = pos < len - 1 ? (float)(up - u) : (float)(u - dn);
-                const float db = pos > 0 ? (float)(u - dn) : (float)(up - u);
-                const float V = ax == 0 ? A.Vx[i] : (ax == 1 ? A.Vy[i] : A.Vz[i]);
-                const float flag = V > 0.f ? 1.f : 0.f;
-                const float d = df * (1.f - flag) + db * flag;
-                const float term = V * d;
-                acc = first ? term : acc + term;
-                first = false;
-            }
-            const float kn = -acc;
+            const T u = sU[((tx + 1) * HY + (ty + 1)) * HZ + (tz + 1)];
+            const auto rk = box_rhs<T, CFG>(sU, tx, ty, tz, x, yy, z, sx, sy, sz, i, A.Vx, A.Vy, A.Vz, A.P);
+            const float kn = (float)rk;
             out[i] = kn;
             if (STAGE == 6) {
                 // y1 is the UNconditioned combination at i (rk_combine); the LDS value is boundary-conditioned, which
@@ -277,16 +385,63 @@ __global__ void ode_init(OdeState* st, double t0, double dt0) {
 }
 
 
-bool ode_ok(const bfm_dopri5_advect_t* d) {
-    if (!d || !d->y[0] || !d->y[1] || !d->f[0] || !d->f[1] || !d->Vx || !d->Vy || !d->Vz || !d->state || !d->workspace ||
-        !d->t_out || !d->sol || d->nt < 2)
+// CFG of a terms block (NULL: the generator's 'adv' with a divergence-free V), -1 if it names no built configuration or
+// lacks a field that configuration reads
+int pde_cfg(const bfm_pde_terms_t* t, const float* Vx, const float* Vy, const float* Vz) {
+    const bool hasV = Vx && Vy && Vz;
+    if (!t) return hasV ? CFG_ADV : -1;
+    const bool adv = t->perf & BFM_PDE_ADV, diff = t->perf & BFM_PDE_DIFF;
+    if ((!adv && !diff) || (t->perf & ~(BFM_PDE_ADV | BFM_PDE_DIFF))) return -1;
+    int vk = V_NONE, dk = D_NONE;
+    if (adv) {
+        if (!hasV || (t->v_general && !t->divV)) return -1;
+        vk = t->v_general ? V_GENERAL : V_DIVFREE;
+    }
+    if (diff) {
+        dk = t->d_type;
+        if (dk < D_CONSTANT || dk > D_FULL) return -1;
+        const int nd = dk == D_CONSTANT ? 0 : (dk == D_SCALAR ? 1 : (dk == D_DIAG ? 3 : 6));
+        for (int j = 0; j < nd; ++j) if (!t->D[j]) return -1;
+        if (dk != D_CONSTANT) for (int j = 0; j < 3; ++j) if (!t->G[j]) return -1;
+    }
+    return vk + 4 * dk;
+}
+
+PdeTerms pde_terms(const bfm_pde_terms_t* t) {
+    PdeTerms P{};
+    if (!t) return P;
+    for (int j = 0; j < 6; ++j) P.D[j] = t->D[j];
+    for (int j = 0; j < 3; ++j) P.G[j] = t->G[j];
+    P.divV = t->divV; P.Dc = t->D_const;
+    return P;
+}
+
+// f(std::integral_constant<int, CFG>) for the built configuration `cfg`
+template <typename F>
+bool pde_dispatch(int cfg, F&& f) {
+    switch (cfg) {
+#define BFM_PDE_CASE(VK, DK) case (VK) + 4 * (DK): f(std::integral_constant<int, (VK) + 4 * (DK)>{}); return true;
+        BFM_PDE_CASE(V_DIVFREE, D_NONE) BFM_PDE_CASE(V_GENERAL, D_NONE)
+        BFM_PDE_CASE(V_NONE, D_CONSTANT) BFM_PDE_CASE(V_DIVFREE, D_CONSTANT) BFM_PDE_CASE(V_GENERAL, D_CONSTANT)
+        BFM_PDE_CASE(V_NONE, D_SCALAR) BFM_PDE_CASE(V_DIVFREE, D_SCALAR) BFM_PDE_CASE(V_GENERAL, D_SCALAR)
+        BFM_PDE_CASE(V_NONE, D_DIAG) BFM_PDE_CASE(V_DIVFREE, D_DIAG) BFM_PDE_CASE(V_GENERAL, D_DIAG)
+        BFM_PDE_CASE(V_NONE, D_FULL) BFM_PDE_CASE(V_DIVFREE, D_FULL) BFM_PDE_CASE(V_GENERAL, D_FULL)
+#undef BFM_PDE_CASE
+        default: return false;
+    }
+}
+
+bool ode_ok(const bfm_dopri5_advect_t* d, const bfm_pde_terms_t* t) {
+    if (!d || !d->y[0] || !d->y[1] || !d->f[0] || !d->f[1] || !d->state || !d->workspace || !d->t_out || !d->sol ||
+        d->nt < 2 || pde_cfg(t, d->Vx, d->Vy, d->Vz) < 0)
         return false;
     for (int j = 0; j < 5; ++j) if (!d->k[j]) return false;
     return d->sx >= 3 && d->sy >= 3 && d->sz >= 3 && (int64_t)d->sx * d->sy <= INT32_MAX;
 }
 
-OdeArgs ode_args(const bfm_dopri5_advect_t* d) {
+OdeArgs ode_args(const bfm_dopri5_advect_t* d, const bfm_pde_terms_t* t) {
     OdeArgs A;
+    A.P = pde_terms(t);
     A.y[0] = d->y[0]; A.y[1] = d->y[1]; A.f[0] = d->f[0]; A.f[1] = d->f[1];
     for (int j = 0; j < 5; ++j) A.k[j] = d->k[j];
     A.Vx = d->Vx; A.Vy = d->Vy; A.Vz = d->Vz;
@@ -299,18 +454,18 @@ int ode_boxes(const bfm_dopri5_advect_t* d) {
     return ((d->sx + TX - 1) / TX) * ((d->sy + TY - 1) / TY) * ((d->sz + TZ - 1) / TZ);
 }
 
-template <typename T>
+template <typename T, int CFG>
 void ode_enqueue_step(const bfm_dopri5_advect_t* d, const OdeArgs& A, hipStream_t s) {
     const int64_t n = (int64_t)d->sx * d->sy * d->sz;
     const int nb = ode_boxes(d);
     const dim3 gs(nb), bs(256);
     double* part = static_cast<double*>(d->workspace);
-    hipLaunchKernelGGL((ode_stage<T, 1>), gs, bs, 0, s, A, d->atol, d->rtol, part);
-    hipLaunchKernelGGL((ode_stage<T, 2>), gs, bs, 0, s, A, d->atol, d->rtol, part);
-    hipLaunchKernelGGL((ode_stage<T, 3>), gs, bs, 0, s, A, d->atol, d->rtol, part);
-    hipLaunchKernelGGL((ode_stage<T, 4>), gs, bs, 0, s, A, d->atol, d->rtol, part);
-    hipLaunchKernelGGL((ode_stage<T, 5>), gs, bs, 0, s, A, d->atol, d->rtol, part);
-    hipLaunchKernelGGL((ode_stage<T, 6>), gs, bs, 0, s, A, d->atol, d->rtol, part);
+    hipLaunchKernelGGL((ode_stage<T, 1, CFG>), gs, bs, 0, s, A, d->atol, d->rtol, part);
+    hipLaunchKernelGGL((ode_stage<T, 2, CFG>), gs, bs, 0, s, A, d->atol, d->rtol, part);
+    hipLaunchKernelGGL((ode_stage<T, 3, CFG>), gs, bs, 0, s, A, d->atol, d->rtol, part);
+    hipLaunchKernelGGL((ode_stage<T, 4, CFG>), gs, bs, 0, s, A, d->atol, d->rtol, part);
+    hipLaunchKernelGGL((ode_stage<T, 5, CFG>), gs, bs, 0, s, A, d->atol, d->rtol, part);
+    hipLaunchKernelGGL((ode_stage<T, 6, CFG>), gs, bs, 0, s, A, d->atol, d->rtol, part);
     CtlP P{d->tol_min_dt, d->dt_max, d->safety, d->ifactor, d->dfactor, n};
     hipLaunchKernelGGL(ode_control, dim3(1), bs, 0, s, A.st, part, nb, P);
     hipLaunchKernelGGL(ode_dense<T>, dim3(grid_for(n)), bs, 0, s, A, d->t_out, d->nt, static_cast<T*>(d->sol), n);
@@ -324,20 +479,33 @@ extern "C" size_t bfm_dopri5_advect_workspace(int sx, int sy, int sz) {
     return (size_t)((sx + TX - 1) / TX) * ((sy + TY - 1) / TY) * ((sz + TZ - 1) / TZ) * sizeof(double);
 }
 
-extern "C" int bfm_dopri5_advect_init(const bfm_dopri5_advect_t* d, double t0, double dt0, bfm_stream_t stream) {
-    if (!ode_ok(d) || !(dt0 > 0)) return BFM_E_ARG;
+extern "C" int bfm_dopri5_advdiff_init(const bfm_dopri5_advect_t* d, const bfm_pde_terms_t* terms, double t0, double dt0,
+                                       bfm_stream_t stream) {
+    if (!ode_ok(d, terms) || !(dt0 > 0)) return BFM_E_ARG;
     hipLaunchKernelGGL(ode_init, dim3(1), dim3(1), 0, bfm_s(stream), static_cast<OdeState*>(d->state), t0, dt0);
     return bfm_launch_status();
 }
 
-extern "C" int bfm_dopri5_advect_steps(const bfm_dopri5_advect_t* d, int nsteps, bfm_stream_t stream) {
-    if (!ode_ok(d) || nsteps <= 0) return BFM_E_ARG;
-    const OdeArgs A = ode_args(d);
-    for (int s = 0; s < nsteps; ++s) {
-        if (d->is_f64) ode_enqueue_step<double>(d, A, bfm_s(stream));
-        else ode_enqueue_step<float>(d, A, bfm_s(stream));
-    }
+extern "C" int bfm_dopri5_advdiff_steps(const bfm_dopri5_advect_t* d, const bfm_pde_terms_t* terms, int nsteps,
+                                        bfm_stream_t stream) {
+    if (!ode_ok(d, terms) || nsteps <= 0) return BFM_E_ARG;
+    const OdeArgs A = ode_args(d, terms);
+    pde_dispatch(pde_cfg(terms, d->Vx, d->Vy, d->Vz), [&](auto cfg) {
+        constexpr int CFG = decltype(cfg)::value;
+        for (int s = 0; s < nsteps; ++s) {
+            if (d->is_f64) ode_enqueue_step<double, CFG>(d, A, bfm_s(stream));
+            else ode_enqueue_step<float, CFG>(d, A, bfm_s(stream));
+        }
+    });
     return bfm_launch_status();
+}
+
+extern "C" int bfm_dopri5_advect_init(const bfm_dopri5_advect_t* d, double t0, double dt0, bfm_stream_t stream) {
+    return bfm_dopri5_advdiff_init(d, nullptr, t0, dt0, stream);
+}
+
+extern "C" int bfm_dopri5_advect_steps(const bfm_dopri5_advect_t* d, int nsteps, bfm_stream_t stream) {
+    return bfm_dopri5_advdiff_steps(d, nullptr, nsteps, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -357,9 +525,11 @@ struct FixedArgs {
     const float *Vx, *Vy, *Vz;
     float* kout;
     int sx, sy, sz, neumann;
+    PdeTerms P;
+    double* kout64;     // a general V with an fp64 state, stand-alone RHS only: the unrounded value (pde.py:524 promotes)
 };
 
-template <typename T, int NK, int NF>
+template <typename T, int NK, int NF, int CFG>
 __global__ void __launch_bounds__(256) ode_fixed_stage(const T* __restrict__ y, T* __restrict__ y1, FixedArgs A) {
     __shared__ T sU[HX * HY * HZ];
     const int sx = A.sx, sy = A.sy, sz = A.sz;
@@ -396,30 +566,15 @@ __global__ void __launch_bounds__(256) ode_fixed_stage(const T* __restrict__ y, 
             const int x = x0 + tx;
             if (x >= sx) break;
             const int64_t i = x * stx + yy * sty + z;
-            auto U = [&](int dx, int dy, int dz) -> T { return sU[((tx + 1 + dx) * HY + (ty + 1 + dy)) * HZ + (tz + 1 + dz)]; };
-            const T u = U(0, 0, 0);
-            float acc = 0.f;
-            bool first = true;
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                const int pos = ax == 0 ? x : (ax == 1 ? yy : z);
-                const int len = ax == 0 ? sx : (ax == 1 ? sy : sz);
-                const int ex = ax == 0, ey = ax == 1, ez = ax == 2;
-                const int fw = pos < len - 1 ? 1 : 0, bw = pos > 0 ? 1 : 0;
-                const T up = U(ex * fw, ey * fw, ez * fw);
-                const T dn = U(-ex * bw, -ey * bw, -ez * bw);
-                const float df = pos < len - 1 ? (float)(up - u) : (float)(u - dn);
-                const float db = pos > 0 ? (float)(u - dn) : (float)(up - u);
-                const float V = ax == 0 ? A.Vx[i] : (ax == 1 ? A.Vy[i] : A.Vz[i]);
-                const float flag = V > 0.f ? 1.f : 0.f;
-                const float d = df * (1.f - flag) + db * flag;
-                const float term = V * d;
-                acc = first ? term : acc + term;
-                first = false;
-            }
-            const float kn = -acc;
+            const auto rk = box_rhs<T, CFG>(sU, tx, ty, tz, x, yy, z, sx, sy, sz, i, A.Vx, A.Vy, A.Vz, A.P);
+            const float kn = (float)rk;
             if constexpr (NF < 0) {
-                A.kout[i] = kn;
+                if constexpr (std::is_same<rhs_t<T, CFG>, double>::value) {
+                    if (A.kout64) A.kout64[i] = rk;
+                    else A.kout[i] = kn;
+                } else {
+                    A.kout[i] = kn;
+                }
             } else if constexpr (NF == 0) {
                 y1[i] = (T)(y[i] + (T)(A.cf[0] * kn));
             } else {
@@ -433,16 +588,17 @@ __global__ void __launch_bounds__(256) ode_fixed_stage(const T* __restrict__ y, 
     }
 }
 
-template <typename T, int NK, int NF>
+template <typename T, int NK, int NF, int CFG>
 void fixed_launch(const T* y, T* y1, const FixedArgs& A, int nb, hipStream_t s) {
-    hipLaunchKernelGGL((ode_fixed_stage<T, NK, NF>), dim3(nb), dim3(256), 0, s, y, y1, A);
+    hipLaunchKernelGGL((ode_fixed_stage<T, NK, NF, CFG>), dim3(nb), dim3(256), 0, s, y, y1, A);
 }
 
-template <typename T>
-void fixed_enqueue(const bfm_ode_fixed_advect_t* d, hipStream_t s) {
+template <typename T, int CFG>
+void fixed_enqueue(const bfm_ode_fixed_advect_t* d, const bfm_pde_terms_t* t, hipStream_t s) {
     const int64_t n = (int64_t)d->sx * d->sy * d->sz;
     const int nb = ((d->sx + TX - 1) / TX) * ((d->sy + TY - 1) / TY) * ((d->sz + TZ - 1) / TZ);
     FixedArgs A{};
+    A.P = pde_terms(t);
     A.Vx = d->Vx; A.Vy = d->Vy; A.Vz = d->Vz;
     A.sx = d->sx; A.sy = d->sy; A.sz = d->sz; A.neumann = d->neumann_bc ? 1 : 0;
     for (int j = 0; j < 3; ++j) A.k[j] = d->k[j];
@@ -453,23 +609,23 @@ void fixed_enqueue(const bfm_ode_fixed_advect_t* d, hipStream_t s) {
         const float* c = d->coef + (size_t)i * bfm_ode_fixed_ncoef(d->method);
         if (d->method == BFM_ODE_EULER) {                       // dy = dt * f(y)
             A.cf[0] = c[0];
-            fixed_launch<T, 0, 0>(y, y1, A, nb, s);
+            fixed_launch<T, 0, 0, CFG>(y, y1, A, nb, s);
         } else if (d->method == BFM_ODE_MIDPOINT) {             // dy = dt * f(y + f(y) * dt / 2)
             A.kout = d->k[0];
-            fixed_launch<T, 0, -1>(y, y1, A, nb, s);
+            fixed_launch<T, 0, -1, CFG>(y, y1, A, nb, s);
             A.c[0] = c[0]; A.cf[0] = c[1];
-            fixed_launch<T, 1, 0>(y, y1, A, nb, s);
+            fixed_launch<T, 1, 0, CFG>(y, y1, A, nb, s);
         } else {                                                // the 3/8 rule, rk4_alt_step_func
             A.kout = d->k[0];
-            fixed_launch<T, 0, -1>(y, y1, A, nb, s);
+            fixed_launch<T, 0, -1, CFG>(y, y1, A, nb, s);
             A.c[0] = c[0]; A.kout = d->k[1];
-            fixed_launch<T, 1, -1>(y, y1, A, nb, s);
+            fixed_launch<T, 1, -1, CFG>(y, y1, A, nb, s);
             A.c[0] = c[1]; A.c[1] = c[2]; A.kout = d->k[2];
-            fixed_launch<T, 2, -1>(y, y1, A, nb, s);
+            fixed_launch<T, 2, -1, CFG>(y, y1, A, nb, s);
             A.c[0] = c[3]; A.c[1] = c[4]; A.c[2] = c[5];
             A.cf[0] = c[6]; A.cf[1] = c[7]; A.cf[2] = c[8]; A.cf[3] = c[9];
             A.kout = nullptr;
-            fixed_launch<T, 3, 3>(y, y1, A, nb, s);
+            fixed_launch<T, 3, 3, CFG>(y, y1, A, nb, s);
         }
     }
 }
@@ -480,13 +636,89 @@ extern "C" int bfm_ode_fixed_ncoef(int method) {
     return method == BFM_ODE_EULER ? 1 : (method == BFM_ODE_MIDPOINT ? 2 : (method == BFM_ODE_RK4 ? 10 : 0));
 }
 
-extern "C" int bfm_ode_fixed_advect(const bfm_ode_fixed_advect_t* d, bfm_stream_t stream) {
-    if (!d || !d->sol || !d->Vx || !d->Vy || !d->Vz || !d->coef || d->nt < 2) return BFM_E_ARG;
+extern "C" int bfm_ode_fixed_advdiff(const bfm_ode_fixed_advect_t* d, const bfm_pde_terms_t* terms, bfm_stream_t stream) {
+    if (!d || !d->sol || !d->coef || d->nt < 2) return BFM_E_ARG;
+    const int cfg = pde_cfg(terms, d->Vx, d->Vy, d->Vz);
+    if (cfg < 0) return BFM_E_ARG;
     const int nk = d->method == BFM_ODE_EULER ? 0 : (d->method == BFM_ODE_MIDPOINT ? 1 : (d->method == BFM_ODE_RK4 ? 3 : -1));
     if (nk < 0) return BFM_E_ARG;
     for (int j = 0; j < nk; ++j) if (!d->k[j]) return BFM_E_ARG;
     if (d->sx < 3 || d->sy < 3 || d->sz < 3 || (int64_t)d->sx * d->sy > INT32_MAX) return BFM_E_ARG;
-    if (d->is_f64) fixed_enqueue<double>(d, bfm_s(stream));
-    else fixed_enqueue<float>(d, bfm_s(stream));
+    pde_dispatch(cfg, [&](auto c) {
+        constexpr int CFG = decltype(c)::value;
+        if (d->is_f64) fixed_enqueue<double, CFG>(d, terms, bfm_s(stream));
+        else fixed_enqueue<float, CFG>(d, terms, bfm_s(stream));
+    });
+    return bfm_launch_status();
+}
+
+extern "C" int bfm_ode_fixed_advect(const bfm_ode_fixed_advect_t* d, bfm_stream_t stream) {
+    return bfm_ode_fixed_advdiff(d, nullptr, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The stand-alone right-hand side (AdvDiffPDE.forward and the unfused host routes): the first stage of the fixed-grid
+// kernel, k_1 = f(y), so the bits of the fused routes.  Derived fields: sums of central differences of fp32 fields.
+namespace {
+
+// out = sum_j c_{axis[j]}(f[j]), j < nterms, added left to right in fp32 (gradient_c of pde.py:127-186)
+struct CentralSum { const float* f[3]; int axis[3]; int nterms; };
+
+__global__ void pde_central_sum(CentralSum S, int sx, int sy, int sz, float* __restrict__ out) {
+    const int64_t n = (int64_t)sx * sy * sz;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int z = (int)(i % sz), y = (int)((i / sz) % sy), x = (int)(i / ((int64_t)sz * sy));
+        float acc = 0.f;
+        for (int j = 0; j < S.nterms; ++j) {
+            const int a = S.axis[j];
+            const int pos = a == 0 ? x : (a == 1 ? y : z), len = a == 0 ? sx : (a == 1 ? sy : sz);
+            const int64_t st = a == 0 ? (int64_t)sy * sz : (a == 1 ? sz : 1);
+            const float* __restrict__ f = S.f[j];
+            float d;
+            if (pos == 0) d = f[i + st] - f[i];
+            else if (pos == len - 1) d = f[i] - f[i - st];
+            else d = (f[i + st] - f[i - st]) / 2.f;
+            acc = j == 0 ? d : acc + d;
+        }
+        out[i] = acc;
+    }
+}
+
+}  // namespace
+
+extern "C" int bfm_pde_central_sum(const float* const* f, const int* axis, int nterms, int sx, int sy, int sz, float* out,
+                                   bfm_stream_t stream) {
+    if (!f || !axis || !out || nterms < 1 || nterms > 3 || sx < 2 || sy < 2 || sz < 2) return BFM_E_ARG;
+    CentralSum S{};
+    S.nterms = nterms;
+    for (int j = 0; j < nterms; ++j) {
+        if (!f[j] || axis[j] < 0 || axis[j] > 2) return BFM_E_ARG;
+        S.f[j] = f[j]; S.axis[j] = axis[j];
+    }
+    const int64_t n = (int64_t)sx * sy * sz;
+    hipLaunchKernelGGL(pde_central_sum, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), S, sx, sy, sz, out);
+    return bfm_launch_status();
+}
+
+extern "C" int bfm_advdiff_rhs(const void* C, int c_is_f64, const float* Vx, const float* Vy, const float* Vz,
+                               const bfm_pde_terms_t* terms, int sx, int sy, int sz, int neumann_bc, void* out,
+                               int out_is_f64, bfm_stream_t stream) {
+    if (!C || !out) return BFM_E_ARG;
+    const int cfg = pde_cfg(terms, Vx, Vy, Vz);
+    if (cfg < 0) return BFM_E_ARG;
+    if (sx < 3 || sy < 3 || sz < 3 || (int64_t)sx * sy > INT32_MAX) return BFM_E_ARG;
+    if (out_is_f64 && !(c_is_f64 && (cfg & 3) == V_GENERAL)) return BFM_E_ARG;     // only that product promotes
+    FixedArgs A{};
+    A.P = pde_terms(terms);
+    A.Vx = Vx; A.Vy = Vy; A.Vz = Vz;
+    A.sx = sx; A.sy = sy; A.sz = sz; A.neumann = neumann_bc ? 1 : 0;
+    if (out_is_f64) A.kout64 = static_cast<double*>(out);
+    else A.kout = static_cast<float*>(out);
+    const int nb = ((sx + TX - 1) / TX) * ((sy + TY - 1) / TY) * ((sz + TZ - 1) / TZ);
+    pde_dispatch(cfg, [&](auto c) {
+        constexpr int CFG = decltype(c)::value;
+        if (c_is_f64) fixed_launch<double, 0, -1, CFG>(static_cast<const double*>(C), nullptr, A, nb, bfm_s(stream));
+        else fixed_launch<float, 0, -1, CFG>(static_cast<const float*>(C), nullptr, A, nb, bfm_s(stream));
+    });
     return bfm_launch_status();
 }

@@ -2,7 +2,7 @@
 
   generate_perlin_noise_3d / generate_shape_3d / generate_velocity_3d     ShapeID/perlin3d.py:15-156
   stream_3D                                                               ShapeID/misc.py:66-80
-  AdvDiffPDE(...).forward(t, batch_C)                                     ShapeID/DiffEqs/pde.py:563-640
+  AdvDiffPDE(...).forward(t, batch_C)                                     ShapeID/DiffEqs/pde.py:331-640 ('adv', 'diff', 'adv_diff')
   odeint / odeint_adjoint (method 'dopri5')                               DiffEqs/odeint.py:20-75, adjoint.py:105-132,
                                                                           dopri5.py:58-172, rk_common.py, interp.py, misc.py
   odeint_adjoint (methods 'euler', 'midpoint', 'rk4')                     DiffEqs/fixed_grid.py:5-33, solvers.py:158-207,
@@ -11,7 +11,7 @@
 The lattice gradients are drawn on the host with ``np.random`` exactly like the reference (two
 ``rand`` calls per field) and uploaded; everything per voxel runs in libbrainfm_hip.so.  The
 Dormand-Prince controller (accept / reject, clamped step) stays on the host and reads one reduced
-scalar per step; only the solvers and PDE variants the shipped configs use are provided.
+scalar per step.
 """
 import ctypes as C
 import math
@@ -184,26 +184,157 @@ def generate_velocity_3d(shape, perlin_res, V_multiplier, device):
 
 
 # ----------------------------------------------------------------------------- PDE right-hand side
+_V_DIV_FREE = ("vector_div_free", "vector_div_free_clebsch", "vector_div_free_stream", "vector_div_free_stream_gauge")
+_D_TENSOR = ("Dxx", "Dyy", "Dzz", "Dxy", "Dyz", "Dxz")
+# D_type -> (BFM_PDE_D_*, the D_dict entries read); Grad_Ds of pde.py:338-349
+_D_TYPES = {"constant": (L.PDE_D_CONSTANT, ("D",)), "scalar": (L.PDE_D_SCALAR, ("D",)),
+            "diag": (L.PDE_D_DIAG, _D_TENSOR[:3]), "full": (L.PDE_D_FULL, _D_TENSOR)}
+for _alias in ("full_dual", "full_spectral", "full_cholesky", "full_symmetric"):
+    _D_TYPES[_alias] = _D_TYPES["full"]
+# the fields whose central differences, summed over x, y, z, multiply c_x C, c_y C, c_z C in Grad_fullD (pde.py:435-437)
+_FULL_ROWS = ((0, 3, 5), (3, 1, 4), (5, 4, 2))
+
+
 class AdvDiffPDE(nn.Module):
-    """ShapeID/DiffEqs/pde.py:563-640 for the configuration the generator uses
-    (Generator/datasets.py:131-138): perf_pattern='adv', V_type='vector_div_free', 3-D, unit spacing."""
+    """ShapeID/DiffEqs/pde.py:563-640 on 3-D unit-spacing volumes, one volume per call.
+
+    perf_pattern   'adv' (the generator's, Generator/datasets.py:131-138), 'diff', or both names ('adv_diff'): pde.py:623-639
+    D_type         'constant', 'scalar', 'diag', 'full' and the 'full_*' aliases (pde.py:362-441); D_dict holds fp32
+                   (1, s, r, c) fields ((s, r, c) is read as that), 'constant' a float or one-element tensor
+    V_type         'vector_div_free' and its aliases, or 'vector' (pde.py:499-524); V_dict holds fp32 Vx, Vy, Vz
+    BC             None, 'neumann', 'cauchy'; 'dirichlet' is the reference's identity branch (pde.py:613-614)
+    Refused by name: stochastic=True, V_type 'constant' / 'scalar', BC 'dirichlet_neumann' / 'source_neumann' (the
+    reference's 3-D branch calls an attribute that does not exist, pde.py:610), non-unit spacing, 1-D and 2-D.
+
+    The central differences of the D fields and div V do not depend on the state: bfm_pde_central_sum computes them at
+    the start of every integration and in every `forward` call, from the dictionaries as they are then; only `stage`, the
+    integrators' call, reuses what the integration computed."""
 
     def __init__(self, data_spacing, perf_pattern, D_type="scalar", V_type="vector", BC=None, dt=0.1, V_dict={},
                  D_dict={}, stochastic=False, device="cpu"):
         super().__init__()
         if len(data_spacing) != 3 or list(data_spacing) != [1., 1., 1.]:
             raise NotImplementedError("only 3-D unit-spacing volumes are on the synthesis path")
-        if "diff" in perf_pattern or V_type != "vector_div_free" or stochastic:
-            raise NotImplementedError("only perf_pattern='adv' with V_type='vector_div_free' is on the synthesis path")
-        if BC not in (None, "neumann", "cauchy"):
+        if stochastic:
+            raise NotImplementedError("stochastic=True (the Sigma noise term of pde.py:625-635) is not built")
+        self._has_diff = "diff" in perf_pattern
+        self._has_adv = not self._has_diff or "adv" in perf_pattern
+        if self._has_adv:
+            if V_type in ("constant", "scalar"):
+                raise NotImplementedError("V_type %r (Grad_constantV / Grad_scalarV) is not built: 'vector' and the "
+                                          "'vector_div_free' names are" % V_type)
+            if V_type not in _V_DIV_FREE + ("vector",):
+                raise NotImplementedError("unknown V_type %r" % (V_type,))
+        if self._has_diff and D_type not in _D_TYPES:
+            raise NotImplementedError("unknown D_type %r" % (D_type,))
+        if BC in ("dirichlet_neumann", "source_neumann"):
+            raise NotImplementedError("BC %r: the reference's 3-D branch names an attribute that does not exist "
+                                      "(pde.py:610)" % BC)
+        if BC not in (None, "neumann", "cauchy", "dirichlet"):
             raise NotImplementedError("Unsupported B.C.!")
         self.BC, self.dt, self.dimension = BC, dt, 3
         self.perf_pattern, self.V_type, self.D_type = perf_pattern, V_type, D_type
         self.V_dict, self.D_dict = V_dict, D_dict
+        self.stochastic = False
         self.nfe = 0
+        self._general_v = self._has_adv and V_type == "vector"
+        # the generator's configuration keeps its own kernel and call
+        self._adv_only = self._has_adv and not self._has_diff and not self._general_v
+        self._cache = None
+
+    @property
+    def _neumann(self):
+        return 1 if self.BC in ("neumann", "cauchy") else 0
+
+    # ---- the fields of the new configurations
+    @staticmethod
+    def _field(d, name, shape, dev):
+        t = d.get(name)
+        if t is None:
+            raise KeyError("AdvDiffPDE needs %r in its field dictionary" % name)
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise TypeError("%s must be an fp32 tensor" % name)
+        if t.device != dev:
+            raise L.BfmError("%s is on %s, the state on %s" % (name, t.device, dev))
+        if tuple(t.shape) not in (shape, (1,) + shape):
+            raise ValueError("%s has shape %s, the state %s" % (name, tuple(t.shape), (1,) + shape))
+        return t.contiguous()
+
+    @staticmethod
+    def _central_sum(fields, axes, shape):
+        out = torch.empty(shape, dtype=torch.float32, device=fields[0].device)
+        fp = (C.c_void_p * len(fields))(*[f.data_ptr() for f in fields])
+        ax = (C.c_int * len(axes))(*axes)
+        L.check(L.load().bfm_pde_central_sum(fp, ax, len(fields), shape[0], shape[1], shape[2], L.ptr(out),
+                                             L.stream_ptr()), "pde_central_sum")
+        return out
+
+    def prepare(self, shape, dev, refresh=True):
+        """The terms block (bfm_pde_terms_t) of this configuration on a volume of `shape`, with its derived fields, from
+        V_dict / D_dict as they are now.  refresh=False (`stage` alone) returns the last block if it is for this shape."""
+        shape = tuple(int(v) for v in shape)
+        c = self._cache
+        if not refresh and c is not None and c["shape"] == shape and c["dev"] == dev:
+            return c
+        terms = L.PdeTerms()
+        terms.perf = (L.PDE_ADV if self._has_adv else 0) | (L.PDE_DIFF if self._has_diff else 0)
+        V, D, G, divV = [None] * 3, [], [], None
+        if self._has_adv:
+            V = [self._field(self.V_dict, k, shape, dev) for k in ("Vx", "Vy", "Vz")]
+            if self._general_v:
+                terms.v_general = 1
+                divV = self._central_sum(V, (0, 1, 2), shape)
+                terms.divV = divV.data_ptr()
+        if self._has_diff:
+            kind, names = _D_TYPES[self.D_type]
+            terms.d_type = kind
+            if kind == L.PDE_D_CONSTANT:
+                if "D" not in self.D_dict:
+                    raise KeyError("AdvDiffPDE needs 'D' in its field dictionary")
+                terms.D_const = float(np.float32(float(self.D_dict["D"])))
+            else:
+                D = [self._field(self.D_dict, k, shape, dev) for k in names]
+                if kind == L.PDE_D_FULL:
+                    G = [self._central_sum([D[j] for j in row], (0, 1, 2), shape) for row in _FULL_ROWS]
+                else:
+                    G = [self._central_sum([D[0 if kind == L.PDE_D_SCALAR else a]], (a,), shape) for a in range(3)]
+                for j, t in enumerate(D):
+                    terms.D[j] = t.data_ptr()
+                for j, t in enumerate(G):
+                    terms.G[j] = t.data_ptr()
+        self._cache = {"shape": shape, "dev": dev, "terms": terms, "V": V, "keep": (D, G, divV)}
+        return self._cache
+
+    def _rhs(self, batch_C, promote, c=None):
+        lib = L.load()
+        if c is None:                                        # forward: always from the dictionaries as they are now
+            c = self.prepare(tuple(batch_C.shape[-3:]), batch_C.device, refresh=promote)
+        if batch_C.shape[0] != 1:
+            return torch.cat([self._rhs(batch_C[b:b + 1], promote, c) for b in range(batch_C.shape[0])], 0)
+        Cc = batch_C.contiguous()
+        _, sx, sy, sz = Cc.shape
+        f64 = Cc.dtype == torch.float64
+        out64 = bool(promote and f64 and self._general_v)
+        out = torch.empty((1, sx, sy, sz), dtype=torch.float64 if out64 else torch.float32, device=Cc.device)
+        V = c["V"]
+        L.check(lib.bfm_advdiff_rhs(L.ptr(Cc), int(f64), L.ptr(V[0]), L.ptr(V[1]), L.ptr(V[2]), C.byref(c["terms"]),
+                                    sx, sy, sz, self._neumann, L.ptr(out), int(out64), L.stream_ptr()), "advdiff_rhs")
+        self.nfe += 1
+        return out
+
+    def stage(self, t, batch_C):
+        """forward as the integrators take it: an fp32 stage in every configuration (the reference's stage is fp64 for
+        V_type='vector' with an fp64 state; here the same value rounded once to fp32), on the derived fields the
+        integration computed at its start (`prepare`)."""
+        if self._adv_only:
+            return self(t, batch_C)
+        return self._rhs(batch_C, False)
 
     def forward(self, t, batch_C):
-        """batch_C: (1, s, r, c) fp32 or fp64 -> fp32 (1, s, r, c)."""
+        """batch_C: (1, s, r, c) fp32 or fp64 -> (1, s, r, c) in the reference's dtype: fp32, except V_type='vector' with
+        an fp64 state, where C * div V promotes the result to fp64."""
+        if not self._adv_only:
+            return self._rhs(batch_C, True)
         lib = L.load()
         if batch_C.shape[0] != 1:
             return torch.cat([self.forward(t, batch_C[b:b + 1]) for b in range(batch_C.shape[0])], 0)
@@ -217,6 +348,20 @@ class AdvDiffPDE(nn.Module):
                 "advect_upwind_rhs")
         self.nfe += 1
         return out
+
+
+def _pde_call(func, y0):
+    """(the stage function, the terms block or None, (Vx, Vy, Vz) pointers) of an integration from y0: the derived
+    fields of an AdvDiffPDE are recomputed here, once per integration."""
+    if not isinstance(func, AdvDiffPDE):
+        return func, None, None
+    if func._adv_only:
+        V = func.V_dict
+        return func.stage, None, [V[k].data_ptr() for k in ("Vx", "Vy", "Vz")]
+    if y0.dim() != 4:
+        return func.stage, None, None
+    c = func.prepare(tuple(y0.shape[-3:]), y0.device)
+    return func.stage, c["terms"], [None if v is None else v.data_ptr() for v in c["V"]]
 
 
 # ----------------------------------------------------------------------------- Dormand-Prince (as shipped)
@@ -246,6 +391,7 @@ class Dopri5Solver:
 
     def __init__(self, func, y0, rtol, atol, dt, safety=0.9, ifactor=10.0, dfactor=0.2):
         self.func, self.y0, self.rtol, self.atol, self.dt_cfg = func, y0, rtol, atol, dt
+        self.f = func                                    # the stage function: set by integrate()
         self.safety, self.ifactor, self.dfactor = safety, ifactor, dfactor
         self.lib = L.load()
         self.f64 = y0.dtype == torch.float64
@@ -278,7 +424,7 @@ class Dopri5Solver:
         y1 = torch.empty_like(y0)
         L.check(self.lib.bfm_rk_combine(L.ptr(y0), int(self.f64), C.byref(s), L.ptr(y1), self.n, L.stream_ptr()),
                 "rk_combine")
-        f1 = self.func(t0 + h0, y1)
+        f1 = self.f(t0 + h0, y1)
         d2 = self._rms_scaled(f1, f0, y0) / h0
         if d1 <= 1e-15 and d2 <= 1e-15:
             h1 = max(1e-6, h0 * 1e-3)
@@ -288,13 +434,14 @@ class Dopri5Solver:
 
     def integrate(self, t):
         t = [float(v) for v in t]
-        if isinstance(self.func, AdvDiffPDE) and self.y0.dim() == 4 and self.y0.shape[0] == 1 and len(t) >= 2 \
-                and os.environ.get("BFM_ODE_DEVICE", "1") != "0":
+        device = isinstance(self.func, AdvDiffPDE) and self.y0.dim() == 4 and self.y0.shape[0] == 1
+        self.f, self.terms, self.Vp = _pde_call(self.func, self.y0)       # an AdvDiffPDE's fp32 stage for any state shape
+        if device and len(t) >= 2 and os.environ.get("BFM_ODE_DEVICE", "1") != "0":
             return self._integrate_device(t)
         return self._integrate_host(t)
 
     def _integrate_device(self, t):
-        """The same integration with the controller on the device (bfm_dopri5_advect_*, csrc/synth_ode.hip): the host
+        """The same integration with the controller on the device (bfm_dopri5_advect_* / _advdiff_*, csrc/synth_ode.hip): the host
         selects the first step (three read-backs, once), then enqueues steps in chunks and reads one state block per
         chunk; accept / reject, the clamped next step and the dense outputs never leave the GPU.  Same expressions as
         the host loop below: same bits up to the last ulp of pow() in the step-size rule."""
@@ -304,7 +451,7 @@ class Dopri5Solver:
         dev = y0.device
         _, sx, sy, sz = y0.shape
         n = self.n
-        f0 = func(t[0], y0)
+        f0 = self.f(t[0], y0)
         dt0 = self._initial_step(t[0], y0, f0)
         nt = len(t)
         sol = torch.empty((nt,) + tuple(y0.shape), dtype=y0.dtype, device=dev)
@@ -321,8 +468,7 @@ class Dopri5Solver:
         d.f[0], d.f[1] = fbuf[0].data_ptr(), fbuf[1].data_ptr()
         for j in range(5):
             d.k[j] = ks[j].data_ptr()
-        V = func.V_dict
-        d.Vx, d.Vy, d.Vz = V["Vx"].data_ptr(), V["Vy"].data_ptr(), V["Vz"].data_ptr()
+        d.Vx, d.Vy, d.Vz = self.Vp
         d.sx, d.sy, d.sz = sx, sy, sz
         d.neumann_bc = 1 if func.BC in ("neumann", "cauchy") else 0
         d.is_f64 = int(self.f64)
@@ -332,11 +478,18 @@ class Dopri5Solver:
         d.safety, d.ifactor, d.dfactor = self.safety, self.ifactor, self.dfactor
         d.t_out, d.nt, d.sol = t_out.data_ptr(), nt, sol.data_ptr()
         d.state, d.workspace = state.data_ptr(), ws.data_ptr()
-        L.check(lib.bfm_dopri5_advect_init(C.byref(d), t[0], dt0, L.stream_ptr()), "dopri5_advect_init")
+        if self.terms is None:
+            init = lambda: lib.bfm_dopri5_advect_init(C.byref(d), t[0], dt0, L.stream_ptr())
+            steps = lambda n: lib.bfm_dopri5_advect_steps(C.byref(d), n, L.stream_ptr())
+        else:
+            tp = C.byref(self.terms)
+            init = lambda: lib.bfm_dopri5_advdiff_init(C.byref(d), tp, t[0], dt0, L.stream_ptr())
+            steps = lambda n: lib.bfm_dopri5_advdiff_steps(C.byref(d), tp, n, L.stream_ptr())
+        L.check(init(), "dopri5_advect_init" if self.terms is None else "dopri5_advdiff_init")
         # steps needed if every one were as long as allowed; the first chunk covers that, later ones what is left
         chunk = max(4, min(16, int(math.ceil((t[-1] - t[0]) / d.dt_max)) + 2))
         while True:
-            L.check(lib.bfm_dopri5_advect_steps(C.byref(d), chunk, L.stream_ptr()), "dopri5_advect_steps")
+            L.check(steps(chunk), "dopri5_advect_steps" if self.terms is None else "dopri5_advdiff_steps")
             ints = state[40:72].cpu().numpy().view(np.int32)
             cur, done, next_out, nsteps, naccept, accepted, err = (int(v) for v in ints[:7])
             if err:
@@ -350,7 +503,7 @@ class Dopri5Solver:
 
     def _integrate_host(self, t):
         y = self.y0
-        f = self.func(t[0], y)
+        f = self.f(t[0], y)
         dt = self._initial_step(t[0], y, f)
         t0s = t1s = t[0]
         interp = None
@@ -363,7 +516,7 @@ class Dopri5Solver:
                 yi = y
                 for beta in _BETA:
                     yi = self._combine(y, ks, dt, beta)
-                    ks.append(self.func(t1s, yi))
+                    ks.append(self.f(t1s, yi))
                 y1, f1 = yi, ks[-1]
                 es = _kset(ks, dt, _C_ERR, self.sd)
                 L.check(self.lib.bfm_rk_error_sumsq(C.byref(es), L.ptr(y), L.ptr(y1), int(self.f64), self.atol,
@@ -429,6 +582,7 @@ class FixedGridSolver:
 
     def __init__(self, func, y0, method):
         self.func, self.y0, self.method = func, y0, method
+        self.f = func                                    # the stage function: set by integrate()
         self.stages, self.first, self.final = _FIXED_TABLES[method]
         self.lib = L.load()
         self.f64 = y0.dtype == torch.float64
@@ -451,13 +605,14 @@ class FixedGridSolver:
 
     def integrate(self, t):
         t = [float(v) for v in t]
-        if isinstance(self.func, AdvDiffPDE) and self.y0.dim() == 4 and self.y0.shape[0] == 1 and len(t) >= 2 \
-                and os.environ.get("BFM_ODE_DEVICE", "1") != "0":
+        device = isinstance(self.func, AdvDiffPDE) and self.y0.dim() == 4 and self.y0.shape[0] == 1
+        self.f, self.terms, self.Vp = _pde_call(self.func, self.y0)       # an AdvDiffPDE's fp32 stage for any state shape
+        if device and len(t) >= 2 and os.environ.get("BFM_ODE_DEVICE", "1") != "0":
             return self._integrate_device(t)
         return self._integrate_host(t)
 
     def _integrate_device(self, t):
-        """All steps enqueued by one call (bfm_ode_fixed_advect, csrc/synth_ode.hip): one fused kernel per stage, the
+        """All steps enqueued by one call (bfm_ode_fixed_advect / _advdiff, csrc/synth_ode.hip): one fused kernel per stage, the
         last one storing y1 into its row of the solution.  Same expressions as the host loop below: same bits."""
         func, y0 = self.func, self.y0
         _, sx, sy, sz = y0.shape
@@ -474,14 +629,16 @@ class FixedGridSolver:
         d.sol = sol.data_ptr()
         for j, k in enumerate(ks):
             d.k[j] = k.data_ptr()
-        V = func.V_dict
-        d.Vx, d.Vy, d.Vz = V["Vx"].data_ptr(), V["Vy"].data_ptr(), V["Vz"].data_ptr()
+        d.Vx, d.Vy, d.Vz = self.Vp
         d.sx, d.sy, d.sz = sx, sy, sz
         d.neumann_bc = 1 if func.BC in ("neumann", "cauchy") else 0
         d.is_f64 = int(self.f64)
         d.method, d.nt = _FIXED_IDS[self.method], nt
         d.coef = (C.c_float * len(coef))(*coef)
-        L.check(self.lib.bfm_ode_fixed_advect(C.byref(d), L.stream_ptr()), "ode_fixed_advect")
+        if self.terms is None:
+            L.check(self.lib.bfm_ode_fixed_advect(C.byref(d), L.stream_ptr()), "ode_fixed_advect")
+        else:
+            L.check(self.lib.bfm_ode_fixed_advdiff(C.byref(d), C.byref(self.terms), L.stream_ptr()), "ode_fixed_advdiff")
         func.nfe += (len(self.stages) + 1) * (nt - 1)
         return sol
 
@@ -491,9 +648,9 @@ class FixedGridSolver:
         sol = [y]
         t0 = t[0]
         for dt in self.grid_steps(t):
-            ks = [self.func(t0, y)]
+            ks = [self.f(t0, y)]
             for c in self.stages:
-                ks.append(self.func(t0, self._combine(y, ks, dt, c)))
+                ks.append(self.f(t0, self._combine(y, ks, dt, c)))
             y = self._combine(y, ks[self.first:], dt, self.final)
             sol.append(y)
             t0 = t0 + float(dt)

@@ -924,6 +924,43 @@ typedef struct {
 int bfm_ode_fixed_ncoef(int method);
 int bfm_ode_fixed_advect(const bfm_ode_fixed_advect_t* d, bfm_stream_t stream);
 
+/* The other configurations of AdvDiffPDE (ShapeID/DiffEqs/pde.py:331-640, 3-D, unit spacing, batch of one): the diffusion
+ * terms Grad_constantD / Grad_scalarD / Grad_diagD / Grad_fullD (:362-441), the general velocity Grad_vectorV (:511-524)
+ * and their sum out_V + out_D (:623-639).  A terms block goes beside the structs above, whose layout is unchanged; NULL
+ * terms is the generator's configuration ('adv', divergence-free V), and the calls above are that case.
+ *   perf       BFM_PDE_ADV, BFM_PDE_DIFF or both ('adv', 'diff', 'adv_diff'); without ADV the V pointers may be NULL
+ *   d_type     BFM_PDE_D_* (with DIFF); the 'full_*' names of Grad_Ds are BFM_PDE_D_FULL
+ *   v_general  0: Grad_div_free_vectorV;  1: Grad_vectorV, the upwind term minus C * divV (promoting an fp64 state's
+ *              value to fp64 before it is rounded to the fp32 stage)
+ *   D          fp32 fields of n voxels: {D} (scalar), {Dxx, Dyy, Dzz} (diag), {Dxx, Dyy, Dzz, Dxy, Dyz, Dxz} (full)
+ *   G          the time-invariant factors of c_x C, c_y C, c_z C, by bfm_pde_central_sum: scalar {c_x D, c_y D, c_z D},
+ *              diag {c_x Dxx, c_y Dyy, c_z Dzz}, full the row sums {c_x Dxx + c_y Dxy + c_z Dxz, c_x Dxy + c_y Dyy +
+ *              c_z Dyz, c_x Dxz + c_y Dyz + c_z Dzz} (:435-437)
+ *   divV       c_x Vx + c_y Vy + c_z Vz (:517-524), with v_general
+ * f / b / c: gradient_f / gradient_b / gradient_c (:13-186).  The stage kernels are those of the calls above with the
+ * right-hand side chosen at compile time; sx, sy, sz >= 3. */
+enum { BFM_PDE_ADV = 1, BFM_PDE_DIFF = 2 };
+enum { BFM_PDE_D_CONSTANT = 1, BFM_PDE_D_SCALAR = 2, BFM_PDE_D_DIAG = 3, BFM_PDE_D_FULL = 4 };
+typedef struct {
+    int perf, d_type, v_general; float D_const;
+    const float* D[6]; const float* G[3]; const float* divV;
+} bfm_pde_terms_t;
+/* out = sum_j c_{axis[j]}(f[j]), j < nterms <= 3, added left to right in fp32 -- gradient_c, pde.py:127-186 (the derived
+ * fields G and divV above).  f, axis: host arrays of device pointers / axis numbers 0..2. */
+int bfm_pde_central_sum(const float* const* f, const int* axis, int nterms, int sx, int sy, int sz, float* out,
+                        bfm_stream_t stream);
+/* AdvDiffPDE.forward for any built configuration -- pde.py:616-640.  out is fp32, or fp64 (out_is_f64) for v_general
+ * with an fp64 C, the one case where the reference's result is fp64. */
+int bfm_advdiff_rhs(const void* C, int c_is_f64, const float* Vx, const float* Vy, const float* Vz,
+                    const bfm_pde_terms_t* terms, int sx, int sy, int sz, int neumann_bc, void* out, int out_is_f64,
+                    bfm_stream_t stream);
+/* bfm_dopri5_advect_init / _steps and bfm_ode_fixed_advect with a terms block -- dopri5.py:58-172, fixed_grid.py:5-33 over
+ * pde.py:616-640. */
+int bfm_dopri5_advdiff_init(const bfm_dopri5_advect_t* d, const bfm_pde_terms_t* terms, double t0, double dt0,
+                            bfm_stream_t stream);
+int bfm_dopri5_advdiff_steps(const bfm_dopri5_advect_t* d, const bfm_pde_terms_t* terms, int nsteps, bfm_stream_t stream);
+int bfm_ode_fixed_advdiff(const bfm_ode_fixed_advect_t* d, const bfm_pde_terms_t* terms, bfm_stream_t stream);
+
 /* ---- backward pass of the SingleConv block and its neighbours (first correct version) -------------------
  * The reference trains through torch autograd over buildingblocks.py:31-60 (GroupNorm -> Conv3d -> LeakyReLU),
  * :185-186 (MaxPool3d(2)), :265-276,361-363 (nearest upsample + concat).
