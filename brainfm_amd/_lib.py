@@ -198,6 +198,9 @@ SIGNATURES = {
     "bfm_grid_pull3d_spline": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
     "bfm_grid_push3d_spline": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
     "bfm_grid_grad3d_spline": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
+    "bfm_grid_pull2d_spline": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
+    "bfm_grid_push2d_spline": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
+    "bfm_grid_grad2d_spline": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
     "bfm_grid_hess3d": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P, _P]),
     "bfm_grid_pushgrad3d": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
     "bfm_spline_axis_table_workspace": (_Z, [_I, _I, _I]),

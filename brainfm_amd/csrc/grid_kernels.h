@@ -1,6 +1,7 @@
-// What the voxel-wise interpol grid kernels (spline_grid.hip, grid_hess.hip, label_pull.hip) and their exports share: the
-// launch shape, the options a call carries, the prologue of a voxel, the argument checks and the dispatch from the orders
-// of a call to the instantiation that runs it.  The nodes themselves are axis_node / axis_nodes of spline_nodes.h.
+// What the voxel-wise interpol grid kernels (spline_grid.hip, spline_grid2d.hip, grid_hess.hip, label_pull.hip) and their
+// exports share: the launch shape, the options a call carries, the prologue of a voxel (of a pixel on a 2-D grid), the
+// argument checks and the dispatch from the orders of a call to the instantiation that runs it.  The nodes themselves
+// are axis_node / axis_nodes of spline_nodes.h.
 //
 // One thread per voxel of the grid (the output of pull / grad / hess, the source of push / pushgrad).  A kernel is
 // instantiated for some isotropic orders O with O + 1 taps per axis, so that every array is indexed by constants and
@@ -48,6 +49,20 @@ __device__ __forceinline__ GridVoxel grid_voxel(int64_t i, int64_t nvox, const f
     return p;
 }
 
+// Pixel i of B * npix of a 2-D grid [Bg][*out][2] against (nx, ny): two ld_tex loads and the 2-D mask
+struct GridPixel { int b; int64_t v; float gx, gy, mask; };
+
+__device__ __forceinline__ GridPixel grid_pixel(int64_t i, int64_t npix, const float* grid, int Bg, int nx, int ny,
+                                                int extrap) {
+    GridPixel p;
+    p.b = (int)(i / npix);
+    p.v = i - (int64_t)p.b * npix;
+    const float* g = grid + ((int64_t)(Bg == 1 ? 0 : p.b) * npix + p.v) * 2;
+    p.gx = ld_tex(g); p.gy = ld_tex(g + 1);
+    p.mask = inbounds(p.gx, p.gy, nx, ny, extrap);
+    return p;
+}
+
 // the argument checks of the _linear exports (synth_interp.hip) plus the orders; (a0, a1, a2) and (b0, b1, b2) are the two
 // spatial shapes of the call
 inline int grid_check_args(const void* inp, const void* grid, const void* out, const int* bound, const int* order, int Bi,
@@ -64,6 +79,20 @@ inline int grid_check_args(const void* inp, const void* grid, const void* out, c
 
 inline GridOpts grid_opts(const int* bound, const int* order, int extrapolate) {
     return GridOpts{extrapolate, {bound[0], bound[1], bound[2]}, {order[0], order[1], order[2]}};
+}
+
+// The 2-D exports read bound[2] and order[2]: the same checks over two axes and two extents per shape (a 3-D call with a
+// third extent of 1, bound 0 and the order of the second axis, which keeps an isotropic 2-D call isotropic), and the
+// options with that third axis, which no 2-D kernel reads.
+inline int grid_check_args(const void* inp, const void* grid, const void* out, const int* bound, const int* order, int Bi,
+                           int Bg, int C, int a0, int a1, int b0, int b1, int extrapolate) {
+    if (!bound || !order) return BFM_E_ARG;
+    const int b3[3] = {bound[0], bound[1], 0}, o3[3] = {order[0], order[1], order[1]};
+    return grid_check_args(inp, grid, out, b3, o3, Bi, Bg, C, a0, a1, 1, b0, b1, 1, extrapolate);
+}
+
+inline GridOpts grid_opts2(const int* bound, const int* order, int extrapolate) {
+    return GridOpts{extrapolate, {bound[0], bound[1], 0}, {order[0], order[1], order[1]}};
 }
 
 // the order of an isotropic call, -1 for any other

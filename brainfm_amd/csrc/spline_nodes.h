@@ -87,3 +87,13 @@ __device__ __forceinline__ float inbounds(float gx, float gy, float gz, int nx, 
     }
     return 1.f;
 }
+
+// the same mask over the two axes of a 2-D grid
+__device__ __forceinline__ float inbounds(float gx, float gy, int nx, int ny, int extrap) {
+    if (extrap == 0 || extrap == 2) {
+        const float thr = extrap == 2 ? 0.5f + 5e-2f : 5e-2f;
+        const bool in = (gx > -thr) && (gx < (float)(nx - 1) + thr) && (gy > -thr) && (gy < (float)(ny - 1) + thr);
+        return in ? 1.f : 0.f;
+    }
+    return 1.f;
+}

@@ -6,6 +6,11 @@ restrict.hip, which also give the separable cubic ``resize`` its gradient).  All
 splines.py:30-103, bounds.py:24-89) on spline_grid.hip.  ``prefilter`` goes through ``spline_coeff_nd``
 (coeff.py:254-344), which is differentiable (autograd.py:276-300).
 
+``grid_pull`` / ``grid_push`` / ``grid_count`` of a floating-point image, ``spline_coeff_nd`` and ``resize`` also take
+2-D grids (..., X, Y, 2) on spline_grid2d.hip, differentiable to first order like their 3-D forms; there every order,
+the all-linear one included, is an instantiation of one kernel.  Label maps, ``grid_grad`` / ``grid_hess`` /
+``grid_pushgrad`` and ``restrict`` are 3-D only, and 1-D grids raise everywhere.
+
 grid_pull / grid_push are differentiable to first order through grid_push / grid_grad, and grid_grad through
 ``grid_pushgrad`` and ``grid_hess`` (pushpull.py:176-233 and :303-325; nd.py:291-464, iso1.py:390-675, iso0.py:326-368)
 on grid_hess.hip, which takes every order 0 to 3 in one export per operation.  Nothing here has a double backward, as in
@@ -72,7 +77,7 @@ def _bound_list(bound):
 
 
 def _prep(input, grid, dim=3, tail=(), cast=True):
-    """api.py:81-118 _preproc: broadcast batch dims, default channel of 1.  Returns (x (B,C,*in,*tail), g (B,*out,3), info).
+    """api.py:81-118 _preproc: broadcast batch dims, default channel of 1.  Returns (x (B,C,*in,*tail), g (B,*out,dim), info).
     tail: trailing dimensions of `input` behind the spatial ones (grid_pushgrad: (3,)); cast=False keeps the dtype of
     `input` (a label map) where the default computes in float32."""
     grid_spatial = tuple(grid.shape[-dim - 1:-1])
@@ -109,18 +114,23 @@ LABEL_PULL_AUTO, LABEL_PULL_LDS, LABEL_PULL_REGS, LABEL_PULL_PASSES = 0, 1, 2, 3
 
 def _export(name, x, g, dims, b, o, ext, extra, out):
     """One call of an export of the grid family, which all take (inp[, label dtype], Bi, C, *in, grid, Bg, *dims, bound[,
-    order], extrapolate, *extra, out, stream): x (Bi,C,*in[,3]) and g (Bg,*,3) contiguous, `dims` the other spatial shape
+    order], extrapolate, *extra, out, stream): x (Bi,C,*in[,3]) and g (Bg,*,D) contiguous, `dims` the other spatial shape
     of the call (the grid's for a pull, the volume's for a push), o None for a _linear export, which takes no order.
+    D = 2: the two extents of each shape; the export reads the first two of the three bounds and orders.
     Returns `out`."""
+    dim = g.shape[-1]
     args = [L.ptr(x)] + ([] if x.dtype.is_floating_point else [_LABEL_DTYPE[x.dtype]])
-    args += [x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.shape[4], L.ptr(g), g.shape[0], dims[0], dims[1], dims[2], b]
+    args += [x.shape[0], x.shape[1], *x.shape[2:2 + dim], L.ptr(g), g.shape[0], *dims[:dim], b]
     args += [] if o is None else [(C.c_int * 3)(*o)]
     L.check(getattr(L.load(), "bfm_" + name)(*args, ext, *extra, L.ptr(out), L.stream_ptr()), name)
     return out
 
 
-def _linear_or_spline(op, o):
-    """all-linear calls run iso1 on the kernels of synth_interp.hip, every other combination the generic path"""
+def _linear_or_spline(op, o, dim=3):
+    """3-D: all-linear calls run iso1 on the kernels of synth_interp.hip, every other combination the generic path.
+    2-D: every order is an instantiation of spline_grid2d.hip."""
+    if dim == 2:
+        return "grid_%s2d_spline" % op, o
     return ("grid_%s3d_linear" % op, None) if o == _LINEAR else ("grid_%s3d_spline" % op, o)
 
 
@@ -129,20 +139,22 @@ def _out(x, g, *trailing, fill=torch.empty):
 
 
 def _pull_raw(x, g, b, o, ext):
-    gs = tuple(g.shape[1:4])
-    name, o = _linear_or_spline("pull", o)
+    """x (Bi,C,*in), g (Bg,*out,D), D = 2 or 3 -> (B,C,*out)"""
+    gs = tuple(g.shape[1:-1])
+    name, o = _linear_or_spline("pull", o, g.shape[-1])
     return _export(name, x, g, gs, b, o, ext, (), _out(x, g, *gs))
 
 
 def _push_raw(x, g, shape, b, o, ext):
-    name, o = _linear_or_spline("push", o)
+    name, o = _linear_or_spline("push", o, g.shape[-1])
     return _export(name, x, g, shape, b, o, ext, (), _out(x, g, *shape, fill=torch.zeros))
 
 
 def _grad_raw(x, g, b, o, ext):
-    gs = tuple(g.shape[1:4])
-    name, o = _linear_or_spline("grad", o)
-    return _export(name, x, g, gs, b, o, ext, (), _out(x, g, *gs, 3))
+    """-> (B,C,*out,D).  On a 2-D grid this serves the autograd of pull and push only; the public grid_grad is 3-D."""
+    gs = tuple(g.shape[1:-1])
+    name, o = _linear_or_spline("grad", o, g.shape[-1])
+    return _export(name, x, g, gs, b, o, ext, (), _out(x, g, *gs, g.shape[-1]))
 
 
 def _hess_raw(x, g, b, o, ext, cot=None):
@@ -228,6 +240,14 @@ def _require_cuda(t, what):
         raise L.BfmError("%s runs on a HIP device only; there is no CPU fallback in the product path" % what)
 
 
+def _grid_dim(grid, what):
+    """The number of spatial dimensions of a call, from the last dimension of its grid: 2 or 3"""
+    dim = grid.shape[-1]
+    if dim not in (2, 3) or (dim == 2 and grid.dim() < 3):
+        raise NotImplementedError("%s: only 2-D and 3-D grids (..., *spatial, 2 or 3) are implemented" % what)
+    return dim
+
+
 def _needs_prefilter(prefilter, o, b, shape):
     """Orders 0 and 1: the prefilter is the identity.  Raises for an axis it would have to filter under 'dst1' / 'dst2'."""
     if not prefilter or all(k < 2 for k in o):
@@ -243,28 +263,30 @@ def _check_prefilter_bounds(orders, bounds, shape):
 
 
 def grid_push(input, grid, shape=None, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):
-    """api.py:203-250: splat `input` (..., [channel], *spatial) at the coordinates `grid` (..., *spatial, 3) into a
-    volume of `shape` (default: the input's spatial shape).  Differentiable w.r.t. input and grid.  `prefilter` filters
-    the result, as the reference does."""
+    """api.py:203-250: splat `input` (..., [channel], *spatial) at the coordinates `grid` (..., *spatial, D) into a
+    volume of `shape` (default: the input's spatial shape), D = 2 or 3.  Differentiable w.r.t. input and grid.
+    `prefilter` filters the result, as the reference does."""
     b, o, ext = _opts(interpolation, bound, extrapolate)
-    shape = tuple(int(v) for v in (shape if shape is not None else input.shape[-3:]))
-    prefilter = _needs_prefilter(prefilter, o, list(b), shape)
+    dim = _grid_dim(grid, "grid_push")
+    shape = tuple(int(v) for v in (shape if shape is not None else input.shape[-dim:]))
+    prefilter = _needs_prefilter(prefilter, o[:dim], list(b)[:dim], shape)
     _require_cuda(input, "grid_push")
-    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid)
+    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid, dim)
     if in_spatial != grid_spatial:
         raise ValueError("Input and grid should have the same spatial shape")
     out = _GridPush.apply(x, g, shape, b, o, ext)
     if prefilter:
-        out = spline_coeff_nd(out, interpolation=list(o), bound=bound, dim=3, inplace=True)
+        out = spline_coeff_nd(out, interpolation=list(o), bound=bound, dim=dim, inplace=True)
     return _unprep(out, batch, channel, *shape)
 
 
 def grid_count(grid, shape=None, interpolation="linear", bound="zero", extrapolate=False):
     """api.py:253-287: push of an image of ones (the Jacobian-free 'count' image)."""
     _opts(interpolation, bound, extrapolate)
+    dim = _grid_dim(grid, "grid_count")
     _require_cuda(grid, "grid_count")
-    gs = tuple(grid.shape[-4:-1])
-    ones = torch.ones(tuple(grid.shape[:-4]) + (1,) + gs, dtype=torch.float32, device=grid.device)
+    gs = tuple(grid.shape[-dim - 1:-1])
+    ones = torch.ones(tuple(grid.shape[:-dim - 1]) + (1,) + gs, dtype=torch.float32, device=grid.device)
     out = grid_push(ones, grid, shape, interpolation, bound, extrapolate)
     return out
 
@@ -341,21 +363,25 @@ def _label_pull(input, grid, b, o, ext, prefilter):
 def grid_pull(input, grid, interpolation="linear", bound="zero", extrapolate=False, prefilter=False):
     """Sample `input` at the voxel coordinates in `grid` (api.py:137-200).
 
-    input: (..., [channel], *spatial) ; grid: (..., *spatial_out, 3).  Returns (..., [channel], *spatial_out).
+    input: (..., [channel], *spatial) ; grid: (..., *spatial_out, D), D = 2 or 3.  Returns (..., [channel], *spatial_out).
     Computes in fp32 like the reference's custom_fwd(cast_inputs=torch.float32).  `prefilter` turns the image into
     spline coefficients first, so that the result interpolates it.  An integer image (uint8, int16, int32, int64) is a
-    label map: the result has its dtype and holds the label with the largest interpolated weight (_label_pull)."""
+    label map: the result has its dtype and holds the label with the largest interpolated weight (_label_pull); label
+    maps are pulled through 3-D grids only.  On a 2-D grid the first two of the orders and bounds are read."""
     b, o, ext = _opts(interpolation, bound, extrapolate)
-    if grid.shape[-1] != 3:
+    dim = grid.shape[-1]
+    if dim != 3 and not input.dtype.is_floating_point:
         raise NotImplementedError("only 3-D grids are on the hot path")
+    if dim not in (2, 3) or (dim == 2 and grid.dim() < 3):
+        raise NotImplementedError("only 2-D and 3-D grids are on the hot path")
     if not input.dtype.is_floating_point:
         return _label_pull(input, grid, b, o, ext, prefilter)
-    prefilter = _needs_prefilter(prefilter, o, list(b), input.shape[-3:])
+    prefilter = _needs_prefilter(prefilter, o[:dim], list(b)[:dim], input.shape[-dim:])
     if input.device.type != "cuda":
         raise L.BfmError("grid_pull runs on a HIP device only; there is no CPU fallback in the product path")
     if prefilter:
-        input = spline_coeff_nd(input, interpolation=list(o), bound=bound, dim=3)
-    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid)
+        input = spline_coeff_nd(input, interpolation=list(o), bound=bound, dim=dim)
+    x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid, dim)
     out = _GridPull.apply(x, g, b, o, ext)                       # differentiable w.r.t. input and grid (first order)
     return _unprep(out, batch, channel, *grid_spatial)
 
@@ -399,14 +425,16 @@ def _prefilter_scalars(n, order=3, family=0):
     return z, gain, 0.0, 1.0 / (1.0 - zm), 1.0 / (zm - 1.0), None, max_iter
 
 
-def _coeff_raw(inp, orders, bounds, inplace):
+def _coeff_raw(inp, orders, bounds, inplace, dim=3):
     """coeff.py:313-344 over the last three dimensions, one launch per volume and filtered axis (order 2 or 3, length
-    above 1).  Filters `inp` itself only if `inplace` and it is contiguous fp32; returns fp32."""
-    lead = inp.shape[:-3]
+    above 1).  dim = 2: over the last two, the whole batch as one (N, X, Y) volume filtered along its axes 1 and 2, one
+    launch per filtered axis.  Filters `inp` itself only if `inplace` and it is contiguous fp32; returns fp32."""
     vols = inp.to(torch.float32).reshape((-1,) + tuple(inp.shape[-3:])).contiguous()
     if not inplace or vols.data_ptr() != inp.data_ptr():
         vols = vols.clone()
     lib = L.load()
+    if dim == 2:
+        vols, orders, bounds = vols.reshape((1, -1) + tuple(inp.shape[-2:])), (0,) + tuple(orders[:2]), (0,) + tuple(bounds[:2])
     nx, ny, nz = vols.shape[-3:]
     for v in vols:
         for axis, n in enumerate((nx, ny, nz)):
@@ -416,43 +444,44 @@ def _coeff_raw(inp, orders, bounds, inplace):
                 n, inp.device, orders[axis], _PREFILTER_FAMILY[bounds[axis]])
             L.check(lib.bfm_bspline3_prefilter_axis(L.ptr(v), nx, ny, nz, axis, bounds[axis], z, gain, L.ptr(wd), pole_last,
                                                     init_scale, final_scale, max_iter, L.stream_ptr()), "bspline3_prefilter")
-    return vols.reshape(tuple(lead) + (nx, ny, nz))
+    return vols.reshape(inp.shape)
 
 
 class _SplineCoeffND(torch.autograd.Function):
     """autograd.py:276-300: the filter is symmetric, so its backward is the same filter applied to the gradient."""
 
     @staticmethod
-    def forward(ctx, x, orders, bounds):
-        ctx.opt = (orders, bounds, x.dtype)
-        return _coeff_raw(x, orders, bounds, False)
+    def forward(ctx, x, orders, bounds, dim=3):
+        ctx.opt = (orders, bounds, x.dtype, dim)
+        return _coeff_raw(x, orders, bounds, False, dim)
 
     @staticmethod
     def backward(ctx, grad):
-        orders, bounds, dtype = ctx.opt
-        return _coeff_raw(grad.contiguous(), orders, bounds, False).to(dtype), None, None
+        orders, bounds, dtype, dim = ctx.opt
+        return _coeff_raw(grad.contiguous(), orders, bounds, False, dim).to(dtype), None, None, None
 
 
 def spline_coeff_nd(input, interpolation="linear", bound="dct2", dim=None, inplace=False):
-    """utils/interpol/api.py:386-432 -> coeff.py:313-344 over the last three dimensions (`dim` None or 3): orders 2 and 3,
-    per axis if given as a list, under the DCT-I ('zero' / 'dct1'), DCT-II ('nearest' / 'dct2') or DFT ('dft') conditions;
-    an axis of order 0 / 1 or of length 1 is left as it is.  Differentiable (autograd.py:276-300); `inplace` holds only
-    for a tensor that needs no gradient."""
+    """utils/interpol/api.py:386-432 -> coeff.py:313-344 over the last three dimensions (`dim` None or 3) or the last two
+    (`dim` 2, which reads the first two orders and bounds): orders 2 and 3, per axis if given as a list, under the DCT-I
+    ('zero' / 'dct1'), DCT-II ('nearest' / 'dct2') or DFT ('dft') conditions; an axis of order 0 / 1 or of length 1 is
+    left as it is.  Differentiable (autograd.py:276-300); `inplace` holds only for a tensor that needs no gradient."""
     inp = input
     orders = _order_list(interpolation)
     bounds = tuple(_bound_list(bound))
     dim = 3 if dim is None else dim
-    if dim == 3:
-        _check_prefilter_bounds(orders, bounds, inp.shape[-3:])
+    if dim in (2, 3):
+        orders, bounds = orders[:dim], bounds[:dim]
+        _check_prefilter_bounds(orders, bounds, inp.shape[-dim:])
     if inp.device.type != "cuda":
         raise L.BfmError("spline_coeff_nd runs on a HIP device only")
     if all(o < 2 for o in orders):
         return inp if inplace else inp.clone()
-    if dim != 3:
-        raise NotImplementedError("only 3-D prefiltering is implemented")
+    if dim not in (2, 3) or inp.dim() < dim:
+        raise NotImplementedError("only 2-D and 3-D prefiltering is implemented")
     if torch.is_grad_enabled() and inp.requires_grad:
-        return _SplineCoeffND.apply(inp, orders, bounds)
-    return _coeff_raw(inp, orders, bounds, inplace)
+        return _SplineCoeffND.apply(inp, orders, bounds, dim)
+    return _coeff_raw(inp, orders, bounds, inplace, dim)
 
 
 def _coeff_axis_raw(inp, order, bound, dim):
@@ -542,7 +571,8 @@ def _affine_raw(mat, nb, shape, dtype, device):
 
 def identity_grid(shape, dtype=None, device=None):
     """api.py:455-476: the (*shape, dim) grid of voxel indices, dim = len(shape).  3-D shapes are written by one kernel
-    (no meshgrid); 1-D and 2-D shapes, which no kernel of this package reads, are built with torch on the device."""
+    (no meshgrid); 1-D and 2-D shapes are built with torch on the device (a 2-D grid is what grid_pull / grid_push /
+    grid_count take on spline_grid2d.hip; no kernel of this package reads a 1-D grid)."""
     shape = tuple(int(s) for s in shape)
     dtype = _builder_dtype(dtype)
     device = torch.device("cuda" if device is None else device)
@@ -637,7 +667,9 @@ def _anchor_coords(anchor, f, n_src, n_dst):
 def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilter=True, **kwargs):
     """utils/interpol/resize.py:13-119.  image: (..., X, Y, Z).  Cubic (interpolation=3) with extrapolation under the
     'nearest' / 'dct2' bounds runs as prefilter + three separable 4-tap passes; every other case (orders 0 to 3, any
-    bound, extrapolate=False) builds the grid and goes through grid_pull like the reference."""
+    bound, extrapolate=False) builds the grid and goes through grid_pull like the reference.  Two entries in `factor`,
+    `shape` or `anchor` (or none and an image (B, C, X, Y)) make it a 2-D resize of (..., X, Y), which always takes the
+    grid route, on the 2-D grid_pull."""
     orders = _order_list(kwargs.get("interpolation", interpolation))
     if image.device.type != "cuda":
         raise L.BfmError("resize runs on a HIP device only; there is no CPU fallback in the product path")
@@ -645,8 +677,8 @@ def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilte
     shape = _make_list(shape) if shape else []
     anchor = _make_list(anchor)
     nb_dim = max(len(factor), len(shape), len(anchor)) or (image.dim() - 2)
-    if nb_dim != 3:
-        raise NotImplementedError("only 3-D resize is implemented")
+    if nb_dim not in (2, 3):
+        raise NotImplementedError("only 2-D and 3-D resize is implemented")
     anchor = [a[0].lower() for a in _make_list(anchor, nb_dim)]
     inshape = image.shape[-nb_dim:]
     if factor:
@@ -662,12 +694,12 @@ def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilte
     lin = [_anchor_coords(anch, f, inshp, outshp) for anch, f, inshp, outshp in zip(anchor, factor, inshape, shape)]
     bound = kwargs.get("bound", "nearest")
     prefilter = kwargs.get("prefilter", prefilter)
-    if orders == _LINEAR:
+    if orders[:nb_dim] == _LINEAR[:nb_dim]:
         grid = torch.stack(torch.meshgrid(*[v.to(image.device) for v in lin], indexing="ij"), dim=-1)
         return grid_pull(image, grid, interpolation=1, bound=bound, extrapolate=kwargs.get("extrapolate", True))
     bl = _bound_list(bound)
     b = bl[0] if bl[0] in (1, 3) and bl == [bl[0]] * 3 else None           # the separable path: 'nearest' / 'dct2'
-    if orders != (3, 3, 3) or not kwargs.get("extrapolate", True) or b is None:
+    if nb_dim != 3 or orders != (3, 3, 3) or not kwargs.get("extrapolate", True) or b is None:
         # every case but the separable cubic one: build the grid and pull, like the reference (resize.py:111-117)
         grid = torch.stack(torch.meshgrid(*[v.to(image.device) for v in lin], indexing="ij"), dim=-1)
         return grid_pull(image, grid, interpolation=list(orders), bound=bound,

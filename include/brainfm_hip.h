@@ -638,6 +638,17 @@ int bfm_grid_push3d_spline(const float* inp, int Bi, int C, int ix, int iy, int 
 int bfm_grid_grad3d_spline(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox,
                            int oy, int oz, const int* bound, const int* order, int extrapolate, float* out,
                            bfm_stream_t stream);
+/* The same three on 2-D grids -> iso0.pull2d / push2d (iso0.py) for order {0,0}, iso1.pull2d / push2d / grad2d (iso1.py)
+ * for order {1,1}, nd.pull / nd.push / nd.grad (nd.py:30-290) for every other combination.  inp (Bi,C,nx,ny), grid
+ * (Bg,ox,oy,2), out (max(Bi,Bg),C,ox,oy), grad out (B,C,ox,oy,2); bound[2] and order[2] are read, checked as above.
+ * push: out MUST be zero on entry (fp32 atomics).  grad at order {1,1} takes iso1's slope (-1 / +1); a linear axis of a
+ * mixed-order call takes the sign of splines.py:93-97, as in 3-D.  Serves the autograd of grid_pull / grid_push. */
+int bfm_grid_pull2d_spline(const float* inp, int Bi, int C, int nx, int ny, const float* grid, int Bg, int ox, int oy,
+                           const int* bound, const int* order, int extrapolate, float* out, bfm_stream_t stream);
+int bfm_grid_push2d_spline(const float* inp, int Bi, int C, int ix, int iy, const float* grid, int Bg, int nx, int ny,
+                           const int* bound, const int* order, int extrapolate, float* out_zeroed, bfm_stream_t stream);
+int bfm_grid_grad2d_spline(const float* inp, int Bi, int C, int nx, int ny, const float* grid, int Bg, int ox, int oy,
+                           const int* bound, const int* order, int extrapolate, float* out, bfm_stream_t stream);
 /* interpol.grid_hess / grid_pushgrad, the two halves of the backward of grid_grad (utils/interpol/pushpull.py:176-233 and
  * :303-325) -> nd.hess / nd.pushgrad (nd.py:291-464), iso1.hess3d / pushgrad3d for order {1,1,1} (iso1.py:390-675) and
  * the zeros of iso0.hess / pushgrad for order {0,0,0} (iso0.py:326-368).  One export per operation takes every order and
