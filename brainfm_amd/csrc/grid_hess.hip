@@ -42,12 +42,12 @@ __global__ void __launch_bounds__(256) spline_hess3d(const float* __restrict__ i
     const int64_t n = (int64_t)B * nout;
     const int64_t vol = (int64_t)nx * ny * nz;
     GRID_STRIDE(i, n) {
-        const GridVoxel p = grid_voxel(i, nout, grid, Bg, nx, ny, nz, op.extrap);
+        const GridPoint<3> p = grid_point<3>(i, nout, grid, Bg, GridDims<3>{{nx, ny, nz}}, op.extrap);
         int ix[T], iy[T], iz[T];
         float wx[T], wy[T], wz[T], dx[T], dy[T], dz[T], hx[T], hy[T], hz[T];
-        axis_nodes<T, 2, O == 1>(p.gx, ox, nx, op.bound[0], ix, wx, dx, hx);
-        axis_nodes<T, 2, O == 1>(p.gy, oy, ny, op.bound[1], iy, wy, dy, hy);
-        axis_nodes<T, 2, O == 1>(p.gz, oz, nz, op.bound[2], iz, wz, dz, hz);
+        axis_nodes<T, 2, O == 1>(p.g[0], ox, nx, op.bound[0], ix, wx, dx, hx);
+        axis_nodes<T, 2, O == 1>(p.g[1], oy, ny, op.bound[1], iy, wy, dy, hy);
+        axis_nodes<T, 2, O == 1>(p.g[2], oz, nz, op.bound[2], iz, wz, dz, hz);
         float c0 = 0.f, c1 = 0.f, c2 = 0.f;              // the contraction, summed over the channels
         for (int c = 0; c < C; ++c) {
             const float* src = inp + ((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * vol;
@@ -105,13 +105,13 @@ __global__ void __launch_bounds__(256) spline_pushgrad3d(const float* __restrict
     const int64_t n = (int64_t)B * nin;
     const int64_t vol = (int64_t)nx * ny * nz;
     GRID_STRIDE(i, n) {
-        const GridVoxel p = grid_voxel(i, nin, grid, Bg, nx, ny, nz, op.extrap);
+        const GridPoint<3> p = grid_point<3>(i, nin, grid, Bg, GridDims<3>{{nx, ny, nz}}, op.extrap);
         if (p.mask == 0.f) continue;
         int ix[T], iy[T], iz[T];
         float wx[T], wy[T], wz[T], dx[T], dy[T], dz[T];
-        axis_nodes<T, 1, O == 1>(p.gx, ox, nx, op.bound[0], ix, wx, dx);
-        axis_nodes<T, 1, O == 1>(p.gy, oy, ny, op.bound[1], iy, wy, dy);
-        axis_nodes<T, 1, O == 1>(p.gz, oz, nz, op.bound[2], iz, wz, dz);
+        axis_nodes<T, 1, O == 1>(p.g[0], ox, nx, op.bound[0], ix, wx, dx);
+        axis_nodes<T, 1, O == 1>(p.g[1], oy, ny, op.bound[1], iy, wy, dy);
+        axis_nodes<T, 1, O == 1>(p.g[2], oz, nz, op.bound[2], iz, wz, dz);
         for (int c = 0; c < C; ++c) {
             const float* t = inp + (((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * nin + p.v) * 3;
             const float tx = t[0], ty = t[1], tz = t[2];
@@ -145,16 +145,17 @@ static int launch_hess(const int* order, int64_t n, F&& launch) {
 extern "C" int bfm_grid_hess3d(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg, int ox,
                                int oy, int oz, const int* bound, const int* order, int extrapolate, const float* cot,
                                float* out, bfm_stream_t stream) {
-    const int rc = grid_check_args(inp, grid, out, bound, order, Bi, Bg, C, nx, ny, nz, ox, oy, oz, extrapolate);
+    const GridDims<3> in{{nx, ny, nz}}, og{{ox, oy, oz}};
+    const int rc = grid_check_args(3, inp, grid, out, bound, order, Bi, Bg, C, in.n, og.n, extrapolate);
     if (rc != BFM_OK) return rc;
     const int B = Bi > Bg ? Bi : Bg;
-    const int64_t nout = (int64_t)ox * oy * oz;
+    const int64_t nout = og.count();
     if (iso_order(order) == 0) {                         // iso0.py:353-368: zeros
         const size_t count = (size_t)B * nout * (cot ? 3 : (size_t)C * 9);
         if (hipMemsetAsync(out, 0, count * sizeof(float), bfm_s(stream)) != hipSuccess) return BFM_E_LAUNCH;
         return bfm_launch_status();
     }
-    const GridOpts op = grid_opts(bound, order, extrapolate);
+    const GridOpts op = grid_opts(3, bound, order, extrapolate);
     return launch_hess(order, B * nout, [&](auto o, dim3 gr, dim3 bl) {
         hipLaunchKernelGGL(spline_hess3d<decltype(o)::value>, gr, bl, 0, bfm_s(stream), inp, Bi, C, nx, ny, nz, grid, Bg,
                            nout, op, B, cot, out);
@@ -164,12 +165,13 @@ extern "C" int bfm_grid_hess3d(const float* inp, int Bi, int C, int nx, int ny, 
 extern "C" int bfm_grid_pushgrad3d(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg,
                                    int nx, int ny, int nz, const int* bound, const int* order, int extrapolate,
                                    float* out_zeroed, bfm_stream_t stream) {
-    const int rc = grid_check_args(inp, grid, out_zeroed, bound, order, Bi, Bg, C, ix, iy, iz, nx, ny, nz, extrapolate);
+    const GridDims<3> in{{ix, iy, iz}}, vol{{nx, ny, nz}};
+    const int rc = grid_check_args(3, inp, grid, out_zeroed, bound, order, Bi, Bg, C, in.n, vol.n, extrapolate);
     if (rc != BFM_OK) return rc;
     if (iso_order(order) == 0) return BFM_OK;            // iso0.py:326-349: zeros, which the caller has written
     const int B = Bi > Bg ? Bi : Bg;
-    const int64_t nin = (int64_t)ix * iy * iz;
-    const GridOpts op = grid_opts(bound, order, extrapolate);
+    const int64_t nin = in.count();
+    const GridOpts op = grid_opts(3, bound, order, extrapolate);
     return launch_hess(order, B * nin, [&](auto o, dim3 gr, dim3 bl) {
         hipLaunchKernelGGL(spline_pushgrad3d<decltype(o)::value>, gr, bl, 0, bfm_s(stream), inp, Bi, C, grid, Bg, nin, nx,
                            ny, nz, op, B, out_zeroed);

@@ -1,5 +1,5 @@
-// Boundary rules of the interpol grid kernels (utils/interpol/bounds.py:24-89), shared by the linear kernels of
-// synth_interp.hip and the spline kernels of spline_grid.hip: where an out-of-range node index lands (bound_index) and
+// Boundary rules of the interpol grid kernels (utils/interpol/bounds.py:24-89), shared by the linear and
+// the spline kernels of spline_grid.hip, grid_hess.hip and label_pull.hip: where an out-of-range node index lands (bound_index) and
 // the sign its value takes (bound_sign).  b: 0 zero, 1 replicate, 2 dct1, 3 dct2, 4 dst1, 5 dst2, 6 dft (bounds.py:8-15).
 // For every b in 0..6 and |i| <= 2^30, bound_index returns an index in [0, n-1].
 #pragma once

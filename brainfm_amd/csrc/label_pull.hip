@@ -61,12 +61,12 @@ __global__ void __launch_bounds__(256) label_pull3d_regs(const LT* __restrict__ 
     const int64_t n = (int64_t)B * nout;
     const int64_t vol = (int64_t)nx * ny * nz;
     GRID_STRIDE(i, n) {
-        const GridVoxel p = grid_voxel(i, nout, grid, Bg, nx, ny, nz, op.extrap);
+        const GridPoint<3> p = grid_point<3>(i, nout, grid, Bg, GridDims<3>{{nx, ny, nz}}, op.extrap);
         int ix[T], iy[T], iz[T];
         float wx[T], wy[T], wz[T];
-        axis_nodes<T>(p.gx, ox, nx, op.bound[0], ix, wx);
-        axis_nodes<T>(p.gy, oy, ny, op.bound[1], iy, wy);
-        axis_nodes<T>(p.gz, oz, nz, op.bound[2], iz, wz);
+        axis_nodes<T>(p.g[0], ox, nx, op.bound[0], ix, wx);
+        axis_nodes<T>(p.g[1], oy, ny, op.bound[1], iy, wy);
+        axis_nodes<T>(p.g[2], oz, nz, op.bound[2], iz, wz);
         for (int c = 0; c < C; ++c) {
             LT* dst = out + ((int64_t)p.b * C + c) * nout + p.v;
             if (p.mask == 0.f) { *dst = (LT)0; continue; }
@@ -112,11 +112,11 @@ __global__ void __launch_bounds__(64) label_pull3d_lds(const LT* __restrict__ in
     const int64_t n = (int64_t)B * nout;
     const int64_t vol = (int64_t)nx * ny * nz;
     GRID_STRIDE(i, n) {
-        const GridVoxel p = grid_voxel(i, nout, grid, Bg, nx, ny, nz, op.extrap);
+        const GridPoint<3> p = grid_point<3>(i, nout, grid, Bg, GridDims<3>{{nx, ny, nz}}, op.extrap);
         int iy[T], iz[T];                                          // the x nodes: axis_node, slab by slab
         float wy[T], wz[T];
-        axis_nodes<T>(p.gy, oy, ny, op.bound[1], iy, wy);
-        axis_nodes<T>(p.gz, oz, nz, op.bound[2], iz, wz);
+        axis_nodes<T>(p.g[1], oy, ny, op.bound[1], iy, wy);
+        axis_nodes<T>(p.g[2], oz, nz, op.bound[2], iz, wz);
         for (int c = 0; c < C; ++c) {
             LT* dst = out + ((int64_t)p.b * C + c) * nout + p.v;
             if (p.mask == 0.f) { *dst = (LT)0; continue; }
@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(64) label_pull3d_lds(const LT* __restrict__ in
             for (int a = 0; a < T; ++a) {                          // rolled: one x-slab of the footprint at a time
                 int ixa;
                 float wxa;
-                axis_node(p.gx, ox, nx, op.bound[0], a, ixa, wxa);
+                axis_node(p.g[0], ox, nx, op.bound[0], a, ixa, wxa);
                 K lab[T * T];                                      // its loads go out together
 #pragma unroll
                 for (int bb = 0; bb < T; ++bb) {
@@ -183,11 +183,11 @@ __global__ void __launch_bounds__(256) label_pull3d_passes(const LT* __restrict_
     const int64_t n = (int64_t)B * nout;
     const int64_t vol = (int64_t)nx * ny * nz;
     GRID_STRIDE(i, n) {
-        const GridVoxel p = grid_voxel(i, nout, grid, Bg, nx, ny, nz, op.extrap);
+        const GridPoint<3> p = grid_point<3>(i, nout, grid, Bg, GridDims<3>{{nx, ny, nz}}, op.extrap);
         int iy[T], iz[T];                                          // the x nodes: axis_node, slab by slab
         float wy[T], wz[T];
-        axis_nodes<T>(p.gy, oy, ny, op.bound[1], iy, wy);
-        axis_nodes<T>(p.gz, oz, nz, op.bound[2], iz, wz);
+        axis_nodes<T>(p.g[1], oy, ny, op.bound[1], iy, wy);
+        axis_nodes<T>(p.g[2], oz, nz, op.bound[2], iz, wz);
         for (int c = 0; c < C; ++c) {
             LT* dst = out + ((int64_t)p.b * C + c) * nout + p.v;
             if (p.mask == 0.f) { *dst = (LT)0; continue; }
@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(256) label_pull3d_passes(const LT* __restrict_
                 for (int a = 0; a < T; ++a) {                      // rolled: one x-slab of the footprint at a time
                     int ixa;
                     float wxa;
-                    axis_node(p.gx, ox, nx, op.bound[0], a, ixa, wxa);
+                    axis_node(p.g[0], ox, nx, op.bound[0], a, ixa, wxa);
                     K lab[T * T];
 #pragma unroll
                     for (int bb = 0; bb < T; ++bb) {
@@ -301,13 +301,14 @@ void launch_dtype(int variant, hipStream_t s, const void* inp, int Bi, int C, in
 extern "C" int bfm_label_pull3d(const void* inp, int dtype, int Bi, int C, int nx, int ny, int nz, const float* grid, int Bg,
                                 int ox, int oy, int oz, const int* bound, const int* order, int extrapolate, int variant,
                                 void* out, bfm_stream_t stream) {
-    const int rc = grid_check_args(inp, grid, out, bound, order, Bi, Bg, C, nx, ny, nz, ox, oy, oz, extrapolate);
+    const GridDims<3> in{{nx, ny, nz}}, og{{ox, oy, oz}};
+    const int rc = grid_check_args(3, inp, grid, out, bound, order, Bi, Bg, C, in.n, og.n, extrapolate);
     if (rc != BFM_OK) return rc;
     if (dtype < BFM_LABEL_U8 || dtype > BFM_LABEL_I64) return BFM_E_ARG;
     if (variant < BFM_LABEL_PULL_AUTO || variant > BFM_LABEL_PULL_PASSES) return BFM_E_ARG;
     const int B = Bi > Bg ? Bi : Bg;
-    const int64_t nout = (int64_t)ox * oy * oz;
-    const GridOpts op = grid_opts(bound, order, extrapolate);
+    const int64_t nout = og.count();
+    const GridOpts op = grid_opts(3, bound, order, extrapolate);
     hipStream_t s = bfm_s(stream);
     switch (dtype) {
         case BFM_LABEL_U8: launch_dtype<uint8_t>(variant, s, inp, Bi, C, nx, ny, nz, grid, Bg, nout, op, B, out); break;

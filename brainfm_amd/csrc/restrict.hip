@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(256) axis_table_kernel(const float* __restrict
         if (rowptr) rowptr[i] = i * T;
         if (i == m) break;
         const float g = coord[i];
-        const float mask = inbounds(g, 0.f, 0.f, n, 1, 1, extrap);          // this axis alone: 0 is inside a length of 1
+        const float mask = inbounds<1>(&g, &n, extrap);                       // this axis alone
         int idx[4];
         float w[4];
         axis_nodes<4>(g, order, n, bound, idx, w);

@@ -78,21 +78,14 @@ __device__ __forceinline__ void axis_nodes(float g, int order, int n, int b, int
         axis_node<D, ISO1>(g, order, n, b, k, idx[k], w[k], D >= 1 ? dw + k : nullptr, D >= 2 ? d2w + k : nullptr);
 }
 
-__device__ __forceinline__ float inbounds(float gx, float gy, float gz, int nx, int ny, int nz, int extrap) {
+// the inbounds mask of a coordinate g[0..D) against the extents n[0..D): 1 inside, 0 outside
+template <int D>
+__device__ __forceinline__ float inbounds(const float* g, const int* n, int extrap) {
     if (extrap == 0 || extrap == 2) {
         const float thr = extrap == 2 ? 0.5f + 5e-2f : 5e-2f;
-        const bool in = (gx > -thr) && (gx < (float)(nx - 1) + thr) && (gy > -thr) && (gy < (float)(ny - 1) + thr) &&
-                        (gz > -thr) && (gz < (float)(nz - 1) + thr);
-        return in ? 1.f : 0.f;
-    }
-    return 1.f;
-}
-
-// the same mask over the two axes of a 2-D grid
-__device__ __forceinline__ float inbounds(float gx, float gy, int nx, int ny, int extrap) {
-    if (extrap == 0 || extrap == 2) {
-        const float thr = extrap == 2 ? 0.5f + 5e-2f : 5e-2f;
-        const bool in = (gx > -thr) && (gx < (float)(nx - 1) + thr) && (gy > -thr) && (gy < (float)(ny - 1) + thr);
+        bool in = true;
+#pragma unroll
+        for (int a = 0; a < D; ++a) in = in && (g[a] > -thr) && (g[a] < (float)(n[a] - 1) + thr);
         return in ? 1.f : 0.f;
     }
     return 1.f;

@@ -2,14 +2,14 @@
 ``grid_grad`` for spline orders 0 to 3, any order per axis, in 3-D (utils/interpol/api.py:137-335, autograd.py:125-245,
 pushpull.py:35-282), ``resize`` (resize.py:13-119) and ``restrict`` (restrict.py:9-122; separable axis passes on
 restrict.hip, which also give the separable cubic ``resize`` its gradient).  All-linear calls run ``iso1``
-(iso1.py:28-387) on the kernels of synth_interp.hip; every other combination runs the generic path (nd.py:30-290,
-splines.py:30-103, bounds.py:24-89) on spline_grid.hip.  ``prefilter`` goes through ``spline_coeff_nd``
-(coeff.py:254-344), which is differentiable (autograd.py:276-300).
+(iso1.py:28-387) on the linear kernels of spline_grid.hip; every other combination runs the generic path (nd.py:30-290,
+splines.py:30-103, bounds.py:24-89) on the dimension-generic kernels of the same file.  ``prefilter`` goes through
+``spline_coeff_nd`` (coeff.py:254-344), which is differentiable (autograd.py:276-300).
 
 ``grid_pull`` / ``grid_push`` / ``grid_count`` of a floating-point image, ``spline_coeff_nd`` and ``resize`` also take
-2-D grids (..., X, Y, 2) on spline_grid2d.hip, differentiable to first order like their 3-D forms; there every order,
-the all-linear one included, is an instantiation of one kernel.  Label maps, ``grid_grad`` / ``grid_hess`` /
-``grid_pushgrad`` and ``restrict`` are 3-D only, and 1-D grids raise everywhere.
+2-D grids (..., X, Y, 2) on the 2-D instantiations of spline_grid.hip, differentiable to first order like their 3-D
+forms; there every order, the all-linear one included, is an instantiation of one kernel.  Label maps, ``grid_grad`` /
+``grid_hess`` / ``grid_pushgrad`` and ``restrict`` are 3-D only, and 1-D grids raise everywhere.
 
 grid_pull / grid_push are differentiable to first order through grid_push / grid_grad, and grid_grad through
 ``grid_pushgrad`` and ``grid_hess`` (pushpull.py:176-233 and :303-325; nd.py:291-464, iso1.py:390-675, iso0.py:326-368)
@@ -127,8 +127,8 @@ def _export(name, x, g, dims, b, o, ext, extra, out):
 
 
 def _linear_or_spline(op, o, dim=3):
-    """3-D: all-linear calls run iso1 on the kernels of synth_interp.hip, every other combination the generic path.
-    2-D: every order is an instantiation of spline_grid2d.hip."""
+    """3-D: all-linear calls run iso1 on the linear kernels of spline_grid.hip, every other combination the generic path.
+    2-D: every order is an instantiation of the generic kernels."""
     if dim == 2:
         return "grid_%s2d_spline" % op, o
     return ("grid_%s3d_linear" % op, None) if o == _LINEAR else ("grid_%s3d_spline" % op, o)
@@ -369,16 +369,13 @@ def grid_pull(input, grid, interpolation="linear", bound="zero", extrapolate=Fal
     label map: the result has its dtype and holds the label with the largest interpolated weight (_label_pull); label
     maps are pulled through 3-D grids only.  On a 2-D grid the first two of the orders and bounds are read."""
     b, o, ext = _opts(interpolation, bound, extrapolate)
-    dim = grid.shape[-1]
-    if dim != 3 and not input.dtype.is_floating_point:
-        raise NotImplementedError("only 3-D grids are on the hot path")
-    if dim not in (2, 3) or (dim == 2 and grid.dim() < 3):
-        raise NotImplementedError("only 2-D and 3-D grids are on the hot path")
     if not input.dtype.is_floating_point:
+        if grid.shape[-1] != 3:
+            raise NotImplementedError("only 3-D grids are on the hot path")
         return _label_pull(input, grid, b, o, ext, prefilter)
+    dim = _grid_dim(grid, "grid_pull")
     prefilter = _needs_prefilter(prefilter, o[:dim], list(b)[:dim], input.shape[-dim:])
-    if input.device.type != "cuda":
-        raise L.BfmError("grid_pull runs on a HIP device only; there is no CPU fallback in the product path")
+    _require_cuda(input, "grid_pull")
     if prefilter:
         input = spline_coeff_nd(input, interpolation=list(o), bound=bound, dim=dim)
     x, g, (batch, channel, in_spatial, grid_spatial) = _prep(input, grid, dim)
@@ -572,7 +569,7 @@ def _affine_raw(mat, nb, shape, dtype, device):
 def identity_grid(shape, dtype=None, device=None):
     """api.py:455-476: the (*shape, dim) grid of voxel indices, dim = len(shape).  3-D shapes are written by one kernel
     (no meshgrid); 1-D and 2-D shapes are built with torch on the device (a 2-D grid is what grid_pull / grid_push /
-    grid_count take on spline_grid2d.hip; no kernel of this package reads a 1-D grid)."""
+    grid_count take on spline_grid.hip; no kernel of this package reads a 1-D grid)."""
     shape = tuple(int(s) for s in shape)
     dtype = _builder_dtype(dtype)
     device = torch.device("cuda" if device is None else device)
@@ -694,16 +691,15 @@ def resize(image, factor=None, shape=None, anchor="c", interpolation=1, prefilte
     lin = [_anchor_coords(anch, f, inshp, outshp) for anch, f, inshp, outshp in zip(anchor, factor, inshape, shape)]
     bound = kwargs.get("bound", "nearest")
     prefilter = kwargs.get("prefilter", prefilter)
-    if orders[:nb_dim] == _LINEAR[:nb_dim]:
-        grid = torch.stack(torch.meshgrid(*[v.to(image.device) for v in lin], indexing="ij"), dim=-1)
-        return grid_pull(image, grid, interpolation=1, bound=bound, extrapolate=kwargs.get("extrapolate", True))
     bl = _bound_list(bound)
     b = bl[0] if bl[0] in (1, 3) and bl == [bl[0]] * 3 else None           # the separable path: 'nearest' / 'dct2'
     if nb_dim != 3 or orders != (3, 3, 3) or not kwargs.get("extrapolate", True) or b is None:
-        # every case but the separable cubic one: build the grid and pull, like the reference (resize.py:111-117)
+        # every case but the separable cubic one: build the grid and pull, like the reference (resize.py:111-117).  Below
+        # order 2 there is nothing to prefilter, and the flag is dropped here, so that a label map still resizes at those
+        # orders (grid_pull refuses a label map with prefilter=True)
         grid = torch.stack(torch.meshgrid(*[v.to(image.device) for v in lin], indexing="ij"), dim=-1)
-        return grid_pull(image, grid, interpolation=list(orders), bound=bound,
-                         extrapolate=kwargs.get("extrapolate", True), prefilter=prefilter)
+        return grid_pull(image, grid, interpolation=list(orders), bound=bound, extrapolate=kwargs.get("extrapolate", True),
+                         prefilter=prefilter and any(o >= 2 for o in orders[:nb_dim]))
     coeff = spline_coeff_nd(image, interpolation=3, bound=b, dim=3) if prefilter else image.to(torch.float32)
     lead = coeff.shape[:-3]
     vols = coeff.reshape((-1,) + tuple(coeff.shape[-3:])).contiguous()

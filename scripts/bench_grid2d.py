@@ -1,6 +1,6 @@
-"""Cold kernel times of interpol grid_pull / grid_push on a 2-D grid (spline_grid2d.hip) beside the same call embedded
-in 3-D -- image (X, Y, 1), a third coordinate 0, orders (ox, oy, 0) -- on the 3-D kernels of spline_grid.hip, at 2048 x 2048
-with one channel, bound dct2, extrapolate on.  The protocol of bench_spline_grid.py: before every timed launch a 1 GiB
+"""Cold kernel times of interpol grid_pull / grid_push on a 2-D grid (the D = 2 instantiations of spline_grid.hip)
+beside the same call embedded in 3-D -- image (X, Y, 1), a third coordinate 0, orders (ox, oy, 0) -- on the D = 3
+instantiations of the same kernels, at 2048 x 2048 with one channel, bound dct2, extrapolate on.  The protocol of bench_spline_grid.py: before every timed launch a 1 GiB
 buffer is overwritten, one launch between two HIP events, median (min .. max) of 9.  Two grids: the identity plus a
 smooth displacement (1.5 pixels times a sine of period 40 pixels) and the identity plus a uniform jitter of +-1.5 pixels.
 

@@ -6,8 +6,8 @@ uniform +-1.5 voxels per voxel.
 
 Two comparisons are the yardsticks.  The contracted backward (the Hessian times the incoming gradient, formed in the
 kernel) against materialising the Hessian with the same kernel and reducing it in torch, which is the reference's
-algorithm (pushpull.py:322-324).  grid_pushgrad against grid_push at the same order and grid (spline_grid.hip /
-synth_interp.hip, which this file's kernels do not touch): the same atomics, 8 more bytes read per voxel.
+algorithm (pushpull.py:322-324).  grid_pushgrad against grid_push at the same order and grid (spline_grid.hip,
+which this file's kernels do not touch): the same atomics, 8 more bytes read per voxel.
 
 usage: python scripts/bench_grid_hess.py [output file]   (profiles/grid_hess.txt holds a run)"""
 import os

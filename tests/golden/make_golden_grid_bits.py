@@ -12,7 +12,15 @@ Regenerate it only from a commit whose kernels are known good; the cases are in 
   big/sha              SHA-256 of the outputs of the two 130^3 launches that take the grid-stride loop
   atomic/*             push / pushgrad of 8 source voxels into 16^3.  fp32 atomics commute only up to two addends per
                        address, (0 + a) + b = (0 + b) + a, so the coordinates are checked against that cap on the CPU
-                       first (grid_bits_cases.max_addends) and nothing is written if a case breaks it."""
+                       first (grid_bits_cases.max_addends) and nothing is written if a case breaks it.
+
+python tests/golden/make_golden_grid_bits.py nd -> grid_nd_bits.npz, made from the kernels as they stood before the 2-D
+and the 3-D kernels became one dimension-generic set.  It reads its inputs from grid_family_bits.npz and draws nothing.
+
+  cases2d              names of the 2-D cases; pull2d / grad2d hold one entry per case
+  atomic2d/*           push of 8 source pixels into 16^2, under the same two-addend cap
+  lin3d/*              pull / grad of the all-linear 3-D exports under the two batch broadcasts
+  big/*                SHA-256 of the all-linear pull at 130^3 (a second grid-stride round)"""
 import os
 import sys
 
@@ -54,5 +62,33 @@ def main():
         print("  %-16s %s  non-zero %.3f  finite %s" % (k, d[k].shape, float((d[k] != 0).mean()), bool(np.isfinite(d[k]).all())))
 
 
+def main_nd():
+    """grid_nd_bits.npz: the 2-D kernels and the gaps of the all-linear 3-D ones, on the inputs grid_family_bits.npz holds"""
+    import torch
+    from brainfm_amd import interpol as IP
+    out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(HERE, "grid_nd_bits.npz")
+    d = dict(np.load(os.path.join(HERE, "grid_family_bits.npz")))
+    GB.check_two_addends2(d)                             # raises: no file for coordinates that break the cap
+    out = {}
+    cases = GB.det2_cases()
+    res = [GB.run_det2_case(IP, torch, d, c) for c in cases]
+    out["cases2d"] = np.array([c[0] for c in cases])
+    out["pull2d"], out["grad2d"] = (np.stack([r[i] for r in res]) for i in (0, 1))
+    atomics = GB.atomic2_cases()
+    out["atomic2d/names"] = np.array([c[0] for c in atomics])
+    out["atomic2d/push"] = np.stack([GB.run_atomic2_case(IP, torch, d, c) for c in atomics])
+    lres = [GB.run_lin3_case(IP, torch, d, c) for c in GB.LIN3_CASES]
+    out["lin3d/names"] = np.array([c[0] for c in GB.LIN3_CASES])
+    out["lin3d/pull"], out["lin3d/grad"] = (np.stack([r[i] for r in lres]) for i in (0, 1))
+    out["big/names"] = np.array(GB.BIG2_CASES)
+    out["big/sha"] = GB.run_big2(IP, torch)
+    torch.cuda.synchronize()
+    np.savez_compressed(out_path, **out)
+    print("%s: %d keys, %d bytes" % (out_path, len(out), os.path.getsize(out_path)))
+    for k in ("pull2d", "grad2d", "atomic2d/push", "lin3d/pull", "lin3d/grad"):
+        print("  %-16s %s  non-zero %.3f  finite %s" % (k, out[k].shape, float((out[k] != 0).mean()),
+                                                       bool(np.isfinite(out[k]).all())))
+
+
 if __name__ == "__main__":
-    main()
+    main_nd() if sys.argv[1:2] == ["nd"] else main()

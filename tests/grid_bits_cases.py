@@ -1,7 +1,8 @@
 """The cases of tests/golden/grid_family_bits.npz: the bits of the interpol grid kernels (spline_grid.hip, grid_hess.hip,
 label_pull.hip, the axis tables of restrict.hip) as they stood before their shared layer was factored out.  The generator
 (tests/golden/make_golden_grid_bits.py) and the tests (test_gpu_grid_bits.py, test_host_grid_bits.py) both take the
-inputs, the case lists and the calls from here, so what was stored and what is compared cannot drift apart.
+inputs, the case lists and the calls from here, so what was stored and what is compared cannot drift apart.  The second
+half of the file holds the cases of tests/golden/grid_nd_bits.npz in the same way.
 
 Only names that the refactor keeps are used: the C exports and IP._opts / _order_list / _pull_raw / _grad_raw / _hess_raw /
 _push_raw / _pushgrad_raw / _label_pull_raw / _axis_table.
@@ -9,6 +10,7 @@ _push_raw / _pushgrad_raw / _label_pull_raw / _axis_table.
 Bounds: 0 zero, 1 replicate, 2 dct1, 3 dct2, 4 dst1, 5 dst2, 6 dft.  extrapolate: 0 no, 1 yes, 2 hist."""
 import ctypes as C
 import hashlib
+import itertools
 
 import numpy as np
 
@@ -128,22 +130,23 @@ def big_inputs():
 
 # ------------------------------------------------------------------------------- the two-addend cap of the atomic cases
 def max_addends(grid, shape, orders, bound):
-    """The largest number of atomic adds that any address of `shape` can receive from the source voxels at `grid`
-    (1, ..., 3): every node of every voxel's footprint that the bound does not drop (sign != 0) counts, whatever its
-    weight, with the node indices of the float64 restatement.  A cap, not a measurement."""
-    g = np.asarray(grid, np.float64).reshape(-1, 3)
+    """The largest number of atomic adds that any address of `shape` (2 or 3 extents) can receive from the source voxels
+    at `grid` (1, ..., len(shape)): every node of every voxel's footprint that the bound does not drop (sign != 0) counts,
+    whatever its weight, with the node indices of the float64 restatement.  A cap, not a measurement."""
+    dim = len(shape)
+    g = np.asarray(grid, np.float64).reshape(-1, dim)
     ax = []
-    for a in range(3):
+    for a in range(dim):
         g0 = np.floor(g[:, a] - (orders[a] - 1) / 2).astype(np.int64)
         nodes = np.stack([g0 + k for k in range(orders[a] + 1)])
         ax.append((SR.bound_index(nodes, shape[a], bound), SR.bound_sign(nodes, shape[a], bound) != 0))
     count = np.zeros(int(np.prod(shape)), np.int64)
-    for a in range(orders[0] + 1):
-        for b in range(orders[1] + 1):
-            for c in range(orders[2] + 1):
-                live = ax[0][1][a] & ax[1][1][b] & ax[2][1][c]
-                lin = (ax[0][0][a] * shape[1] + ax[1][0][b]) * shape[2] + ax[2][0][c]
-                np.add.at(count, lin[live], 1)
+    for taps in itertools.product(*[range(orders[a] + 1) for a in range(dim)]):
+        live, lin = True, 0
+        for a, k in enumerate(taps):
+            live = live & ax[a][1][k]
+            lin = lin * shape[a] + ax[a][0][k]
+        np.add.at(count, lin[live], 1)
     return int(count.max())
 
 
@@ -152,6 +155,107 @@ def check_two_addends(d):
         m = max_addends(d["atomic/grid_b%d" % b], ATOMIC_SHAPE, o, b)
         if m > 2:
             raise ValueError("%s: an address receives %d addends; the sum would depend on their order" % (name, m))
+
+
+# ------------------------------------------------------------------------- the second fixture: tests/golden/grid_nd_bits.npz
+# What grid_family_bits.npz does not pin, taken from the kernels as they stood before the 2-D and the 3-D kernels became
+# one dimension-generic set: pull / grad / push on 2-D grids, the two batch broadcasts of the all-linear 3-D kernels and
+# their second grid-stride round.  Every input is one of the first fixture's (`d` below is that fixture): nothing is drawn.
+ORDERS2 = [(0, 0), (1, 1), (2, 2), (3, 3), (3, 1), (0, 2)]
+ATOMIC_SHAPE2 = (16, 16)
+BIG2_CASES = ("big/pull_o111",)
+LIN3_CASES = (("o111/b036_e1/Bi1", 1, 2), ("o111/b036_e1/Bg1", 2, 1))
+
+
+def otag2(o):
+    return "o%d%d" % tuple(o)
+
+
+def _pad3(v):
+    """two per-axis values -> the three an export reads its first two of, padded with the last like IP._opts pads"""
+    return tuple(v) + (v[-1],)
+
+
+def inputs2d(d):
+    """image (2,2,5,6): the first slice of in/vol along z; grid (2,6,5,2): the x and y coordinates of in/grid, which keeps
+    the integer and half-integer ties against nx = 5, ny = 6"""
+    return np.ascontiguousarray(d["in/vol"][..., 0]), np.ascontiguousarray(d["in/grid"][..., :2]).reshape(2, 6, 5, 2)
+
+
+def det2_cases():
+    """(name, orders, bounds, ext, Bi, Bg): every 2-D order under the first two bounds of every configuration, then one
+    broadcast each way"""
+    out = [("%s/b%d%d_e%d" % ((otag2(o),) + b[:2] + (e,)), o, b[:2], e, 2, 2) for o in ORDERS2 for b, e in CONFIGS]
+    out.append(("o31/b03_e1/Bi1", (3, 1), (0, 3), 1, 1, 2))
+    out.append(("o31/b03_e1/Bg1", (3, 1), (0, 3), 1, 2, 1))
+    return out
+
+
+def run_det2_case(IP, torch, d, case):
+    """-> pull (B,C,6,5), grad (B,C,6,5,2).  Bi == Bg goes through the _raw wrappers, a broadcast through the exports."""
+    from brainfm_amd import _lib as L
+    name, o, b, ext, Bi, Bg = case
+    vol, grid = inputs2d(d)
+    x, g = _dev(vol[:Bi], torch), _dev(grid[:Bg], torch)
+    if Bi == Bg:
+        res = IP._pull_raw(x, g, _c3(_pad3(b)), _pad3(o), ext), IP._grad_raw(x, g, _c3(_pad3(b)), _pad3(o), ext)
+    else:
+        B, Cc, gs = max(Bi, Bg), x.shape[1], tuple(g.shape[1:3])
+        lib = L.load()
+        head = (L.ptr(x), Bi, Cc, x.shape[2], x.shape[3], L.ptr(g), Bg, gs[0], gs[1], _c3(_pad3(b)), _c3(_pad3(o)), ext)
+        pull = torch.empty((B, Cc) + gs, dtype=torch.float32, device=x.device)
+        grad = torch.empty((B, Cc) + gs + (2,), dtype=torch.float32, device=x.device)
+        L.check(lib.bfm_grid_pull2d_spline(*head, L.ptr(pull), L.stream_ptr()), "pull2d")
+        L.check(lib.bfm_grid_grad2d_spline(*head, L.ptr(grad), L.stream_ptr()), "grad2d")
+        res = pull, grad
+    return res[0].cpu().numpy(), res[1].cpu().numpy()
+
+
+def atomic2_inputs(d, bound):
+    """source (1,2,2,4) and grid (1,2,4,2): the 8 source voxels of the 3-D atomic cases with their x and y coordinates"""
+    return (d["atomic/src"].reshape(1, 2, 2, 4),
+            np.ascontiguousarray(d["atomic/grid_b%d" % bound][..., :2]).reshape(1, 2, 4, 2))
+
+
+def atomic2_cases():
+    """(name, orders, bound): 8 source pixels, C = 2, into 16^2, extrapolate 1"""
+    return [("%s/b%d" % (otag2(o), b), o, b) for b in ATOMIC_BOUNDS for o in ORDERS2]
+
+
+def check_two_addends2(d):
+    for name, o, b in atomic2_cases():
+        m = max_addends(atomic2_inputs(d, b)[1], ATOMIC_SHAPE2, o, b)
+        if m > 2:
+            raise ValueError("%s: an address receives %d addends; the sum would depend on their order" % (name, m))
+
+
+def run_atomic2_case(IP, torch, d, case):
+    name, o, b = case
+    src, grid = atomic2_inputs(d, b)
+    return IP._push_raw(_dev(src, torch), _dev(grid, torch), ATOMIC_SHAPE2, _c3((b, b, b)), _pad3(o), 1).cpu().numpy()
+
+
+def run_lin3_case(IP, torch, d, case):
+    """The all-linear 3-D exports under a batch broadcast, which the _raw wrappers do not take: bounds (0,3,6),
+    extrapolate 1 -> pull (2,2,3,2,5), grad (2,2,3,2,5,3)"""
+    from brainfm_amd import _lib as L
+    name, Bi, Bg = case
+    x, g = _dev(d["in/vol"][:Bi], torch), _dev(d["in/grid"][:Bg], torch)
+    B, Cc, gs = max(Bi, Bg), x.shape[1], tuple(g.shape[1:4])
+    lib = L.load()
+    head = (L.ptr(x), Bi, Cc, x.shape[2], x.shape[3], x.shape[4], L.ptr(g), Bg, gs[0], gs[1], gs[2], _c3((0, 3, 6)), 1)
+    pull = torch.empty((B, Cc) + gs, dtype=torch.float32, device=x.device)
+    grad = torch.empty((B, Cc) + gs + (3,), dtype=torch.float32, device=x.device)
+    L.check(lib.bfm_grid_pull3d_linear(*head, L.ptr(pull), L.stream_ptr()), "pull3d_linear")
+    L.check(lib.bfm_grid_grad3d_linear(*head, L.ptr(grad), L.stream_ptr()), "grad3d_linear")
+    return pull.cpu().numpy(), grad.cpu().numpy()
+
+
+def run_big2(IP, torch):
+    """-> the SHA-256 of the all-linear pull of big_inputs() under dct2, extrapolate 1: (1, 32) uint8"""
+    vol, _, grid = big_inputs()
+    pull = IP._pull_raw(_dev(vol, torch), _dev(grid, torch), _c3((3, 3, 3)), (1, 1, 1), 1).cpu().numpy()
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(pull).tobytes()).digest(), np.uint8).reshape(1, 32)
 
 
 # --------------------------------------------------------------------------------------------------- calls on the device

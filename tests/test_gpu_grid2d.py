@@ -1,4 +1,5 @@
-"""interpol.grid_pull / grid_push / grid_count on 2-D grids on the device (brainfm_amd/csrc/spline_grid2d.hip), their
+"""interpol.grid_pull / grid_push / grid_count on 2-D grids on the device (the D = 2 instantiations of
+brainfm_amd/csrc/spline_grid.hip), their
 first-order backward, the 2-D prefilter and the 2-D resize, against the reference's own results
 (tests/golden/interpol_grid2d*.npz, float64 runs of the vendored torch-interpol rounded to float32), against the float64
 restatement (tests/grid2d_refs.py) on shapes the fixture does not have, and bit for bit against the 3-D kernels on the

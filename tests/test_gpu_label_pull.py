@@ -363,3 +363,22 @@ def test_spline_coeff_low_orders_inplace_and_gradient():
         xd = torch.randn(shape, dtype=torch.float64, device=DEV, requires_grad=True)
         assert torch.autograd.gradcheck(lambda t: IP.spline_coeff(t, order, bound, dim), (xd,), eps=1e-2, atol=2e-4,
                                         rtol=0.0)
+
+
+# --------------------------------------------------------------------------------------------------- 7. resize of labels
+def test_resize_of_a_label_map_at_orders_below_two_is_the_label_pull_on_the_resize_grid():
+    """resize defaults to prefilter=True, which a label map refuses; below order 2 there is nothing to filter, so the default
+    call pulls the labels through the grid that resize builds (anchor 'c': linspace(0, n - 1, m) per axis), under
+    'nearest' with extrapolation.  Order 2 keeps the refusal."""
+    from brainfm_amd import interpol as IP
+    seg = T(golden()["S/img"])
+    shape = [2 * n - 1 for n in seg.shape[2:]]
+    grid = torch.stack(torch.meshgrid(*[torch.linspace(0, n - 1, m, dtype=torch.float32, device=DEV)
+                                        for n, m in zip(seg.shape[2:], shape)], indexing="ij"), dim=-1)
+    for order in (1, "linear", 0):
+        got = IP.resize(seg, shape=shape, interpolation=order)
+        assert got.dtype == seg.dtype and tuple(got.shape[2:]) == tuple(shape)
+        assert torch.equal(got, IP.grid_pull(seg, grid, order, "nearest", True))
+    assert torch.equal(IP.resize(seg, shape=shape)[..., ::2, ::2, ::2], seg)          # the nodes themselves come back
+    with pytest.raises(NotImplementedError, match="prefilter"):
+        IP.resize(seg, shape=shape, interpolation=2)

@@ -215,9 +215,10 @@ def test_resize_orders_and_the_cases_the_separable_path_refuses():
 
 
 def test_linear_calls_keep_their_kernels_and_their_bits():
-    """interpolation=1 and [1, 1, 1] go to the linear kernels, whose code is unchanged: equal bits for pull and grad.
-    push adds with fp32 atomics, whose order differs from launch to launch (synth_interp.hip says so), so two launches
-    are held to 4 units in the last place of the largest value instead; all three still meet the order-1 fixture."""
+    """interpolation=1 and [1, 1, 1] go to the linear kernels, whose arithmetic is iso1's as it always was: equal bits
+    for pull and grad.  push adds with fp32 atomics, whose order differs from launch to launch (spline_grid.hip says so),
+    so two launches are held to 4 units in the last place of the largest value instead; all three still meet the order-1
+    fixture."""
     from brainfm_amd import interpol as IP
     d = load_npz("interpol_pushgrad.npz")
     vol, grid, src = (T(d[k]) for k in ("vol", "grid", "src"))

@@ -180,19 +180,41 @@ def test_opts_keep_three_entries():
 
 
 def test_kernel_source_loads_texels_and_coordinates_through_ld_tex_only():
-    """Every read of the image and of the grid in spline_grid2d.hip is a 4-byte ld_tex: no wider vector type, no other
-    load builtin, and no subscript or dereference of the two pointers."""
-    src = open(os.path.join(CSRC, "spline_grid2d.hip")).read()
+    """Every read of the image and of the grid in spline_grid.hip -- the three dimension-generic kernels, the three padded 3-D
+    ones, the three linear ones and the tap walk -- and in the point prologue of grid_kernels.h is a 4-byte ld_tex: no wider vector
+    type, no other load builtin, and no subscript or dereference of the image, row or grid pointers."""
+    src = open(os.path.join(CSRC, "spline_grid.hip")).read()
+    assert not os.path.exists(os.path.join(CSRC, "spline_grid2d.hip"))
     code = re.sub(r"//[^\n]*", "", src)
     assert "ld_tex(" in code and "ld_tex3" not in code
     for word in ("float2", "float4", "uint2", "uint4", "int2", "int4", "__builtin_nontemporal_load", "__ldg",
                  "buffer_load", "global_load", "asm"):
         assert not re.search(r"\b%s\b" % word, code), word
-    kernels = code[:code.index('extern "C"')]
-    assert not re.search(r"\b(src|row|grid)\s*\[", kernels)                      # image and grid: never subscripted
-    pull = kernels[kernels.index("spline_pull2d"):kernels.index("spline_push2d")]
-    grad = kernels[kernels.index("spline_grad2d"):]
-    assert pull.count("ld_tex(") == 1 and grad.count("ld_tex(") == 1
+    kernels = code[:code.index("static int launch_grid")]
+    assert 'extern "C"' not in kernels
+    assert not re.search(r"\b(src|row|grid)\s*\[", kernels) and not re.search(r"(?<![.\w])g\s*\[", kernels)   # never subscripted
+    # nor dereferenced: the image pointer is declared and handed to ld_tex, the grid pointer is a parameter handed to the
+    # prologue, and neither appears anywhere else
+    assert len(re.findall(r"\bsrc\b", kernels)) == (kernels.count("const float* src = ") + kernels.count("ld_tex(src + ") +
+                                                      kernels.count("const float* row = src + "))
+    assert len(re.findall(r"\brow\b", kernels)) == (kernels.count("const float* row = ") + kernels.count("ld_tex(row + ") +
+                                                      kernels.count("float* row = dst + ") + kernels.count("atomicAdd(row + "))
+    assert len(re.findall(r"\bgrid\b", kernels)) == (kernels.count("__restrict__ grid, ") + kernels.count(", grid, Bg, dims, ") +
+                                                       kernels.count(", grid, Bg, GridDims<3>{{nx, ny, nz}}, "))
+    names = ["spline_pull", "spline_push", "spline_grad", "padded_pull3d", "padded_push3d", "padded_grad3d", "LinearNodes",
+             "linear_pull3d", "linear_push3d", "linear_grad3d"]
+    at = [kernels.index("void __launch_bounds__(256) " + n if n[:6] in ("spline", "padded") else n) for n in names]
+    at.append(len(kernels))
+    assert at == sorted(at)
+    body = {n: kernels[at[i]:at[i + 1]] for i, n in enumerate(names)}
+    assert kernels[:at[0]].count("ld_tex(") == 0                                # the tap walk itself loads nothing
+    for n in names:
+        loads = 1 if ("pull" in n or "grad" in n) else 0                        # one texel load, in the tap loop; push: none
+        assert body[n].count("ld_tex(") == loads, n
+        if n != "LinearNodes":
+            assert body[n].count("grid_point<") == 1, n
     hdr = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "grid_kernels.h")).read())
-    pixel = hdr[hdr.index("grid_pixel("):hdr.index("grid_check_args")]
-    assert pixel.count("ld_tex(") == 2 and not re.search(r"\bg\s*\[", pixel)
+    assert "GridPixel" not in hdr and "grid_pixel" not in hdr and "GridVoxel" not in hdr
+    point = hdr[hdr.index("grid_point("):hdr.index("grid_check_args")]
+    assert point.count("ld_tex(g + a)") == 1 and point.count("ld_tex(") == 1 and not re.search(r"(?<![.\w])g\s*\[", point)
+    assert "a < D" in point                                                    # D separate 4-byte loads
