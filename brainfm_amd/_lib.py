@@ -203,6 +203,15 @@ SIGNATURES = {
     "bfm_grid_grad2d_spline": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
     "bfm_grid_hess3d": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P, _P]),
     "bfm_grid_pushgrad3d": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P]),
+    "bfm_grid_push_fixed_bits": (_I, [_L, C.POINTER(_I), _I, _I]),
+    "bfm_grid_push_fixed_workspace": (_Z, [_I, _I, _L]),
+    "bfm_grid_push3d_spline_fixed": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P,
+                                          _P, _Z, _P]),
+    "bfm_grid_push2d_spline_fixed": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P, _Z,
+                                          _P]),
+    "bfm_grid_push3d_linear_fixed": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _P, _P, _Z, _P]),
+    "bfm_grid_pushgrad3d_fixed": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P,
+                                       _Z, _P]),
     "bfm_spline_axis_table_workspace": (_Z, [_I, _I, _I]),
     "bfm_spline_axis_table": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "bfm_spline_axis_pass": (_I, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),

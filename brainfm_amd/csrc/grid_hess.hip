@@ -25,8 +25,10 @@
 //
 // pushgrad: a source voxel holds a 3-vector c and adds sign * mask * (c_x dwx wy wz + c_y wx dwy wz + c_z wx wy dwz) to each
 // of its nodes: one fp32 atomic per node, as many as spline_push3d issues.  out must be zero on entry; a node whose
-// value is exactly 0 issues nothing.  The summation order, and so the last bit, is not reproducible.
+// value is exactly 0 issues nothing.  The summation order, and so the last bit, is not reproducible; the _fixed export
+// adds the same values as 64-bit fixed-point integers instead, whose sum has no order (push_accum.h).
 #include "grid_kernels.h"
+#include "push_accum.h"
 
 namespace {
 
@@ -95,11 +97,18 @@ __global__ void __launch_bounds__(256) spline_hess3d(const float* __restrict__ i
     }
 }
 
-// inp [Bi][C][nin][3], out [B][C][nx*ny*nz] zero on entry
-template <int O>
+// inp [Bi][C][nin][3], out [B][C][nx*ny*nz] zero on entry, accumulated through ACC (push_accum.h): AccumFloat, the fp32
+// atomics described above, or AccumFixed, int64 fixed-point atomics that give the same bits in every order.
+// Fixed-point bound, G = 3: with m the largest |component| of the slice, val = tx (dwx wy wz) + ty (wx dwy wz) + tz (wx wy
+// dwz).  The weights (times sign) lie in [-1, 1] (spline_push), and so do the derivatives at orders 1 to 3: the slope is
+// +-1; the quadratic's -2|x| on |x| < 1/2 and |x| - 3/2 on 1/2 <= |x| <= 3/2 lie in [-1, 0]; the cubic's |x| (3/2 |x| - 2) on
+// |x| < 1 is least at |x| = 2/3, -2/3, and its -(2 - |x|)^2 / 2 on 1 <= |x| <= 2 lies in [-1/2, 0].  Rounding is monotone, so
+// every rounded product of such factors stays in [-1, 1], |pw| <= 2 m, |pd| <= m and |val| <= fl(3 m) < 3 * 2^e for m < 2^e.
+template <int O, typename ACC>
 __global__ void __launch_bounds__(256) spline_pushgrad3d(const float* __restrict__ inp, int Bi, int C,
                                                          const float* __restrict__ grid, int Bg, int64_t nin, int nx,
-                                                         int ny, int nz, GridOpts op, int B, float* __restrict__ out) {
+                                                         int ny, int nz, GridOpts op, int B,
+                                                         typename ACC::Cell* __restrict__ out, typename ACC::Aux aux) {
     constexpr int T = grid_taps(O);
     const int ox = axis_order<O>(op, 0), oy = axis_order<O>(op, 1), oz = axis_order<O>(op, 2);
     const int64_t n = (int64_t)B * nin;
@@ -113,20 +122,23 @@ __global__ void __launch_bounds__(256) spline_pushgrad3d(const float* __restrict
         axis_nodes<T, 1, O == 1>(p.g[1], oy, ny, op.bound[1], iy, wy, dy);
         axis_nodes<T, 1, O == 1>(p.g[2], oz, nz, op.bound[2], iz, wz, dz);
         for (int c = 0; c < C; ++c) {
-            const float* t = inp + (((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * nin + p.v) * 3;
+            const int64_t sin = (int64_t)(Bi == 1 ? 0 : p.b) * C + c;
+            const float* t = inp + (sin * nin + p.v) * 3;
             const float tx = t[0], ty = t[1], tz = t[2];
-            float* dst = out + ((int64_t)p.b * C + c) * vol;
+            typename ACC::Cell* dst = out + ((int64_t)p.b * C + c) * vol;
+            const auto scale = ACC::scale(aux, sin);
+            if (ACC::dead(scale)) continue;
 #pragma unroll
             for (int a = 0; a < T; ++a)
 #pragma unroll
                 for (int bb = 0; bb < T; ++bb) {
-                    float* row = dst + ((int64_t)ix[a] * ny + iy[bb]) * nz;
+                    typename ACC::Cell* row = dst + ((int64_t)ix[a] * ny + iy[bb]) * nz;
                     const float pw = fmaf(tx, dx[a] * wy[bb], ty * (wx[a] * dy[bb]));      // goes with wz
                     const float pd = tz * (wx[a] * wy[bb]);                                // goes with dwz
 #pragma unroll
                     for (int d = 0; d < T; ++d) {
                         const float val = fmaf(pw, wz[d], pd * dz[d]);
-                        if (val != 0.f) atomicAdd(row + iz[d], val);
+                        if (val != 0.f) ACC::add(row + iz[d], val, scale);
                     }
                 }
         }
@@ -173,7 +185,31 @@ extern "C" int bfm_grid_pushgrad3d(const float* inp, int Bi, int C, int ix, int 
     const int64_t nin = in.count();
     const GridOpts op = grid_opts(3, bound, order, extrapolate);
     return launch_hess(order, B * nin, [&](auto o, dim3 gr, dim3 bl) {
-        hipLaunchKernelGGL(spline_pushgrad3d<decltype(o)::value>, gr, bl, 0, bfm_s(stream), inp, Bi, C, grid, Bg, nin, nx,
-                           ny, nz, op, B, out_zeroed);
+        hipLaunchKernelGGL((spline_pushgrad3d<decltype(o)::value, AccumFloat>), gr, bl, 0, bfm_s(stream), inp, Bi, C, grid,
+                           Bg, nin, nx, ny, nz, op, B, out_zeroed, AccumFloat::Aux{});
     });
+}
+
+// The same sums through int64 fixed-point accumulators in the workspace (push_fixed.hip), G = 3.  An all-nearest call
+// launches no push: its accumulators stay zero and the finalize pass writes the zeros.
+extern "C" int bfm_grid_pushgrad3d_fixed(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg,
+                                         int nx, int ny, int nz, const int* bound, const int* order, int extrapolate,
+                                         float* out, void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+    const GridDims<3> in{{ix, iy, iz}}, vol{{nx, ny, nz}};
+    int rc = grid_check_args(3, inp, grid, out, bound, order, Bi, Bg, C, in.n, vol.n, extrapolate);
+    if (rc != BFM_OK) return rc;
+    const int B = Bi > Bg ? Bi : Bg;
+    const int64_t nin = in.count();
+    PushFixedPlan plan;
+    rc = push_fixed_begin(&plan, inp, Bi, C, nin * 3, B, vol.count(), nin, order, 3, 3, workspace, workspace_bytes, stream);
+    if (rc != BFM_OK) return rc;
+    if (iso_order(order) != 0) {
+        const GridOpts op = grid_opts(3, bound, order, extrapolate);
+        rc = launch_hess(order, B * nin, [&](auto o, dim3 gr, dim3 bl) {
+            hipLaunchKernelGGL((spline_pushgrad3d<decltype(o)::value, AccumFixed>), gr, bl, 0, bfm_s(stream), inp, Bi, C,
+                               grid, Bg, nin, nx, ny, nz, op, B, plan.acc, plan.k);
+        });
+        if (rc != BFM_OK) return rc;
+    }
+    return push_fixed_end(plan, out, stream);
 }

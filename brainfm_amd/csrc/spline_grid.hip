@@ -31,6 +31,7 @@
 // terms and the order of the 3-D one on the image [nx][ny][1] with a third coordinate 0 and order 0 on the third axis,
 // whose extra factor is an exact 1 and whose padded taps add exact zeros.
 #include "grid_kernels.h"
+#include "push_accum.h"
 
 namespace {
 
@@ -99,14 +100,19 @@ __global__ void __launch_bounds__(256) spline_pull(const float* __restrict__ inp
 }
 
 // nd.push: the adjoint of pull -- every source point scatters its value to its nodes.  out [B][C][*n] must be zero on
-// entry.  fp32 atomics (one global_atomic_add_f32 each): the summation order, and so the last bit, is not reproducible.  A
+// entry.  ACC = AccumFloat: fp32 atomics (one global_atomic_add_f32 each), the summation order, and so the last bit, is
+// not reproducible; ACC = AccumFixed: int64 fixed-point atomics, the same bits in every order (push_accum.h).  A
 // tap whose weight times sign is exactly 0 (a node the `zero` bound drops, a padded tap) issues nothing, and neither does
 // a masked point.  The taps are the outer loops and the lanes run along the fastest axis of the source, so for a smooth
 // grid one atomic wave-instruction covers neighbouring addresses of a few rows.
-template <int D, int O>
+// Fixed-point bound, G = 1: a contribution is val * wt, wt a product of at most D factors weight * sign.  The weights of
+// spline_weight lie in [0, 1] at every order (1, 1 - |x| on |x| <= 1, at most 3/4 and 2/3 for the quadratic and the cubic),
+// the sign is -1, 0 or 1, and a rounded product of factors in [-1, 1] stays in [-1, 1]: |val * wt| <= |val| <= m.
+template <int D, int O, typename ACC>
 __global__ void __launch_bounds__(256) spline_push(const float* __restrict__ inp, int Bi, int C,
                                                    const float* __restrict__ grid, int Bg, int64_t nin, GridDims<D> dims,
-                                                   GridOpts op, int B, float* __restrict__ out) {
+                                                   GridOpts op, int B, typename ACC::Cell* __restrict__ out,
+                                                   typename ACC::Aux aux) {
     constexpr int T = grid_taps(O);
     const int64_t n = (int64_t)B * nin;
     const int64_t vol = dims.count();
@@ -117,10 +123,13 @@ __global__ void __launch_bounds__(256) spline_push(const float* __restrict__ inp
         float w[D][T];
         point_nodes<D, T, O>(p, dims, op, idx, w);
         for (int c = 0; c < C; ++c) {
-            const float val = inp[((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * nin + p.v];
-            float* dst = out + ((int64_t)p.b * C + c) * vol;
+            const int64_t sin = (int64_t)(Bi == 1 ? 0 : p.b) * C + c;
+            const float val = inp[sin * nin + p.v];
+            typename ACC::Cell* dst = out + ((int64_t)p.b * C + c) * vol;
+            const auto scale = ACC::scale(aux, sin);
+            if (ACC::dead(scale)) continue;
             for_each_tap<D, T, 1>(dims, idx, w, nullptr, [&](int64_t off, const float (&wt)[1]) {
-                if (wt[0] != 0.f) atomicAdd(dst + off, val * wt[0]);
+                if (wt[0] != 0.f) ACC::add(dst + off, val * wt[0], scale);
             });
         }
     }
@@ -193,9 +202,11 @@ __global__ void __launch_bounds__(256) padded_pull3d(const float* __restrict__ i
     }
 }
 
+template <typename ACC>
 __global__ void __launch_bounds__(256) padded_push3d(const float* __restrict__ inp, int Bi, int C,
                                                      const float* __restrict__ grid, int Bg, int64_t nin, int nx, int ny,
-                                                     int nz, GridOpts op, int B, float* __restrict__ out) {
+                                                     int nz, GridOpts op, int B,
+                                                     typename ACC::Cell* __restrict__ out, typename ACC::Aux aux) {
     constexpr int T = 4;
     const int ox = op.order[0], oy = op.order[1], oz = op.order[2];
     const int64_t n = (int64_t)B * nin;
@@ -209,18 +220,21 @@ __global__ void __launch_bounds__(256) padded_push3d(const float* __restrict__ i
         axis_nodes<T>(p.g[1], oy, ny, op.bound[1], iy, wy);
         axis_nodes<T>(p.g[2], oz, nz, op.bound[2], iz, wz);
         for (int c = 0; c < C; ++c) {
-            const float val = inp[((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * nin + p.v];
-            float* dst = out + ((int64_t)p.b * C + c) * vol;
+            const int64_t sin = (int64_t)(Bi == 1 ? 0 : p.b) * C + c;
+            const float val = inp[sin * nin + p.v];
+            typename ACC::Cell* dst = out + ((int64_t)p.b * C + c) * vol;
+            const auto scale = ACC::scale(aux, sin);
+            if (ACC::dead(scale)) continue;
 #pragma unroll
             for (int a = 0; a < T; ++a)
 #pragma unroll
                 for (int bb = 0; bb < T; ++bb) {
-                    float* row = dst + ((int64_t)ix[a] * ny + iy[bb]) * nz;
+                    typename ACC::Cell* cells = dst + ((int64_t)ix[a] * ny + iy[bb]) * nz;
                     const float wxy = wx[a] * wy[bb];
 #pragma unroll
                     for (int d = 0; d < T; ++d) {
                         const float w = wxy * wz[d];
-                        if (w != 0.f) atomicAdd(row + iz[d], val * w);
+                        if (w != 0.f) ACC::add(cells + iz[d], val * w, scale);
                     }
                 }
         }
@@ -323,23 +337,30 @@ __global__ void linear_pull3d(const float* __restrict__ inp, int Bi, int C, Grid
 }
 
 // iso1.push3d (iso1.py:136-265): the adjoint of pull3d -- every source voxel scatters its value to the 8 corners around
-// its grid coordinate.  out [B][C][nx*ny*nz] must be zero on entry.  fp32 atomics: the summation order (and so the last
-// bit) is not reproducible, like torch's scatter_add_ on a GPU.
+// its grid coordinate.  out [B][C][nx*ny*nz] must be zero on entry.  ACC = AccumFloat: fp32 atomics, the summation order
+// (and so the last bit) is not reproducible, like torch's scatter_add_ on a GPU; ACC = AccumFixed: push_accum.h, where a
+// contribution of exactly 0 adds the integer 0.  Fixed-point bound, G = 1: t is val times three signs, the mask (0 or 1)
+// and a product of three weights 1 - t or t with t = g - floor(g) in [0, 1], so |t| <= |val| <= m.
+template <typename ACC>
 __global__ void linear_push3d(const float* __restrict__ inp, int Bi, int C, const float* __restrict__ grid, int Bg,
-                              int64_t nin, GridDims<3> dims, GridOpts op, int B, float* __restrict__ out) {
+                              int64_t nin, GridDims<3> dims, GridOpts op, int B, typename ACC::Cell* __restrict__ out,
+                              typename ACC::Aux aux) {
     const int64_t n = (int64_t)B * nin;
     const int64_t vol = dims.count();
     GRID_STRIDE(i, n) {
         const GridPoint<3> p = grid_point<3>(i, nin, grid, Bg, dims, op.extrap);
         const LinearNodes q = linear_nodes(p, dims, op);
         for (int c = 0; c < C; ++c) {
-            const float val = inp[((int64_t)(Bi == 1 ? 0 : p.b) * C + c) * nin + p.v];
-            float* dst = out + ((int64_t)p.b * C + c) * vol;
+            const int64_t sin = (int64_t)(Bi == 1 ? 0 : p.b) * C + c;
+            const float val = inp[sin * nin + p.v];
+            typename ACC::Cell* dst = out + ((int64_t)p.b * C + c) * vol;
+            const auto scale = ACC::scale(aux, sin);
+            if (ACC::dead(scale)) continue;
             LINEAR_CORNERS(a, bb, d) {
                 float t = val * (float)(q.sg[0][a] * q.sg[1][bb] * q.sg[2][d]);
                 t = t * p.mask;
                 t = t * ((q.w[0][a] * q.w[1][bb]) * q.w[2][d]);
-                atomicAdd(dst + linear_offset(q, dims, a, bb, d), t);
+                ACC::add(dst + linear_offset(q, dims, a, bb, d), t, scale);
             }
         }
     }
@@ -411,26 +432,52 @@ static int launch_sample(const float* inp, int Bi, int C, GridDims<D> in, const 
     });
 }
 
-// push: source and grid `in`, volume `vol`
-template <int D, bool LINEAR>
+// push: source and grid `in`, volume `vol`, accumulated by the policy ACC (push_accum.h) in `acc`, zero on entry
+template <int D, bool LINEAR, typename ACC>
 static int launch_push(const float* inp, int Bi, int C, GridDims<D> in, const float* grid, int Bg, GridDims<D> vol,
-                       const int* bound, const int* order, int extrapolate, float* out_zeroed, bfm_stream_t stream) {
-    const int rc = grid_check_args(D, inp, grid, out_zeroed, bound, order, Bi, Bg, C, in.n, vol.n, extrapolate);
-    if (rc != BFM_OK) return rc;
+                       const int* bound, const int* order, int extrapolate, typename ACC::Cell* acc, typename ACC::Aux aux,
+                       bfm_stream_t stream) {
     const int B = Bi > Bg ? Bi : Bg;
     const int64_t nin = in.count();
     const GridOpts op = grid_opts(D, bound, order, extrapolate);
     auto go = [&](auto kernel) {
-        return launch_grid(kernel, B * nin, stream, inp, Bi, C, grid, Bg, nin, vol, op, B, out_zeroed);
+        return launch_grid(kernel, B * nin, stream, inp, Bi, C, grid, Bg, nin, vol, op, B, acc, aux);
     };
-    if constexpr (LINEAR) return go(linear_push3d);
+    if constexpr (LINEAR) return go(linear_push3d<ACC>);
     else return launch_order<D>(op, [&](auto o) {
         constexpr int O = decltype(o)::value;
         if constexpr (D == 3 && O < 0)
-            return launch_grid(padded_push3d, B * nin, stream, inp, Bi, C, grid, Bg, nin, vol.n[0], vol.n[1], vol.n[2], op, B,
-                               out_zeroed);
-        else return go(spline_push<D, O>);
+            return launch_grid(padded_push3d<ACC>, B * nin, stream, inp, Bi, C, grid, Bg, nin, vol.n[0], vol.n[1], vol.n[2],
+                               op, B, acc, aux);
+        else return go(spline_push<D, O, ACC>);
     });
+}
+
+// the float-atomic route: out_zeroed is the accumulator
+template <int D, bool LINEAR>
+static int push_atomic(const float* inp, int Bi, int C, GridDims<D> in, const float* grid, int Bg, GridDims<D> vol,
+                       const int* bound, const int* order, int extrapolate, float* out_zeroed, bfm_stream_t stream) {
+    const int rc = grid_check_args(D, inp, grid, out_zeroed, bound, order, Bi, Bg, C, in.n, vol.n, extrapolate);
+    if (rc != BFM_OK) return rc;
+    return launch_push<D, LINEAR, AccumFloat>(inp, Bi, C, in, grid, Bg, vol, bound, order, extrapolate, out_zeroed, {},
+                                              stream);
+}
+
+// the fixed-point route: the maxima and exponents of the slices, the push into the int64 accumulators of the workspace,
+// the conversion into out (push_fixed.hip).  P = the points of a batch item, T = the product of order + 1, G = 1.
+template <int D, bool LINEAR>
+static int push_fixed(const float* inp, int Bi, int C, GridDims<D> in, const float* grid, int Bg, GridDims<D> vol,
+                      const int* bound, const int* order, int extrapolate, float* out, void* workspace,
+                      size_t workspace_bytes, bfm_stream_t stream) {
+    int rc = grid_check_args(D, inp, grid, out, bound, order, Bi, Bg, C, in.n, vol.n, extrapolate);
+    if (rc != BFM_OK) return rc;
+    PushFixedPlan plan;
+    rc = push_fixed_begin(&plan, inp, Bi, C, in.count(), Bi > Bg ? Bi : Bg, vol.count(), in.count(), order, D, 1, workspace,
+                          workspace_bytes, stream);
+    if (rc != BFM_OK) return rc;
+    rc = launch_push<D, LINEAR, AccumFixed>(inp, Bi, C, in, grid, Bg, vol, bound, order, extrapolate, plan.acc, plan.k,
+                                            stream);
+    return rc != BFM_OK ? rc : push_fixed_end(plan, out, stream);
 }
 
 extern "C" int bfm_grid_pull3d_spline(const float* inp, int Bi, int C, int nx, int ny, int nz, const float* grid,
@@ -443,7 +490,7 @@ extern "C" int bfm_grid_pull3d_spline(const float* inp, int Bi, int C, int nx, i
 extern "C" int bfm_grid_push3d_spline(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg,
                                       int nx, int ny, int nz, const int* bound, const int* order, int extrapolate,
                                       float* out_zeroed, bfm_stream_t stream) {
-    return launch_push<3, false>(inp, Bi, C, {{ix, iy, iz}}, grid, Bg, {{nx, ny, nz}}, bound, order, extrapolate,
+    return push_atomic<3, false>(inp, Bi, C, {{ix, iy, iz}}, grid, Bg, {{nx, ny, nz}}, bound, order, extrapolate,
                                  out_zeroed, stream);
 }
 
@@ -464,7 +511,7 @@ extern "C" int bfm_grid_pull2d_spline(const float* inp, int Bi, int C, int nx, i
 extern "C" int bfm_grid_push2d_spline(const float* inp, int Bi, int C, int ix, int iy, const float* grid, int Bg, int nx,
                                       int ny, const int* bound, const int* order, int extrapolate, float* out_zeroed,
                                       bfm_stream_t stream) {
-    return launch_push<2, false>(inp, Bi, C, {{ix, iy}}, grid, Bg, {{nx, ny}}, bound, order, extrapolate, out_zeroed,
+    return push_atomic<2, false>(inp, Bi, C, {{ix, iy}}, grid, Bg, {{nx, ny}}, bound, order, extrapolate, out_zeroed,
                                  stream);
 }
 
@@ -485,7 +532,7 @@ extern "C" int bfm_grid_pull3d_linear(const float* inp, int Bi, int C, int nx, i
 extern "C" int bfm_grid_push3d_linear(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg,
                                       int nx, int ny, int nz, const int* bound, int extrapolate, float* out_zeroed,
                                       bfm_stream_t stream) {
-    return launch_push<3, true>(inp, Bi, C, {{ix, iy, iz}}, grid, Bg, {{nx, ny, nz}}, bound, GRID_LINEAR, extrapolate,
+    return push_atomic<3, true>(inp, Bi, C, {{ix, iy, iz}}, grid, Bg, {{nx, ny, nz}}, bound, GRID_LINEAR, extrapolate,
                                 out_zeroed, stream);
 }
 
@@ -494,4 +541,26 @@ extern "C" int bfm_grid_grad3d_linear(const float* inp, int Bi, int C, int nx, i
                                       bfm_stream_t stream) {
     return launch_sample<3, true, true>(inp, Bi, C, {{nx, ny, nz}}, grid, Bg, {{ox, oy, oz}}, bound, GRID_LINEAR,
                                         extrapolate, out, stream);
+}
+
+extern "C" int bfm_grid_push3d_spline_fixed(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid,
+                                            int Bg, int nx, int ny, int nz, const int* bound, const int* order,
+                                            int extrapolate, float* out, void* workspace, size_t workspace_bytes,
+                                            bfm_stream_t stream) {
+    return push_fixed<3, false>(inp, Bi, C, {{ix, iy, iz}}, grid, Bg, {{nx, ny, nz}}, bound, order, extrapolate, out,
+                                workspace, workspace_bytes, stream);
+}
+
+extern "C" int bfm_grid_push2d_spline_fixed(const float* inp, int Bi, int C, int ix, int iy, const float* grid, int Bg,
+                                            int nx, int ny, const int* bound, const int* order, int extrapolate, float* out,
+                                            void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+    return push_fixed<2, false>(inp, Bi, C, {{ix, iy}}, grid, Bg, {{nx, ny}}, bound, order, extrapolate, out, workspace,
+                                workspace_bytes, stream);
+}
+
+extern "C" int bfm_grid_push3d_linear_fixed(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid,
+                                            int Bg, int nx, int ny, int nz, const int* bound, int extrapolate, float* out,
+                                            void* workspace, size_t workspace_bytes, bfm_stream_t stream) {
+    return push_fixed<3, true>(inp, Bi, C, {{ix, iy, iz}}, grid, Bg, {{nx, ny, nz}}, bound, GRID_LINEAR, extrapolate, out,
+                               workspace, workspace_bytes, stream);
 }

@@ -19,8 +19,15 @@ the reference.
 ``grid_pull`` of an integer image is the reference's label branch (api.py:182-193) in one pass of label_pull.hip.  The grid
 builders ``identity_grid`` / ``add_identity_grid`` / ``add_identity_grid_`` / ``affine_grid`` (api.py:455-560) run on
 grid_builders.hip, and ``spline_coeff`` (api.py:335-383) filters one dimension on the prefilter kernels.
+
+The scatter kernels behind ``grid_push`` / ``grid_count`` / ``grid_pushgrad`` and the backward of ``grid_pull`` /
+``grid_grad`` / the 2-D ``resize`` add with fp32 atomics by default, so their last bit differs from run to run.
+``set_push_mode("fixed")``, ``BFM_PUSH_MODE=fixed`` or ``torch.use_deterministic_algorithms(True)`` send them through
+64-bit fixed-point accumulators instead (``push_mode()``): the same bits on every run, whatever the
+order of the points.
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -112,18 +119,61 @@ _LABEL_DTYPE = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3} 
 LABEL_PULL_AUTO, LABEL_PULL_LDS, LABEL_PULL_REGS, LABEL_PULL_PASSES = 0, 1, 2, 3         # BFM_LABEL_PULL_*
 
 
-def _export(name, x, g, dims, b, o, ext, extra, out):
+def _export(name, x, g, dims, b, o, ext, extra, out, workspace=None):
     """One call of an export of the grid family, which all take (inp[, label dtype], Bi, C, *in, grid, Bg, *dims, bound[,
-    order], extrapolate, *extra, out, stream): x (Bi,C,*in[,3]) and g (Bg,*,D) contiguous, `dims` the other spatial shape
-    of the call (the grid's for a pull, the volume's for a push), o None for a _linear export, which takes no order.
-    D = 2: the two extents of each shape; the export reads the first two of the three bounds and orders.
+    order], extrapolate, *extra, out[, workspace, bytes], stream): x (Bi,C,*in[,3]) and g (Bg,*,D) contiguous, `dims` the
+    other spatial shape of the call (the grid's for a pull, the volume's for a push), o None for a _linear export, which
+    takes no order.  D = 2: the two extents of each shape; the export reads the first two of the three bounds and orders.
     Returns `out`."""
     dim = g.shape[-1]
     args = [L.ptr(x)] + ([] if x.dtype.is_floating_point else [_LABEL_DTYPE[x.dtype]])
     args += [x.shape[0], x.shape[1], *x.shape[2:2 + dim], L.ptr(g), g.shape[0], *dims[:dim], b]
     args += [] if o is None else [(C.c_int * 3)(*o)]
-    L.check(getattr(L.load(), "bfm_" + name)(*args, ext, *extra, L.ptr(out), L.stream_ptr()), name)
+    ws = [] if workspace is None else [L.ptr(workspace), workspace.numel()]
+    L.check(getattr(L.load(), "bfm_" + name)(*args, ext, *extra, L.ptr(out), *ws, L.stream_ptr()), name)
     return out
+
+
+PUSH_MODES = ("atomic", "fixed")
+_push_mode_override = None
+
+
+def _check_push_mode(mode, what):
+    if mode not in PUSH_MODES:
+        raise ValueError("%s: %r is not a push mode (%s)" % (what, mode, " / ".join(PUSH_MODES)))
+    return mode
+
+
+def set_push_mode(mode):
+    """How grid_push, grid_count, grid_pushgrad and the backward of grid_pull / grid_grad / the 2-D resize accumulate:
+    'atomic' (fp32 atomics: the last bit depends on the order of arrival) or 'fixed' (64-bit fixed-point integer atomics:
+    the same bits on every run, in every order of the points).  None clears the choice, and
+    push_mode() follows the environment and torch again."""
+    global _push_mode_override
+    _push_mode_override = None if mode is None else _check_push_mode(mode, "set_push_mode")
+
+
+def push_mode():
+    """The accumulation mode of the scatter kernels, resolved at every call: set_push_mode(mode) if one was given, else the
+    environment variable BFM_PUSH_MODE, else 'fixed' under torch.use_deterministic_algorithms(True), else 'atomic'."""
+    if _push_mode_override is not None:
+        return _push_mode_override
+    env = os.environ.get("BFM_PUSH_MODE")
+    if env:
+        return _check_push_mode(env, "BFM_PUSH_MODE")
+    return "fixed" if torch.are_deterministic_algorithms_enabled() else "atomic"
+
+
+def _fixed_export(name, x, g, shape, b, o, ext):
+    """The _fixed sibling of a scatter export: the same sums through int64 fixed-point accumulators in a workspace; `out`
+    need not be zero, every element is written."""
+    out = _out(x, g, *shape)
+    nvox = 1
+    for n in shape:
+        nvox *= n
+    nbytes = L.load().bfm_grid_push_fixed_workspace(out.shape[0], out.shape[1], nvox)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    return _export(name + "_fixed", x, g, shape, b, o, ext, (), out, workspace=ws)
 
 
 def _linear_or_spline(op, o, dim=3):
@@ -147,6 +197,8 @@ def _pull_raw(x, g, b, o, ext):
 
 def _push_raw(x, g, shape, b, o, ext):
     name, o = _linear_or_spline("push", o, g.shape[-1])
+    if push_mode() == "fixed":
+        return _fixed_export(name, x, g, shape, b, o, ext)
     return _export(name, x, g, shape, b, o, ext, (), _out(x, g, *shape, fill=torch.zeros))
 
 
@@ -166,6 +218,8 @@ def _hess_raw(x, g, b, o, ext, cot=None):
 
 def _pushgrad_raw(x, g, shape, b, o, ext):
     """x (B,C,*in,3) -> (B,C,*shape)"""
+    if push_mode() == "fixed":
+        return _fixed_export("grid_pushgrad3d", x, g, shape, b, o, ext)
     return _export("grid_pushgrad3d", x, g, shape, b, o, ext, (), _out(x, g, *shape, fill=torch.zeros))
 
 
@@ -325,7 +379,7 @@ def grid_hess(input, grid, interpolation="linear", bound="zero", extrapolate=Fal
 def grid_pushgrad(input, grid, shape=None, interpolation="linear", bound="zero", extrapolate=False):
     """pushpull.py:176-203: the adjoint of grid_grad.  input (..., [channel], *spatial, 3) holds a 3-vector per voxel and
     is splatted at the coordinates `grid` (..., *spatial, 3) into a volume of `shape` (default: the input's spatial
-    shape): (..., [channel], *shape).  fp32 atomics, like grid_push.  Forward only."""
+    shape): (..., [channel], *shape).  fp32 atomics, like grid_push, or fixed point under push_mode().  Forward only."""
     b, o, ext = _opts(interpolation, bound, extrapolate)
     if grid.shape[-1] != 3 or input.shape[-1] != 3:
         raise NotImplementedError("grid_pushgrad: only 3-D grids are implemented (1-D and 2-D grids are not)")

@@ -668,6 +668,34 @@ int bfm_grid_hess3d(const float* inp, int Bi, int C, int nx, int ny, int nz, con
 int bfm_grid_pushgrad3d(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg, int nx, int ny,
                         int nz, const int* bound, const int* order, int extrapolate, float* out_zeroed,
                         bfm_stream_t stream);
+/* Bit-reproducible forms of the four scatter exports above: bfm_grid_push3d_spline_fixed replaces bfm_grid_push3d_spline,
+ * bfm_grid_push2d_spline_fixed bfm_grid_push2d_spline, bfm_grid_push3d_linear_fixed bfm_grid_push3d_linear and
+ * bfm_grid_pushgrad3d_fixed bfm_grid_pushgrad3d where the same bits are wanted on every run.  Each takes its sibling's
+ * arguments and a workspace of bfm_grid_push_fixed_workspace(B, C, nx*ny*nz) bytes (B = max(Bi,Bg); 0 for a bad
+ * argument) before the stream; `out` need NOT be zero on entry and every element of it is written.  The kernels, nodes,
+ * weights and contributions are the sibling's; only the accumulation differs.  Per slice (b, c) of inp: m = max |inp|
+ * over the slice (pushgrad: over its 3 components too), taken on the device; e with m < 2^e (frexp); bits =
+ * bfm_grid_push_fixed_bits(P, order, D, G) = ceil(log2(P * T * G)) with P = the grid points of a batch item, T = the
+ * product of order[a] + 1 over the D axes and G = 1 (push) or 3 (pushgrad), a bound of |contribution| / m; k = 62 - bits -
+ * e.  A contribution c, the fp32 value the sibling adds, goes as q = rint(c * 2^k) (nearest even, exact in double) into
+ * an int64 accumulator with one 64-bit integer atomic, so the sum has no order and cannot overflow; then out =
+ * (float)((double)acc * 2^-k).  m = 0: the slice is +0.  m NaN or Inf (pushgrad: or 2^126 and more, where 3 m need not be
+ * a finite float): the whole slice is NaN (the siblings poison the touched nodes only), other slices are unaffected.
+ * bits > 40 (or P, order, D, G out of range): BFM_E_ARG.  No host read-back; everything runs on `stream`. */
+int bfm_grid_push_fixed_bits(int64_t P, const int* order, int D, int G);
+size_t bfm_grid_push_fixed_workspace(int B, int C, int64_t nvox);
+int bfm_grid_push3d_spline_fixed(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg, int nx,
+                                 int ny, int nz, const int* bound, const int* order, int extrapolate, float* out,
+                                 void* workspace, size_t workspace_bytes, bfm_stream_t stream);
+int bfm_grid_push2d_spline_fixed(const float* inp, int Bi, int C, int ix, int iy, const float* grid, int Bg, int nx, int ny,
+                                 const int* bound, const int* order, int extrapolate, float* out, void* workspace,
+                                 size_t workspace_bytes, bfm_stream_t stream);
+int bfm_grid_push3d_linear_fixed(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg, int nx,
+                                 int ny, int nz, const int* bound, int extrapolate, float* out, void* workspace,
+                                 size_t workspace_bytes, bfm_stream_t stream);
+int bfm_grid_pushgrad3d_fixed(const float* inp, int Bi, int C, int ix, int iy, int iz, const float* grid, int Bg, int nx,
+                              int ny, int nz, const int* bound, const int* order, int extrapolate, float* out,
+                              void* workspace, size_t workspace_bytes, bfm_stream_t stream);
 /* interpol.restrict -- utils/interpol/restrict.py:9-122 (grid_push, nd.py:148-214, on torch.stack(meshgrid_ij(*lin))) --
  * and the backward of the separable cubic interpol.resize, as per-axis sparse operators.  A separable grid has one
  * coordinate list per axis, so the (order+1)^3 taps of nd.py factor into three axis passes.
