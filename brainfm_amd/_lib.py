@@ -282,7 +282,9 @@ SIGNATURES = {
     "bfm_deformed_atlas": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), _L, _P, _P]),
     "bfm_deformed_atlas_tile": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), _L, _P, _P]),
     "bfm_zoom_linear": (_I, [_P, _I, _I, _I, _I, C.POINTER(ZoomAxis), _I, _I, _I, _P, _P]),
+    "bfm_zoom_linear_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "bfm_conv1d_axis": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "bfm_conv1d_axis_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_Z)]),
     "bfm_grid_pull3d_linear": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), _I, _P, _P]),
     "bfm_deform_grid_workspace": (_Z, [_I, _I, _I]),
     "bfm_deform_grid": (_I, [_P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_I), _P, _P, _P, _P, _P, _Z, _P]),

@@ -626,6 +626,49 @@ extern "C" int bfm_deformed_atlas_tile(const float* tile_in, const float* regx, 
     return bfm_launch_status();
 }
 
+// The one place that chooses among zoom_linear_small / zoom_linear / zoom_linear_long (the launcher below and the tests
+// both ask here): 0 small, 1 rows with 16-byte stores, 2 rows with scalar stores, 3 long; < 0: a BFM_E_* code.
+extern "C" int bfm_zoom_linear_route(int nx, int ny, int nz, int C, int ox, int oy, int oz, int out_aligned16) {
+    if (nx <= 0 || ny <= 0 || nz <= 0 || C <= 0 || ox <= 0 || oy <= 0 || oz <= 0) return BFM_E_ARG;
+    if ((int64_t)ox * oy > INT32_MAX || (int64_t)oz * C > INT32_MAX) return BFM_E_SHAPE;
+    if (C == 1 && (int64_t)nx * ny * nz <= ZOOM_SRC && ox + oy + oz <= ZOOM_TAB && (oz & 3) == 0 && out_aligned16) return 0;
+    if ((int64_t)nz * C <= ZOOM_ROW && (int64_t)oz * C <= ZOOM_OUT) return (((int64_t)oz * C) & 3) == 0 && out_aligned16 ? 1 : 2;
+    return 3;
+}
+
+// The same for bfm_conv1d_axis: 0 / 1 / 2 the slab kernel of that axis, 3 the per-tap fallback; < 0: a BFM_E_* code.
+// seg: outputs along the filtered axis (axes 0, 1) or rows (axis 2) per slab, 0 for the fallback; nslab: workgroups
+// launched; lds_bytes: dynamic LDS of the launch.  Any of the three may be NULL.
+extern "C" int bfm_conv1d_axis_plan(int nx, int ny, int nz, int axis, int klen, int* seg_out, int* nslab_out,
+                                    size_t* lds_bytes) {
+    if (nx <= 0 || ny <= 0 || nz <= 0 || axis < 0 || axis > 2 || klen <= 0 || !(klen & 1)) return BFM_E_ARG;
+    if ((int64_t)nx * ny > INT32_MAX) return BFM_E_SHAPE;
+    int route = 3, seg = 0, nslab = grid_for((int64_t)nx * ny, 4);
+    size_t smem = 0;
+    if (klen <= C1D_TAPS && (axis != 2 || nz <= C1D_NZ)) {
+        route = axis;
+        if (axis == 2) {
+            const int rows = nx * ny;
+            seg = std::max(4, bfm_cdiv(rows, C1D_RESIDENT));
+            while (seg > 4 && (size_t)seg * (nz | 1) * sizeof(float) > 24 * 1024) --seg;    // <= 24 KB of LDS: 6 per CU
+            nslab = bfm_cdiv(rows, seg);
+            smem = (size_t)seg * (nz | 1) * sizeof(float);
+        } else {
+            const int len = axis == 0 ? nx : ny;
+            const int lines = (axis == 0 ? ny : nx) * ((nz + 63) / 64);
+            const int segs = std::max(1, C1D_RESIDENT / std::max(lines, 1));
+            seg = std::max(8, bfm_cdiv(len, segs));
+            while (seg > 8 && (size_t)(seg + klen - 1) * 65 * sizeof(float) > 24 * 1024) --seg;
+            nslab = lines * bfm_cdiv(len, seg);
+            smem = (size_t)(seg + klen - 1) * 65 * sizeof(float);
+        }
+    }
+    if (seg_out) *seg_out = seg;
+    if (nslab_out) *nslab_out = nslab;
+    if (lds_bytes) *lds_bytes = smem;
+    return route;
+}
+
 extern "C" int bfm_zoom_linear(const float* X, int nx, int ny, int nz, int C, const bfm_zoom_axis_t* ax, int ox,
                                int oy, int oz, float* out, bfm_stream_t stream) {
     if (!X || !ax || !out || nx <= 0 || ny <= 0 || nz <= 0 || C <= 0 || ox <= 0 || oy <= 0 || oz <= 0) return BFM_E_ARG;
@@ -633,12 +676,12 @@ extern "C" int bfm_zoom_linear(const float* X, int nx, int ny, int nz, int C, co
         if (!ax[a].f || !ax[a].c || !ax[a].wf || !ax[a].wc) return BFM_E_ARG;
     ZoomTabs t{ax[0].f, ax[0].c, ax[1].f, ax[1].c, ax[2].f, ax[2].c, ax[0].wf, ax[0].wc, ax[1].wf, ax[1].wc,
                ax[2].wf, ax[2].wc};
-    if ((int64_t)ox * oy > INT32_MAX || (int64_t)oz * C > INT32_MAX) return BFM_E_SHAPE;
-    if (C == 1 && (int64_t)nx * ny * nz <= ZOOM_SRC && ox + oy + oz <= ZOOM_TAB && (oz & 3) == 0 &&
-        (reinterpret_cast<uintptr_t>(out) & 15) == 0)
+    const int route = bfm_zoom_linear_route(nx, ny, nz, C, ox, oy, oz, (reinterpret_cast<uintptr_t>(out) & 15) == 0);
+    if (route < 0) return route;
+    if (route == 0)
         hipLaunchKernelGGL(zoom_linear_small, dim3(grid_for((int64_t)ox * oy * oz * C / 4, 256, 1024)), dim3(256), 0,
                            bfm_s(stream), X, nx, ny, nz, C, t, ox, oy, oz, out);
-    else if ((int64_t)nz * C <= ZOOM_ROW && (int64_t)oz * C <= ZOOM_OUT)
+    else if (route == 1 || route == 2)                          // the kernel picks the store form from the same two facts
         hipLaunchKernelGGL(zoom_linear, dim3(grid_for((int64_t)ox * oy, 8, 4096)), dim3(256),
                            (size_t)(4 * nz * C + 4 * oz * C) * sizeof(float), bfm_s(stream), X, nx, ny, nz, C, t, ox, oy, oz,
                            out);
@@ -652,33 +695,19 @@ extern "C" int bfm_conv1d_axis(const float* in, int nx, int ny, int nz, int axis
                                float* out, bfm_stream_t stream) {
     if (!in || !kern || !out || nx <= 0 || ny <= 0 || nz <= 0 || axis < 0 || axis > 2 || klen <= 0 || !(klen & 1))
         return BFM_E_ARG;
-    if ((int64_t)nx * ny > INT32_MAX) return BFM_E_SHAPE;
-    if (klen <= C1D_TAPS && (axis != 2 || nz <= C1D_NZ)) {
-        hipStream_t st = bfm_s(stream);
-        if (axis == 2) {
-            const int rows = nx * ny;
-            int seg = std::max(4, bfm_cdiv(rows, C1D_RESIDENT));
-            while (seg > 4 && (size_t)seg * (nz | 1) * sizeof(float) > 24 * 1024) --seg;    // <= 24 KB of LDS: 6 per CU
-            const int nslab = bfm_cdiv(rows, seg);
-            const size_t smem = (size_t)seg * (nz | 1) * sizeof(float);
-            hipLaunchKernelGGL(conv1d_slab<2>, dim3(nslab), dim3(256), smem, st, in, nx, ny, nz, kern, klen, seg, out);
-        } else {
-            const int len = axis == 0 ? nx : ny;
-            const int lines = (axis == 0 ? ny : nx) * ((nz + 63) / 64);
-            int segs = std::max(1, C1D_RESIDENT / std::max(lines, 1));
-            int seg = std::max(8, bfm_cdiv(len, segs));
-            while (seg > 8 && (size_t)(seg + klen - 1) * 65 * sizeof(float) > 24 * 1024) --seg;
-            const int nslab = lines * bfm_cdiv(len, seg);
-            const size_t smem = (size_t)(seg + klen - 1) * 65 * sizeof(float);
-            if (axis == 0)
-                hipLaunchKernelGGL(conv1d_slab<0>, dim3(nslab), dim3(256), smem, st, in, nx, ny, nz, kern, klen, seg, out);
-            else
-                hipLaunchKernelGGL(conv1d_slab<1>, dim3(nslab), dim3(256), smem, st, in, nx, ny, nz, kern, klen, seg, out);
-        }
-        return bfm_launch_status();
-    }
-    hipLaunchKernelGGL(conv1d_axis, dim3(grid_for((int64_t)nx * ny, 4)), dim3(256), 0, bfm_s(stream), in, nx, ny, nz, axis,
-                       kern, klen, out);
+    int seg = 0, nslab = 0;
+    size_t smem = 0;
+    const int route = bfm_conv1d_axis_plan(nx, ny, nz, axis, klen, &seg, &nslab, &smem);
+    if (route < 0) return route;
+    hipStream_t st = bfm_s(stream);
+    if (route == 2)
+        hipLaunchKernelGGL(conv1d_slab<2>, dim3(nslab), dim3(256), smem, st, in, nx, ny, nz, kern, klen, seg, out);
+    else if (route == 0)
+        hipLaunchKernelGGL(conv1d_slab<0>, dim3(nslab), dim3(256), smem, st, in, nx, ny, nz, kern, klen, seg, out);
+    else if (route == 1)
+        hipLaunchKernelGGL(conv1d_slab<1>, dim3(nslab), dim3(256), smem, st, in, nx, ny, nz, kern, klen, seg, out);
+    else
+        hipLaunchKernelGGL(conv1d_axis, dim3(nslab), dim3(256), 0, st, in, nx, ny, nz, axis, kern, klen, out);
     return bfm_launch_status();
 }
 

@@ -570,9 +570,18 @@ int bfm_deformed_atlas_tile(const float* tile_in, const float* regx, const float
 typedef struct { const int32_t* f; const int32_t* c; const float* wf; const float* wc; } bfm_zoom_axis_t;
 int bfm_zoom_linear(const float* X, int nx, int ny, int nz, int C, const bfm_zoom_axis_t* axes /*[3]*/, int ox, int oy,
                     int oz, float* out, bfm_stream_t stream);
+/* Which kernel bfm_zoom_linear runs for these extents (host arithmetic, no device needed; the launcher asks here too):
+ * 0 = the whole source in LDS, 1 = wave rows in LDS with 16-byte stores, 2 = the same with scalar stores, 3 = per output
+ * element for long rows.  out_aligned16: whether the output pointer is 16-byte aligned.  < 0: BFM_E_ARG / BFM_E_SHAPE. */
+int bfm_zoom_linear_route(int nx, int ny, int nz, int C, int ox, int oy, int oz, int out_aligned16);
 /* one axis of gaussian_blur_3d -- Generator/utils.py:84-94: zero-padded 1-D correlation, odd kernel. */
 int bfm_conv1d_axis(const float* in, int nx, int ny, int nz, int axis, const float* kern, int klen, float* out,
                     bfm_stream_t stream);
+/* The launch bfm_conv1d_axis makes (host arithmetic, no device needed; the launcher asks here too): 0 / 1 / 2 = the LDS
+ * slab kernel of that axis, 3 = the per-tap fallback (klen > 64, or axis 2 with nz > 1024).  seg: outputs along the
+ * filtered axis (axes 0, 1) or rows (axis 2) per slab, 0 for the fallback; nslab: workgroups; lds_bytes: dynamic LDS.
+ * Each of the three may be NULL.  < 0: BFM_E_ARG / BFM_E_SHAPE. */
+int bfm_conv1d_axis_plan(int nx, int ny, int nz, int axis, int klen, int* seg, int* nslab, size_t* lds_bytes);
 /* interpol.grid_push / grid_grad (order 1, 3-D) -- utils/interpol/iso1.py:136-387; with grid_pull they make
  * grid_pull / grid_push differentiable to first order (autograd.py:125-190, pushpull.py:262-310).
  * push: inp (Bi,C,ix,iy,iz) scattered through grid (Bg,ix,iy,iz,3) into out (B,C,nx,ny,nz), which MUST be zero on

@@ -1,5 +1,8 @@
 """Parity of the HIP synthesis kernels (through the C ABI / host mirrors) against the golden vectors
-of the real reference and the NumPy oracle.  Needs an MI355X: run with `-m gpu`."""
+of the real reference and the NumPy oracle: one golden shape per operation, mostly through the Python fronts, plus the
+whole-generator goldens.  The kernels one at a time -- every route of bfm_zoom_linear and bfm_conv1d_axis, the edge
+coordinates of the gathers, the small kernels of prep.hip, guard bands and sentinel tails -- are in
+tests/test_gpu_synth_kernels.py (references: tests/synth_kernel_refs.py).  Needs an MI355X: run with `-m gpu`."""
 import os
 
 import numpy as np
