@@ -268,6 +268,7 @@ SIGNATURES = {
     "bfm_maxpool2": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "bfm_tail_heads": (_I, [_P, _P, _L, C.POINTER(TailDesc), _P, _P, _P, _P, _P, _P]),
     "bfm_tail_heads_rows": (_I, [_P, _P, _L, C.POINTER(TailDesc), _P, _P, _L, _P, _P, _I, _P]),
+    "bfm_tail_route": (_I, [C.POINTER(TailDesc)]),
     "bfm_ew_unary": (_I, [_I, _P, _L, _P, _L, _L, _F, _F, _P]),
     "bfm_ew_binary": (_I, [_I, _P, _L, _P, _L, _P, _L, _L, _F, _P]),
     "bfm_absmax_f32": (_I, [_P, _L, _L, _L, _P, _P]),

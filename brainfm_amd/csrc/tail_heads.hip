@@ -396,6 +396,20 @@ __global__ void __launch_bounds__(TPBT, 2) tail_kernel(TailParams p, int ld, int
 
 }  // namespace
 
+// Host arithmetic: which instantiation of tail_kernel a launch with this descriptor takes (tail_launch dispatches on it).
+// 0 fp32 MFMA chain, 1 split-f16 generic, 2 split-f16 <56 classes, 3 column blocks>, 3 split-f16 <18 classes, 1 block>.
+// The split-f16 path needs unit_feat (one power-of-two scale fits every normalised row), a finite head_wmax > 0 and whole
+// 16-wide k-steps.  Reads only the scalar fields of the descriptor; -1 for NULL.
+extern "C" int bfm_tail_route(const bfm_tail_desc_t* desc) {
+    if (!desc) return -1;
+    const bool split = desc->unit_feat && desc->head_wmax > 0.f && desc->head_wmax < INFINITY && desc->c_feat % 16 == 0;
+    if (!split) return 0;
+    const int nnb = (desc->n_out + 31) >> 5;
+    if (desc->n_seg == 56 && nnb == 3) return 2;               // the shipped head set (69 outputs, 56 classes)
+    if (desc->n_seg == 18 && nnb == 1) return 3;               // left-hemisphere head set (18 classes, 27 outputs)
+    return 1;
+}
+
 static int tail_launch(const float* feat, const float* input, int64_t nvox, const bfm_tail_desc_t* desc,
                        float* feat_norm, float* const* maps_tab, float* maps_rows, int64_t row_stride, float* seg_prob,
                        int64_t* label, float* raw_out, int skip_zero_input, bfm_stream_t stream, int64_t raw_stride = 0) {
@@ -436,19 +450,18 @@ static int tail_launch(const float* feat, const float* input, int64_t nvox, cons
         return BFM_E_LAUNCH;
     // split-f16 path: weights scaled so that max|w| * 2^wexp < 2^15 (head_wmax from the descriptor)
     int wexp = 0;
-    const bool split = desc->unit_feat && desc->head_wmax > 0.f && desc->head_wmax < INFINITY && desc->c_feat % 16 == 0;
-    if (split) {
+    const int route = bfm_tail_route(desc);
+    if (route != 0) {
         int ex;
         (void)frexpf(desc->head_wmax, &ex);
         wexp = 14 - ex;
         wexp = wexp > 60 ? 60 : (wexp < -60 ? -60 : wexp);
     }
-    const int nnb = (desc->n_out + 31) >> 5;
-    if (split && desc->n_seg == 56 && nnb == 3)                // the shipped head set (69 outputs, 56 classes)
+    if (route == 2)
         hipLaunchKernelGGL((tail_kernel<true, 56, 3>), dim3((unsigned)nb), dim3(TPBT), smem, bfm_s(stream), p, ld, wexp);
-    else if (split && desc->n_seg == 18 && nnb == 1)           // left-hemisphere head set (18 classes, 27 outputs)
+    else if (route == 3)
         hipLaunchKernelGGL((tail_kernel<true, 18, 1>), dim3((unsigned)nb), dim3(TPBT), smem, bfm_s(stream), p, ld, wexp);
-    else if (split)
+    else if (route == 1)
         hipLaunchKernelGGL((tail_kernel<true>), dim3((unsigned)nb), dim3(TPBT), smem, bfm_s(stream), p, ld, wexp);
     else
         hipLaunchKernelGGL((tail_kernel<false>), dim3((unsigned)nb), dim3(TPBT), smem, bfm_s(stream), p, ld, 0);

@@ -397,7 +397,8 @@ enum {
     BFM_ROLE_CT = 1,        /* x1000 */
     BFM_ROLE_BIAS_LOG = 2,  /* exp */
     BFM_ROLE_SEG = 3,       /* softmax member (contiguous run of n_seg rows) */
-    BFM_ROLE_DIST = 4,      /* clamp(+-max_dist); order lp, lw[, rp, rw] */
+    BFM_ROLE_DIST = 4,      /* clamp(+-max_dist) as fminf(fmaxf(v, -max_dist), max_dist): a NaN logit comes out as
+                               -max_dist, where torch.clamp keeps the NaN; order lp, lw[, rp, rw] */
     BFM_ROLE_SR = 5,        /* high_res_residual: also emits high_res = v + input */
     BFM_ROLE_PATHOL = 6     /* sigmoid */
 };
@@ -438,6 +439,11 @@ int bfm_tail_heads(const float* feat, const float* input /*[nvox], may be NULL*/
 int bfm_tail_heads_rows(const float* feat, const float* input /*[nvox], may be NULL*/, int64_t nvox,
                         const bfm_tail_desc_t* desc, float* feat_norm /*or NULL*/, float* maps_rows, int64_t row_stride,
                         float* seg_prob /*or NULL*/, int64_t* label /*or NULL*/, int flags, bfm_stream_t stream);
+/* Host arithmetic, no device needed: the instantiation of the tail kernel that a call with this descriptor takes (the
+ * launcher dispatches on it).  0 = fp32 MFMA chain (unit_feat == 0, head_wmax not a finite positive number, or
+ * c_feat % 16 != 0), 1 = split-f16 generic, 2 = split-f16 with 56 classes and 3 column blocks (65..96 outputs: the shipped
+ * head set), 3 = split-f16 with 18 classes and 1 column block (the left-hemisphere head set).  -1 for NULL. */
+int bfm_tail_route(const bfm_tail_desc_t* desc);
 
 /* ----------------------------------------------------------------- stitch
  * scripts/demo_test.py:88-119 without the NIfTI round trip:
@@ -495,7 +501,7 @@ int bfm_stitch_gather_compact(const int64_t* tiles, int T, int K, const float* v
  * synthesis augmentations (Generator/utils.py:568-638).  Strides are in
  * elements so channel slices of channels-last buffers are read in place. */
 enum {
-    BFM_EW_EXP = 0, BFM_EW_AFFINE = 1 /* x*a+b */, BFM_EW_CLAMP = 2 /* [a,b] */, BFM_EW_CLAMP_MIN = 3,
+    BFM_EW_EXP = 0, BFM_EW_AFFINE = 1 /* x*a+b */, BFM_EW_CLAMP = 2 /* [a,b]; NaN -> a (fmaxf) */, BFM_EW_CLAMP_MIN = 3,
     BFM_EW_GAMMA = 4 /* a*(x/a)^b, add_gamma_transform utils.py:568-572 */, BFM_EW_SIGMOID = 5,
     BFM_EW_DIV = 6 /* x/a */, BFM_EW_NONZERO = 7 /* x!=0 ? 1:0 */, BFM_EW_SUB_DIV = 8 /* (x-a)/b */,
     BFM_EW_GE = 9 /* x>=a ? 1:0, binarize utils.py:65-72 */,
@@ -516,6 +522,10 @@ int bfm_ew_binary(int op, const float* x, int64_t x_stride, const float* y, int6
 int bfm_absmax_f32(const float* x, int64_t rows, int64_t len, int64_t row_stride, float* out_zeroed, bfm_stream_t stream);
 int bfm_softmax_cl(const float* x, int64_t x_row_stride, int C, float* y, int64_t y_row_stride, int64_t n,
                    bfm_stream_t stream);
+/* out[i] = lut[first maximum of row i] (lut NULL: the index).  A NaN is never greater than anything, so a row holding a NaN
+ * gives the first maximum of its other members, unless the NaN is in column 0, which then stays the maximum: torch.argmax
+ * picks a NaN, and this kernel does not unless it is in column 0.  The inference flow only sees all-NaN rows, where both
+ * give 0. */
 int bfm_argmax_lut_cl(const float* p, int64_t row_stride, int C, const int32_t* lut, int64_t* out, int64_t n,
                       bfm_stream_t stream);
 int bfm_fake_cortical(const float* dist, int64_t row_stride, int n_dist, float* out, int64_t n,
