@@ -147,6 +147,8 @@ SIGNATURES = {
     "bfm_conv3x3x3_stem_ex": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P]),
     "bfm_conv3x3x3_stem_mc_ex": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _P, _P, _P]),
     "bfm_gn_stats_rows_workspace": (_Z, [_I, _I, _I, _I]),
+    "bfm_gn_stats_plan": (_I, [_I, _L, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_L), C.POINTER(_I)]),
+    "bfm_gn_stats_rows_route": (_I, [_I, _I, _I, _I, _I, _I]),
     "bfm_gn_stats_rows": (_I, [_P, _I, _I, _P, _I, _I, C.c_double, _L, _P, _P, _I, _F, _P, _P, _P, _P, _Z, _P, _P]),
     "bfm_gn_stats_rows_sliced": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.c_double, _L, _P, _P, _I, _F, _P, _P, _P, _P, _Z,
                                       _P, _P]),

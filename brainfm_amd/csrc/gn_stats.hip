@@ -472,17 +472,26 @@ Plan make_plan(int CA, int CB, int64_t nvoxA, int64_t nvoxB, int S = 1) {
     return p;
 }
 
+// The gn_partial a tensor takes (BFM_GN_ROUTE_*) and the voxel rows it keeps in flight (0 on the wide routes): the one
+// place launch_partial and the bfm_gn_stats_plan query ask.
+int partial_route(int C, bool aligned, int* rows_in_flight) {
+    const bool vec4 = (C % 4 == 0) && aligned;
+    const int CV = vec4 ? C / 4 : C;
+    *rows_in_flight = CV > TPB ? 0 : TPB / CV;
+    return (CV > TPB ? BFM_GN_ROUTE_WIDE_VEC4 : BFM_GN_ROUTE_ROWS_VEC4) + (vec4 ? 0 : 1);
+}
+
 void launch_partial(const float* X, int C, int64_t nvox, int nb, int64_t vpb, RepView rep, char* ws, size_t o_sum,
                     size_t o_sq, size_t o_mn, size_t o_mx, hipStream_t st, int S = 1) {
     double* ps = reinterpret_cast<double*>(ws + o_sum);
     double* pq = reinterpret_cast<double*>(ws + o_sq);
     float* pn = reinterpret_cast<float*>(ws + o_mn);
     float* px = reinterpret_cast<float*>(ws + o_mx);
-    bool vec4 = (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
-    int CV = vec4 ? C / 4 : C;
-    int RP = CV > TPB ? 0 : TPB / CV;
+    int RP;
+    const int route = partial_route(C, (reinterpret_cast<uintptr_t>(X) & 15) == 0, &RP);
     size_t smem = (size_t)RP * C * 24;
-    if (vec4) hipLaunchKernelGGL(gn_partial<4>, dim3(nb, S), dim3(TPB), smem, st, X, C, nvox, vpb, rep, ps, pq, pn, px);
+    if (route == BFM_GN_ROUTE_ROWS_VEC4 || route == BFM_GN_ROUTE_WIDE_VEC4)
+        hipLaunchKernelGGL(gn_partial<4>, dim3(nb, S), dim3(TPB), smem, st, X, C, nvox, vpb, rep, ps, pq, pn, px);
     else hipLaunchKernelGGL(gn_partial<1>, dim3(nb, S), dim3(TPB), smem, st, X, C, nvox, vpb, rep, ps, pq, pn, px);
 }
 
@@ -492,6 +501,20 @@ extern "C" size_t bfm_gn_stats_workspace(int CA, int CB, int D, int H, int W, co
     int64_t nvoxA = (int64_t)D * H * W;
     int64_t nvoxB = (CB > 0 && up) ? (int64_t)up->d * up->h * up->w : 0;
     return make_plan(CA, CB, nvoxA, nvoxB).total;
+}
+
+extern "C" int bfm_gn_stats_plan(int C, int64_t nvox, int aligned, int* route, int* nblocks, int64_t* vox_per_block,
+                                 int* rows_in_flight) {
+    if (C <= 0 || nvox <= 0) return BFM_E_ARG;
+    int rp;
+    int64_t vpb;
+    const int r = partial_route(C, aligned != 0, &rp);
+    const int nb = blocks_for(nvox, C, &vpb);
+    if (route) *route = r;
+    if (nblocks) *nblocks = nb;
+    if (vox_per_block) *vox_per_block = vpb;
+    if (rows_in_flight) *rows_in_flight = rp;
+    return BFM_OK;
 }
 
 static int gn_stats_launch(const float* A, int CA, const float* B, int CB, int S, int D, int H, int W,
@@ -597,6 +620,17 @@ size_t rows_ws_bytes(int nrows, int C) {            // reduced table (only when 
     return (((size_t)RR_MAX * C * 24) + 255) & ~(size_t)255;
 }
 
+// How gn_rows_sliced turns the tables into statistics (BFM_GN_ROWS_*): the one place it and the
+// bfm_gn_stats_rows_route query ask.  One launch (rows_group_finalize) when a table is large, the caller gave G zeroed
+// tickets and the KS x Ctot partials fit the workspace the two-launch form would have used.
+int rows_route(int nrowsA, int CA, int nrowsB, int CB, int G, bool has_ticket) {
+    const int Ctot = CA + CB;
+    const size_t need = rows_ws_bytes(nrowsA, CA) + (CB > 0 ? rows_ws_bytes(nrowsB, CB) : 0);
+    if (need == 0) return BFM_GN_ROWS_DIRECT;
+    if (has_ticket && G <= BFM_GN_TICKETS && (size_t)KS * Ctot * 24 <= need) return BFM_GN_ROWS_ONE_LAUNCH;
+    return BFM_GN_ROWS_FOLD;
+}
+
 // returns the table gn_finalize should read; launches rows_reduce into ws when the row count is large
 PartTab rows_source(const void* rows, int nrows, int C, double wgt, char* ws, hipStream_t st, int total = 0, int first = 0) {
     RowsView v = rows_view(rows, total > 0 ? total : nrows, C, first);
@@ -622,6 +656,13 @@ extern "C" size_t bfm_moment_rows_bytes(int nrows, int C) {
 
 extern "C" size_t bfm_gn_stats_rows_workspace(int nrowsA, int CA, int nrowsB, int CB) {
     return rows_ws_bytes(nrowsA, CA) + (CB > 0 ? rows_ws_bytes(nrowsB, CB) : 0) + 256;
+}
+
+extern "C" int bfm_gn_stats_rows_route(int nrowsA, int CA, int nrowsB, int CB, int G, int has_ticket) {
+    if (nrowsA <= 0 || CA <= 0 || CB < 0 || (CB > 0 && nrowsB <= 0)) return BFM_E_ARG;
+    if (G <= 0 || (CA + CB) % G != 0) return BFM_E_SHAPE;
+    if ((size_t)((CA + CB) / G) * 24 + (size_t)TPB * 24 > 64 * 1024) return BFM_E_SHAPE;
+    return rows_route(nrowsA, CA, nrowsB, CB, G, has_ticket != 0);
 }
 
 static int gn_rows_sliced(const void* rowsA, int nrowsA, int CA, const void* rowsB, int nrowsB, int CB,
@@ -672,10 +713,7 @@ static int gn_rows_sliced(const void* rowsA, int nrowsA, int CA, const void* row
     hipStream_t st = bfm_s(stream);
     char* ws = static_cast<char*>(workspace);
     if (ticket && (reinterpret_cast<uintptr_t>(ticket) & 3)) return BFM_E_ARG;
-    // one launch (rows_group_finalize) when a table is large, the caller gave G zeroed tickets and the KS x Ctot
-    // partials fit the workspace the two-launch form would have used
-    if (ticket && needA + needB > 0 && G <= BFM_GN_TICKETS && (size_t)KS * Ctot * 24 <= needA + needB &&
-        (size_t)cpg * 24 + (size_t)TPB * 24 <= 64 * 1024) {
+    if (rows_route(nrowsA, CA, nrowsB, CB, G, ticket != nullptr) == BFM_GN_ROWS_ONE_LAUNCH) {
         RowsView va = rows_view(rowsA, totalA, CA, firstA);
         RowsSrc sa{va.sum, va.sq, va.mn, va.mx, nrowsA, CA, 1.0};
         RowsSrc sb{nullptr, nullptr, nullptr, nullptr, 0, 0, 1.0};

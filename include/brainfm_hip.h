@@ -51,8 +51,30 @@ const char* bfm_version(void);
  * (scale = gamma*rstd, shift = beta - mean*scale) and, per group, the largest
  * |y| the folded affine can produce (bound[g]) which the MFMA convolution
  * uses to pick a power-of-two operand scale.
- * workspace: bfm_gn_stats_workspace(...) bytes. */
+ * workspace: bfm_gn_stats_workspace(...) bytes.
+ *
+ * Arithmetic: sums and sums of squares of the tensor pass are fp64 from the first addition (one pass, var = E[x^2] -
+ * mean^2 clamped at 0), so var is good to about (N + 4) 2^-53 E[x^2] for N values per group whatever the summation
+ * order: 4e-8 of var on a field whose mean is 10^3 standard deviations.  mean / rstd / scale / shift are the fp32
+ * roundings of the fp64 results; bound[g] is, in fp32, max over the group's channels of
+ * max(|fmaf(min_c, scale, shift)|, |fmaf(max_c, scale, shift)|), folded with fmaxf from 0.
+ * Non-finite input: an Inf or a NaN anywhere in a group makes that group's mean or var non-finite, hence every scale
+ * and shift of the group NaN (nn.GroupNorm gives NaN there too); other groups are untouched.  fmaxf drops NaN, so such
+ * a group's bound[g] is 0, not NaN: a consumer must not read bound[g] == 0 as "this group is all zero".
+ * (tests/test_gpu_gn_pool.py pins both.) */
 size_t bfm_gn_stats_workspace(int CA, int CB, int D, int H, int W, const bfm_upsample_t* up);
+/* Host arithmetic only, no launch: the pass bfm_gn_stats makes over one source of C channels and nvox voxels whose base
+ * pointer is (aligned != 0) or is not 16-byte aligned.  route: float4 lanes need C % 4 == 0 and the alignment, else
+ * scalar lanes; with CV = C / 4 (float4) or C (scalar) columns, CV <= 256 keeps rows_in_flight = 256 / CV voxel rows
+ * per workgroup (threads beyond rows_in_flight * CV idle), CV > 256 is the wide form: a thread per column, laps of
+ * 256 columns, rows_in_flight = 0.  nblocks workgroups of vox_per_block consecutive voxels each (the last one shorter):
+ * nblocks = min(clamp(32768 / C, 8, 2048), ceil(nvox / 16)), then evened out.  Any output pointer may be NULL. */
+#define BFM_GN_ROUTE_ROWS_VEC4 0
+#define BFM_GN_ROUTE_ROWS_SCALAR 1
+#define BFM_GN_ROUTE_WIDE_VEC4 2
+#define BFM_GN_ROUTE_WIDE_SCALAR 3
+int bfm_gn_stats_plan(int C, int64_t nvox, int aligned, int* route, int* nblocks, int64_t* vox_per_block,
+                      int* rows_in_flight);
 int bfm_gn_stats(const float* A, int CA, const float* B, int CB, int D, int H, int W,
                  const bfm_upsample_t* up, const float* gamma, const float* beta, int G, float eps,
                  float* scale, float* shift, float* bound, void* workspace, size_t workspace_bytes,
@@ -216,6 +238,13 @@ int bfm_gn_stats_rows_batch(const void* rowsA, int nrowsA_per_sample, int CA, co
                             int CB, double weightB, int64_t nvox, int S, const float* gamma, const float* beta, int G,
                             float eps, float* scale, float* shift, float* bound, bfm_stream_t stream);
 
+/* nn.MaxPool3d(2) (buildingblocks.py:185-186): window 2, stride 2, floor (the last plane of an odd extent is never
+ * read), NaN from any corner kept.  float4 lanes when C % 4 == 0 and both pointers are 16-byte aligned, scalar lanes
+ * otherwise; D, H, W >= 2 (BFM_E_ARG).  Moment rows of the pooled tensor: bfm_maxpool2_rows() rows, one per workgroup,
+ * 0 (none: asking for them is BFM_E_SHAPE) unless C % 4 == 0, C / 4 <= 256 and 256 % (C / 4) == 0, and only with
+ * aligned pointers.  A row's sums are fp32 inside a thread (fs += m, fq = fmaf(m, m, fq) over the
+ * ceil(items / (rows * 256)) items of its grid-stride loop, items = d*h*w*C/4), widened to fp64 and folded in thread
+ * order; min and max are exact.  See bfm_gn_stats_rows for what that costs on an offset field. */
 int bfm_maxpool2_rows(int C, int D, int H, int W);
 int bfm_maxpool2_ex(const float* in, int C, int D, int H, int W, float* out, void* moment_rows /*or NULL*/,
                     bfm_stream_t stream);
@@ -247,8 +276,25 @@ size_t bfm_gn_stats_rows_workspace(int nrowsA, int CA, int nrowsB, int CB);
  * tickets, a table of more than 128 rows and G <= BFM_GN_TICKETS the whole thing is ONE launch: workgroup (group, row
  * slice) folds its slice for the group's channels, the last workgroup of a group to finish runs the group's finalize.
  * Without, it is up to three launches (a fold per large table, then the finalize).  Both forms are deterministic (fixed
- * summation orders); they differ from each other in the last bits of the fp64 sums. */
+ * summation orders); they differ from each other in the last bits of the fp64 sums.
+ *
+ * Conditioning: the rows are folded in fp64, but every producer (bfm_maxpool2_ex, the conv epilogues) squares and sums
+ * in fp32 inside a thread before it widens, so the statistics carry the producer's fp32 error: for a thread that
+ * visits j values, |dS| <= (j-1) 2^-24 sum|x| and |dQ| <= j 2^-24 sum x^2.  The error of var relative to var grows
+ * with (mean / std)^2: harmless on centred activations, about j 2^-24 (mean/std)^2 on an offset field, where the
+ * tensor pass of bfm_gn_stats stays at 2^-53.  Measured on a pooled 10^3 x 64 field with mean/std = 52 (one item per
+ * thread, so only the squares round): rstd off by 6.8e-7 from the rows, 3.6e-8 from the tensor pass, 1.0e-7 from
+ * torch's fp32 group_norm; on a centred field (mean/std = 2.7) all three are at 3e-8 .. 9e-8
+ * (tests/test_gpu_gn_pool.py, test_chain_pool_rows_against_tensor_pass).  Non-finite rows and bound[g]: as bfm_gn_stats. */
 #define BFM_GN_TICKETS 16
+/* Host arithmetic only: which of the forms above a call takes.  DIRECT: no table has more than 128 rows, the finalize
+ * reads them as they lie (one launch, tickets ignored).  ONE_LAUNCH: a table has more than 128 rows, has_ticket,
+ * G <= BFM_GN_TICKETS and 16 * (CA + CB) * 24 bytes fit the fold workspace (128 * C * 24 bytes, rounded up to 256, per
+ * table of more than 128 rows).  FOLD otherwise.  Negative: the BFM_E_* the call itself would return for these sizes. */
+#define BFM_GN_ROWS_DIRECT 0
+#define BFM_GN_ROWS_FOLD 1
+#define BFM_GN_ROWS_ONE_LAUNCH 2
+int bfm_gn_stats_rows_route(int nrowsA, int CA, int nrowsB, int CB, int G, int has_ticket);
 int bfm_gn_stats_rows(const void* rowsA, int nrowsA, int CA, const void* rowsB, int nrowsB, int CB, double weightB,
                       int64_t nvox, const float* gamma, const float* beta, int G, float eps, float* scale,
                       float* shift, float* bound, void* workspace, size_t workspace_bytes, void* ticket,
