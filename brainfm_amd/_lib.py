@@ -220,6 +220,9 @@ SIGNATURES = {
     "bfm_label_pull3d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _P, _P]),
     "bfm_affine_grid3d": (_I, [_P, _I, _L, _I, _I, _I, _P, _P]),
     "bfm_add_identity_grid3d": (_I, [_P, _I, _L, _I, _I, _I, _P]),
+    "bfm_affine_pull_multi": (_I, [_P, _L, _I, _I, _I, _I, C.POINTER(C.c_double), C.POINTER(_I), _I, _I, _I, _P, _P]),
+    "bfm_affine_pull_argmax": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(C.c_double), _I, _I, _I, _I, _P, _P, _P]),
+    "bfm_affine_pull_route": (_I, [_I]),
     "bfm_gn_stats_train": (_I, [_P, _I, _P, _I, _I, _I, _I, _UP, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "bfm_lrelu_bwd": (_I, [_P, _P, _L, _F, _P, _P]),
     "bfm_lrelu_bwd_ex": (_I, [_P, _P, _L, _F, _P, _P, _P]),

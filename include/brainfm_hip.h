@@ -814,6 +814,30 @@ int bfm_label_pull3d(const void* inp, int dtype, int Bi, int C, int nx, int ny, 
  *   in place.  is_f64 0: fp32, otherwise fp64.  Bit-equal to the reference in both. */
 int bfm_affine_grid3d(const void* mat, int is_f64, int64_t nb, int nx, int ny, int nz, void* out, bfm_stream_t stream);
 int bfm_add_identity_grid3d(void* disp, int is_f64, int64_t nb, int nx, int ny, int nz, bfm_stream_t stream);
+/* Resampling through a voxel-to-voxel matrix (brainfm_amd/native.py, csrc/affine_pull.hip; no counterpart in the
+ * reference, whose results stay on the processed grid of prepare_image, utils/test_utils.py:235-284).  M_host: 12 HOST
+ * doubles, row-major 3 x 4, destination index (i,j,k) -> source coordinate, evaluated in fp64 on the device as
+ * ((M[r][0]*i + M[r][1]*j) + M[r][2]*k) + M[r][3] with every operation rounded on its own.
+ * affine_pull_multi: out [K][X][Y][Z] fp32 <- K fp32 maps of (D,H,W), map m at src + m * map_stride (elements, >= D*H*W:
+ *   the stitched buffer of the tile flows is read in place).  mode_host[m] 0: trilinear, f = floor(x), wc = (float)(x - f),
+ *   wf = 1.f - wc, corners f and f + 1, a corner outside the source counts as 0 (grid_sample's padding_mode='zeros',
+ *   align_corners=True), summed in the c00 .. c chain of Generator/utils.py:177-185; 1: nearest, index floor(x + 0.5),
+ *   the 4-byte pattern copied, 0 outside.  All offsets are 64-bit.
+ * affine_pull_argmax: label [X][Y][Z] int32 <- post (D,H,W,C) fp32 channels-last, the layout the network tail leaves the
+ *   posteriors in.  Every channel is interpolated by the linear rule above; label = lut[c*], c* the first channel whose
+ *   value is > 0 and > every earlier channel's (ties: the lower channel; a NaN never wins); 0 where no value is positive,
+ *   which covers everything outside the field of view.  best (may be NULL): the winning value, 0 where there is none.
+ *   No posterior volume on the destination grid is written.
+ * affine_pull_route (host arithmetic, no device needed; the launcher asks here too): the lanes that share one voxel in
+ *   affine_pull_argmax when it is called with lanes = 0: the smallest power of two at which a lane takes at most five
+ *   channels, at most 16 (the widths were timed at C = 18 and 56, profiles/native.txt).  < 0: BFM_E_ARG.
+ *   lanes = 1, 2, 4 .. 64 forces a width (1: one thread per voxel looping over the channels); every width gives the same
+ *   bits, scripts/bench_native.py times them side by side. */
+int bfm_affine_pull_multi(const float* src, int64_t map_stride, int K, int D, int H, int W, const double* M_host,
+                          const int* mode_host, int X, int Y, int Z, float* out, bfm_stream_t stream);
+int bfm_affine_pull_argmax(const float* post, int C, int D, int H, int W, const int32_t* lut, const double* M_host, int X,
+                           int Y, int Z, int lanes, int32_t* label, float* best, bfm_stream_t stream);
+int bfm_affine_pull_route(int C);
 /* BaseGen.deform_grid -- Generator/datasets.py:264-303: (xc+F) -> A*. + c2, clamp to the source shape, and the
  * six global min/max (minmax = {min x,y,z, max x,y,z}, device).  F is [n][3] or NULL. */
 size_t bfm_deform_grid_workspace(int sx, int sy, int sz);
