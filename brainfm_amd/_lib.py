@@ -161,6 +161,7 @@ SIGNATURES = {
     "bfm_conv3x3x3_wino4_masked_workspace": (_Z, [_I, _I, _I, _I]),
     "bfm_conv3x3x3_wino4_uniform_scratch": (_Z, [_I]),
     "bfm_conv3x3x3_wino4_uniform": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P]),
+    "bfm_conv3x3x3_wino4_uniform_keep": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P]),
     "bfm_conv3x3x3_wino4": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _P]),
     "bfm_conv3x3x3_wino4_batch": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _I, _P]),
     "bfm_conv3x3x3_wino_b5_rows": (_I, [_I, _I, _I, _I]),
@@ -183,6 +184,7 @@ SIGNATURES = {
     "bfm_uniform_boxes_level": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "bfm_uniform_boxes_levels": (_I, [_P, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_P), _P, _P]),
     "bfm_uniform_boxes_bytes": (_Z, [_I, _I, _I, _I]),
+    "bfm_uniform_fill": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "bfm_conv3x3x3_wino_uniform_scratch": (_Z, [_I]),
     "bfm_conv3x3x3_wino_uniform": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P]),
     "bfm_conv3x3x3_wino_pool_ok": (_I, [_I, _I, _I, _I]),

@@ -599,6 +599,7 @@ struct FillParams {
     const int* first;                // [27] the representatives
     const int* list;                 // the mates, ascending
     const int* list_n;
+    const unsigned char* need;       // optional (UniformFlagBuf::need): the box of `out` is copied where it is set only
     double *rsum, *rsq;              // optional moment rows [nMt][Cout]
     float *rmn, *rmx;
     float* pool_out;                 // optional (box 8 x 8 x 4 tiling the tensor): (D/2,H/2,W/2,Cout) and its rows
@@ -615,7 +616,8 @@ __global__ void __launch_bounds__(NTHR) class_fill(const FillParams p) {
     const int z0 = (mt / (p.nTx * p.nTy)) * p.TD, y0 = ((mt / p.nTx) % p.nTy) * p.TH, x0 = (mt % p.nTx) * p.TW;
     const int rz0 = (rp / (p.nTx * p.nTy)) * p.TD, ry0 = ((rp / p.nTx) % p.nTy) * p.TH, rx0 = (rp % p.nTx) * p.TW;
     const int c4 = tid & 15;                                       // 16-byte piece of the 64 couts
-    {
+    // by need: no computed box is next to this one, so no later kernel of the pair stages a voxel of it (workgroup-uniform)
+    if (p.need == nullptr || p.need[mt] != 0) {
         const size_t dbase = (((size_t)z0 * p.H + y0) * p.W + x0) * p.Cout + nt * 64 + c4 * 4;
         const size_t sbase = (((size_t)rz0 * p.H + ry0) * p.W + rx0) * p.Cout + nt * 64 + c4 * 4;
         for (int r = 0; r < 4; ++r) {                              // 256 voxels = 4 rounds x 4 x 16 per workgroup
@@ -749,15 +751,24 @@ __global__ void __launch_bounds__(256) uniform_boxes_kernel(const float* __restr
 // cnt[1], uni[] = the other flagged boxes (conv_wino_uniform: their class's sums through the epilogue).  One workgroup.
 // (AGENT: the flags were written by other workgroups of this launch -- uniform_levels_kernel -- and are read past the L2s
 // that may not have seen them)
+// Then the need table of the (nTz, nTy, nTx) grid (UniformFlagBuf): need[b] = 1 for a box of uni[] with a box of rest[] among
+// its up to 26 neighbours, and ncnt[0], nlist[] = those boxes, ascending.  Which boxes are computed is first set down as one
+// bit per box in `comp` (UL_COMP_WORDS words of LDS), so that a box's 26 neighbours cost no trip to memory; a grid too
+// large for the table reads the flags instead.  Everything is a function of the flags in box order.
+constexpr int UL_COMP_WORDS = 4096;                                // 131 072 boxes: 16 KB
 template <bool AGENT>
-__device__ __forceinline__ void uniform_lists_body(const unsigned char* flags, int n, int* __restrict__ first,
-                                                   int* __restrict__ cnt, int* __restrict__ rest, int* __restrict__ uni,
-                                                   int* sh, int* fst) {
+__device__ __forceinline__ void uniform_lists_body(const unsigned char* flags, int n, int nTz, int nTy, int nTx,
+                                                   int* __restrict__ first, int* __restrict__ cnt, int* __restrict__ rest,
+                                                   int* __restrict__ uni, int* __restrict__ ncnt, int* __restrict__ nlist,
+                                                   unsigned char* __restrict__ need, int* sh, int* fst, unsigned* comp) {
     auto flag = [&](int i) -> int {
         if constexpr (AGENT) return __hip_atomic_load(flags + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else return flags[i];
     };
+    const bool table = n <= UL_COMP_WORDS * 32;
     if (threadIdx.x < 27) fst[threadIdx.x] = n;
+    if (table)
+        for (int i = threadIdx.x; i < (n + 31) / 32; i += 1024) comp[i] = 0u;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += 1024) {
         const int f = flag(i);
@@ -765,19 +776,50 @@ __device__ __forceinline__ void uniform_lists_body(const unsigned char* flags, i
     }
     __syncthreads();
     if (threadIdx.x < 27) first[threadIdx.x] = fst[threadIdx.x];
-    const int n0 = wino_compact(n, [&](int mt) { const int f = flag(mt); return f == 0 || fst[f - 1] == mt; }, rest, sh);
+    // (the pass that lists the computed boxes also sets their bits: every further read of a flag is a trip to memory)
+    const int n0 = wino_compact(n, [&](int mt) {
+        const int f = flag(mt);
+        const bool c = f == 0 || fst[f - 1] == mt;
+        if (c && table) atomicOr(&comp[mt >> 5], 1u << (mt & 31));                     // bitwise or: order independent
+        return c;
+    }, rest, sh);
     if (threadIdx.x == 0) cnt[0] = n0;
     __syncthreads();
-    const int n1 = wino_compact(n, [&](int mt) { const int f = flag(mt); return f != 0 && fst[f - 1] != mt; }, uni, sh);
+    auto computed = [&](int i) -> bool {
+        if (table) return ((comp[i >> 5] >> (i & 31)) & 1u) != 0u;
+        const int f = flag(i);
+        return f == 0 || fst[f - 1] == i;
+    };
+    const int n1 = wino_compact(n, [&](int mt) { return !computed(mt); }, uni, sh);    // flagged, and not its class's first
     if (threadIdx.x == 0) cnt[1] = n1;
+    __syncthreads();
+    const int n2 = wino_compact(n, [&](int mt) {
+        bool nd = false;
+        if (!computed(mt)) {
+            const int tx = mt % nTx, ty = (mt / nTx) % nTy, tz = mt / (nTx * nTy);
+            for (int dz = -1; dz <= 1; ++dz)
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int z = tz + dz, y = ty + dy, x = tx + dx;
+                        if (z >= 0 && z < nTz && y >= 0 && y < nTy && x >= 0 && x < nTx)
+                            nd = nd || computed((z * nTy + y) * nTx + x);        // (the box itself is not computed)
+                    }
+        }
+        need[mt] = nd ? 1 : 0;
+        return nd;
+    }, nlist, sh);
+    if (threadIdx.x == 0) ncnt[0] = n2;
 }
 
-__global__ void __launch_bounds__(1024) uniform_lists_kernel(const unsigned char* __restrict__ flags, int n,
-                                                             int* __restrict__ first, int* __restrict__ cnt,
-                                                             int* __restrict__ rest, int* __restrict__ uni) {
+__global__ void __launch_bounds__(1024) uniform_lists_kernel(const unsigned char* __restrict__ flags, int n, int nTz, int nTy,
+                                                             int nTx, int* __restrict__ first, int* __restrict__ cnt,
+                                                             int* __restrict__ rest, int* __restrict__ uni,
+                                                             int* __restrict__ ncnt, int* __restrict__ nlist,
+                                                             unsigned char* __restrict__ need) {
     __shared__ int sh[17];
     __shared__ int fst[27];
-    uniform_lists_body<false>(flags, n, first, cnt, rest, uni, sh, fst);
+    __shared__ unsigned comp[UL_COMP_WORDS];
+    uniform_lists_body<false>(flags, n, nTz, nTy, nTx, first, cnt, rest, uni, ncnt, nlist, need, sh, fst, comp);
 }
 
 // uniform_boxes_kernel + uniform_lists_kernel for every level of one image in one launch (a tile asks for levels 0 and 1:
@@ -785,15 +827,15 @@ __global__ void __launch_bounds__(1024) uniform_lists_kernel(const unsigned char
 // a time as uniform_boxes_kernel's workgroup does (same region, same flag), `per` boxes one after the other -- 4 at level
 // 0, 1 below, where a box's region is 12 times larger -- so a launch has ~1 500 workgroups and as many arrivals on the
 // ticket, not one per box (16 000 arrivals on one counter cost more than the launches they replaced:
-// profiles/r05_small_measurements.txt).  The last workgroup to arrive builds every level's class table and lists, in box
-// order as uniform_lists_kernel does: nothing depends on which workgroup that is.  *ticket is 0 on entry and left 0.
+// profiles/r05_small_measurements.txt).  The last workgroup to arrive builds every level's class table, lists and need table,
+// in box order as uniform_lists_kernel does: nothing depends on which workgroup that is.  *ticket is 0 on entry and left 0.
 constexpr int UL_MAX = 4;       // levels per launch
 constexpr int UL_LOADS = 8;     // loads a thread has in flight
 struct UniLevel {
     int TD, TH, TW, nTz, nTy, nTx, L, R;
     int n, per, wg0;                 // boxes, boxes per group, first workgroup of the level
     unsigned char* flags;
-    int* first;                      // UniformFlagBuf{flags, n}.first()
+    int* first;                      // UniformFlagBuf{flags, n}.first() (the kernel derives every table from flags and n)
 };
 struct UniLevels {
     const float* img;
@@ -807,6 +849,7 @@ __global__ void __launch_bounds__(1024) uniform_levels_kernel(const UniLevels p)
     __shared__ int fst[27];
     __shared__ int bad_w[16];
     __shared__ int is_last;
+    __shared__ unsigned comp[UL_COMP_WORDS];                       // the last workgroup's need tables
     const int tid = threadIdx.x, grp = tid >> 8, t = tid & 255;
     int li = 0;
     for (int i = 1; i < p.nlev; ++i)
@@ -879,8 +922,9 @@ __global__ void __launch_bounds__(1024) uniform_levels_kernel(const UniLevels p)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     for (int i = 0; i < p.nlev; ++i) {
         const int n = p.lv[i].n;
-        int* const first = p.lv[i].first;                          // UniformFlagBuf: first[27] | counts[2] | rest[n] | uniform[n]
-        uniform_lists_body<true>(p.lv[i].flags, n, first, first + 27, first + 29, first + 29 + n, sh, fst);
+        const UniformFlagBuf fb{p.lv[i].flags, (size_t)n};
+        uniform_lists_body<true>(fb.flags, n, p.lv[i].nTz, p.lv[i].nTy, p.lv[i].nTx, fb.first(), fb.counts(), fb.rest_list(),
+                                 fb.uniform_list(), fb.need_count(), fb.need_list(), fb.need(), sh, fst, comp);
         __syncthreads();                                           // sh and fst start over
     }
 }
@@ -1068,8 +1112,8 @@ extern "C" int bfm_uniform_boxes_level(const float* image, int D, int H, int W, 
     if ((TD << level) < radius || (TH << level) < radius || (TW << level) < radius) return BFM_E_SHAPE;
     hipLaunchKernelGGL(uniform_boxes_kernel, dim3((unsigned)fb.n), dim3(256), 0, bfm_s(stream), image, D, H, W, TD, TH, TW, nTz,
                        nTy, nTx, level, radius, flags);
-    hipLaunchKernelGGL(uniform_lists_kernel, dim3(1), dim3(1024), 0, bfm_s(stream), flags, (int)fb.n, fb.first(), fb.counts(),
-                       fb.rest_list(), fb.uniform_list());
+    hipLaunchKernelGGL(uniform_lists_kernel, dim3(1), dim3(1024), 0, bfm_s(stream), flags, (int)fb.n, nTz, nTy, nTx, fb.first(),
+                       fb.counts(), fb.rest_list(), fb.uniform_list(), fb.need_count(), fb.need_list(), fb.need());
     return bfm_launch_status();
 }
 
@@ -1198,12 +1242,14 @@ static int wino_launch(const WinoLaunch& a) {
             f.TD = p.TD; f.TH = p.TH; f.TW = p.TW; f.nTy = p.nTy; f.nTx = p.nTx;
             f.tw_shift = ilog2i(p.TW); f.thw_shift = ilog2i(p.TH * p.TW);
             f.flags = fb.flags; f.first = fb.first(); f.list = p.list; f.list_n = p.list_n;
+            f.need = (a.flags & 2) ? fb.need() : nullptr;      // by need: the pooled box and the rows are copied all the same
             f.rsum = p.rsum; f.rsq = p.rsq; f.rmn = p.rmn; f.rmx = p.rmx;
             f.pool_out = p.pool_out; f.prsum = p.prsum; f.prsq = p.prsq; f.prmn = p.prmn; f.prmx = p.prmx;
             hipLaunchKernelGGL(class_fill, grid, block, 0, st, f);
             return bfm_launch_status();
         }
-        // accumulate mode: a mate adds its own voxels of `out`, so it runs the epilogue on its class's sums (disjoint boxes)
+        // accumulate mode: a mate adds its own voxels of `out`, so it runs the epilogue on its class's sums (disjoint boxes);
+        // it stores every box, by need or not
         // conv_wino_uniform's LDS: its row fold; with the pooling, the windows' exchange and the pooled rows' fold behind it
         if (a.pool.out) bfm_launch_by_passes(passes, conv_wino_uniform_pool<3>, conv_wino_uniform_pool<1>, grid, block, 20480, st, p);
         else bfm_launch_by_passes(passes, conv_wino_uniform<3>, conv_wino_uniform<1>, grid, block, 6144, st, p);
@@ -1211,6 +1257,25 @@ static int wino_launch(const WinoLaunch& a) {
     }
     if (a.pool.out) bfm_launch_by_passes(passes, conv_wino_pool<3>, conv_wino_pool<1>, grid, block, smem, st, p);
     else bfm_launch_by_passes(passes, conv_wino<3>, conv_wino<1>, grid, block, smem, st, p);
+    return bfm_launch_status();
+}
+
+// Completes a tensor that a non-accumulating bfm_conv3x3x3_wino_uniform[_pool] launch stored by need: class_fill over every
+// mate, the copies the full launch makes (the representatives' boxes are in place), for a reader that is not the pair.
+extern "C" int bfm_uniform_fill(float* out, int D, int H, int W, int Cout, int passes, const unsigned char* uniform_flags,
+                                bfm_stream_t stream) {
+    if (!out || !uniform_flags || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cout % 64) return BFM_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(uniform_flags) & 3)) return BFM_E_ARG;
+    FillParams f{};
+    if (!choose_box(D, H, W, passes == 3 ? 2 : 1, f.TD, f.TH, f.TW)) return BFM_E_SHAPE;
+    f.out = out; f.D = D; f.H = H; f.W = W; f.Cout = Cout; f.NT = Cout / 64;
+    f.nTy = bfm_cdiv(H, f.TH); f.nTx = bfm_cdiv(W, f.TW);
+    f.tw_shift = ilog2i(f.TW); f.thw_shift = ilog2i(f.TH * f.TW);
+    const int64_t nMt = (int64_t)bfm_cdiv(D, f.TD) * f.nTy * f.nTx;
+    if (nMt * f.NT > 0x7fffffff) return BFM_E_SHAPE;
+    const UniformFlagBuf fb{uniform_flags, (size_t)nMt};
+    f.flags = fb.flags; f.first = fb.first(); f.list = fb.uniform_list(); f.list_n = fb.counts() + 1;
+    hipLaunchKernelGGL(class_fill, dim3((unsigned)(nMt * f.NT)), dim3(NTHR), 0, bfm_s(stream), f);
     return bfm_launch_status();
 }
 
@@ -1238,7 +1303,7 @@ extern "C" int bfm_conv3x3x3_wino_uniform(const float* A, int CA, int D, int H, 
                                           const float* shift, const float* bound, int G, const void* wpacked, int wexp,
                                           int Cout, float slope, int passes, int flags, float* out, void* moment_rows,
                                           const unsigned char* uniform_flags, void* scratch, bfm_stream_t stream) {
-    if (!uniform_flags || !scratch || (flags & ~1)) return BFM_E_ARG;
+    if (!uniform_flags || !scratch || (flags & ~3)) return BFM_E_ARG;     // bit 1: class mates by need (UniformFlagBuf)
     if ((reinterpret_cast<uintptr_t>(uniform_flags) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return BFM_E_ARG;
     WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
     a.uniform = {uniform_flags, static_cast<float*>(scratch)};
@@ -1251,7 +1316,7 @@ extern "C" int bfm_conv3x3x3_wino_uniform_pool(const float* A, int CA, int D, in
                                                int wexp, int Cout, float slope, int passes, int flags, float* out,
                                                void* moment_rows, const unsigned char* uniform_flags, void* scratch,
                                                float* pooled, void* pooled_rows, bfm_stream_t stream) {
-    if (!uniform_flags || !scratch || !pooled || (flags & ~1)) return BFM_E_ARG;
+    if (!uniform_flags || !scratch || !pooled || (flags & ~3)) return BFM_E_ARG;
     if ((reinterpret_cast<uintptr_t>(uniform_flags) & 3) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return BFM_E_ARG;
     WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
     a.uniform = {uniform_flags, static_cast<float*>(scratch)};

@@ -64,6 +64,8 @@ struct W4Params {
     const int* list_n;               // ... their number, on the device
     const unsigned char* uni_flags;  // conv_wino4d_rest / _uniform: [nMt] 0, or 1 + the class of a box whose operands equal its class mates'
     float* uni_acc;                  // [27][NT][2][8][NTHR] float4: the class representatives' output-transformed sums
+    const unsigned char* uni_need;   // conv_wino4d_uniform by need (UniformFlagBuf::need): `out` is stored where it is set only
+    const float* uni_keep;           // ... and in the boxes whose first voxel of this (D,H,W) image is not zero (optional)
     // batch (dense form only): nMt = S * nMtS boxes, box mt belongs to sample mt / nMtS; A, out advance by sA, sO elements
     // per sample, scale / shift by saff, bound by G; moment rows are [S * nMtS][Cout].  nMtS == 0: one sample.  A sample's
     // workgroups do exactly what they do in a launch of that sample alone.
@@ -581,6 +583,16 @@ __device__ __forceinline__ void conv_wino4d_body(const W4Params& pin) {
     const bool rep = MODE == 2 && cls != 0;                        // conv_wino4d_rest's flagged boxes: the class representatives
     float4* const ybuf = BY_FLAG && cls ? reinterpret_cast<float4*>(p.uni_acc) + ((size_t)(cls - 1) * p.NT + nt) * (2 * 8 * NTHR) + tid
                                         : nullptr;
+    // by need: a mate that no computed box of a later pair on these flags touches reads its box, sums its moment rows and
+    // stores nothing (workgroup-uniform).  With uni_keep the reader is the masked last convolution instead, which computes
+    // the boxes that hold a non-zero voxel of that image: a flagged box is constant, so its first voxel speaks for it.
+    bool store = true;
+    if constexpr (UNI) {
+        if (p.uni_need != nullptr) {
+            store = p.uni_need[mt] != 0;
+            if (!store && p.uni_keep != nullptr) store = p.uni_keep[((int64_t)z0 * p.H + y0) * p.W + x0] != 0.f;
+        }
+    }
 
     float bmax = 0.f;
     for (int g = 0; g < p.G; ++g) bmax = fmaxf(bmax, p.bound[g]);
@@ -914,7 +926,7 @@ __device__ __forceinline__ void conv_wino4d_body(const W4Params& pin) {
                     float r = y[k];
                     if (p.accum) r = r + prev[it][k];
                     r = r >= 0.f ? r : r * p.slope;
-                    if constexpr ((ABL & 128) == 0) o[off_t + (unsigned)(k * p.Cout)] = r;
+                    if constexpr ((ABL & 128) == 0) { if (!UNI || store) o[off_t + (unsigned)(k * p.Cout)] = r; }
                     fs += r; fq = fmaf(r, r, fq); fmn = fminf(fmn, r); fmx = fmaxf(fmx, r);
                 }
             }
@@ -946,7 +958,7 @@ __device__ __forceinline__ void conv_wino4d_body(const W4Params& pin) {
                         float r = y[k];
                         if (p.accum) r = r + o[off_t + (unsigned)(k * p.Cout)];
                         r = r >= 0.f ? r : r * p.slope;
-                        o[off_t + (unsigned)(k * p.Cout)] = r;
+                        if (!UNI || store) o[off_t + (unsigned)(k * p.Cout)] = r;
                         fs += r; fq = fmaf(r, r, fq); fmn = fminf(fmn, r); fmx = fmaxf(fmx, r);
                     }
                 }
@@ -1144,6 +1156,8 @@ static int w4_launch(const WinoLaunch& a) {
         if (!bfm_wino_choose_box(D, H, W, npl, bd, bh, bw) || bd != p.TD || bh != p.TH || bw != p.TW) return BFM_E_SHAPE;
         p.uni_flags = fb.flags;
         p.uni_acc = a.uniform.scratch;
+        if (a.uniform.keep && !(a.flags & 2)) return BFM_E_ARG;
+        if ((a.flags & 3) == 3) { p.uni_need = fb.need(); p.uni_keep = a.uniform.keep; }   // (without accumulate every box is stored)
     }
     if (dma) {                                                  // more than 64 KB of dynamic LDS
         static bool attr = false;
@@ -1247,5 +1261,22 @@ extern "C" int bfm_conv3x3x3_wino4_uniform(const float* A, int CA, int D, int H,
         return BFM_E_ARG;
     WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
     a.uniform = {uniform_flags, static_cast<float*>(scratch)};
+    return w4_launch(a);
+}
+
+// bfm_conv3x3x3_wino4_uniform accumulating by need (flags == 3) for an output whose reader is not the pair but a masked
+// convolution on the same box grid (bfm_conv3x3x3_wino_masked / _wino4_masked with keep_image as its mask image): beside the
+// class mates with `need`, the flagged boxes whose constant in keep_image (D,H,W) is not zero are stored -- the boxes that
+// reader computes and, around them, stages.  Moment rows as ever.
+extern "C" int bfm_conv3x3x3_wino4_uniform_keep(const float* A, int CA, int D, int H, int W, const float* scale,
+                                                const float* shift, const float* bound, int G, const void* wpacked, int wexp,
+                                                int Cout, float slope, int passes, int flags, float* out, void* moment_rows,
+                                                const unsigned char* uniform_flags, void* scratch, const float* keep_image,
+                                                bfm_stream_t stream) {
+    if (!uniform_flags || !scratch || !keep_image || flags != 3 || (reinterpret_cast<uintptr_t>(uniform_flags) & 3) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 15))
+        return BFM_E_ARG;
+    WinoLaunch a{A, CA, D, H, W, scale, shift, bound, G, wpacked, wexp, Cout, slope, passes, flags, out, moment_rows, stream};
+    a.uniform = {uniform_flags, static_cast<float*>(scratch), keep_image};
     return w4_launch(a);
 }

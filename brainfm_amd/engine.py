@@ -481,17 +481,11 @@ class UNetEngine:
         (Cin, Cout, dims, two-source) by timing them once on the real operands (HIP events on the launch stream).  All variants compute the same result; the chip is
         power-limited on this kernel, so which one wins is shape dependent (profiles/).  BFM_CONV_VER pins one."""
         cfg = self._plan_cache[key]
-        if key in self._tuned or os.environ.get("BFM_CONV_VER") or os.environ.get("BFM_CONV_TUNE", "1") == "0":
+        if self._variant_pinned(key):
             return cfg
-        # one choice per process, device and shape: a second engine (another session, a resumed run) takes the first
-        # one's winner instead of re-timing, so that two sessions in one process compute bit-identical results
         gkey = (torch.cuda.current_device(), getattr(self, "passes", None), key)
-        if gkey not in _TUNE_CHOICES:
-            saved = _tune_lookup(gkey[0], gkey[1], key)         # the persisted table: same bits in every process
-            if saved is not None and not (key[3] and saved in (3, 4)) and (vers is None or saved in vers):
-                _TUNE_CHOICES[gkey] = int(saved)
-        if gkey in _TUNE_CHOICES and (vers is None or _TUNE_CHOICES[gkey] in vers or (_TUNE_CHOICES[gkey] == 4 and 3 in vers)):
-            c = _TUNE_CHOICES[gkey]
+        c = self._settled_variant(key, vers)
+        if c is not None:
             if vers is None or c in vers:
                 cfg[6] = c
                 self._tuned.add(key)
@@ -541,6 +535,28 @@ class UNetEngine:
         _TUNE_CHOICES[gkey] = best
         _tune_store(gkey[0], gkey[1], key, best)
         return cfg
+
+    def _variant_pinned(self, key):
+        """The plan's variant stands as it is: timed before on this engine, or pinned (BFM_CONV_VER, BFM_CONV_TUNE=0)."""
+        return bool(key in self._tuned or os.environ.get("BFM_CONV_VER") or os.environ.get("BFM_CONV_TUNE", "1") == "0")
+
+    def _settled_variant(self, key, vers=None):
+        """The variant _autotune gives this shape without timing anything, or None when it would have to time: the plan's
+        when pinned, else this process's earlier choice, else the persisted table's.  _autotune decides by this, and so does
+        a producer that must know its reader's kernel before the reader runs (_known_variant)."""
+        if self._variant_pinned(key):
+            return int(self._plan_cache[key][6])
+        # one choice per process, device and shape: a second engine (another session, a resumed run) takes the first
+        # one's winner instead of re-timing, so that two sessions in one process compute bit-identical results
+        gkey = (torch.cuda.current_device(), getattr(self, "passes", None), key)
+        if gkey not in _TUNE_CHOICES:
+            saved = _tune_lookup(gkey[0], gkey[1], key)         # the persisted table: same bits in every process
+            if saved is not None and not (key[3] and saved in (3, 4)) and (vers is None or saved in vers):
+                _TUNE_CHOICES[gkey] = int(saved)
+        c = _TUNE_CHOICES.get(gkey)
+        if c is not None and (vers is None or c in vers or (c == 4 and 3 in vers)):
+            return int(c)
+        return None
 
     def conv_choices(self):
         """{shape key: variant} of every conv shape timed so far in this process on this device (see _autotune)."""
@@ -597,6 +613,7 @@ class UNetEngine:
                                                      L.ptr(self._gn_ticket()) if self.gn_one_launch else None, st),
                     "gn_stats_rows " + ly.name)
             return ws
+        self._complete(A, dims)                              # this route reads every voxel (B is never stored by need)
         wsb = self.lib.bfm_gn_stats_workspace(ca, cb, D, H, W, upp)
         ws = self._workspace(max(wsb, ws_min))
         L.check(self.lib.bfm_gn_stats_train(L.ptr(A), ca, L.ptr(B), cb, D, H, W, upp, L.ptr(ly.gamma), L.ptr(ly.beta),
@@ -612,19 +629,33 @@ class UNetEngine:
                                   scale=scale, shift=shift, bound=bound, mean=mean, rstd=rstd, out=out))
 
     def _conv_launch(self, ly, A, ca, B, cb, dims, upp, scale, shift, bound, groups, cfg, out, ws, rows=None, slope=None,
-                     mask_img=None, uni_flags=None, pool=None):
+                     mask_img=None, uni_flags=None, pool=None, need=None):
         """One launch of the planned variant of GN-apply + conv + LeakyReLU (cfg[6]: 0/1/2 conv_mfma family,
         3 / 4 Winograd F(2,3) / F(4,3); cfg[7] bit 0: accumulate onto `out`).  mask_img (variants 3 and 4 only): the tile's
         input image; boxes of output voxels where it is all zero are left uncomputed (the family's _masked entry point).
-        uni_flags (variants 3 and 4, one source): per-box flags of bfm_uniform_boxes -> the family's _uniform entry point."""
+        uni_flags (variants 3 and 4, one source): per-box flags of bfm_uniform_boxes -> the family's _uniform entry point.
+        need (with uni_flags): the class mates of `out` are stored by need (bit 1 of the flag argument); an image instead of
+        True: the masked convolution with that mask image reads `out` next (bfm_conv3x3x3_wino4_uniform_keep).
+        A tensor that was stored by need (_bfm_need) is read by the launch its producer counted on, or not at all."""
         D, H, W = dims
         st = L.stream_ptr()
         slope = self.slope if slope is None else float(slope)
         self._pack(ly, True, cfg[6])
         v = self._variant(cfg[6])
+        tag = getattr(A, "_bfm_need", None)
+        if B is not None and getattr(B, "_bfm_need", None) is not None:
+            raise L.BfmError("%s: an upsampled source that was stored by need" % ly.name)
+
+        def reads(route, ok=False):
+            if tag is not None and not ok:
+                raise L.BfmError("%s: its input was stored by need for %s, and this launch (%s) would read boxes that were "
+                                 "never written" % (ly.name, "the uniform-box pair on its flags" if tag[1] is None else
+                                                    "the masked convolution", route))
+        fbit = (cfg[7] & 1) | (2 if need is not None else 0)
         if mask_img is not None:
             if v.masked is None or cb or rows is not None:
                 raise L.BfmError("a masked launch is a one-source Winograd kernel without moment rows")
+            reads("masked", tag is not None and tag[1] is mask_img and (cfg[6] == 3 or self._same_boxes(dims)))
             nws = v.masked_workspace(D, H, W, self.passes)
             mws = torch.empty(nws, dtype=torch.uint8, device=self.device)       # box activity, count, list of boxes
             L.check(v.masked(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked),
@@ -637,28 +668,44 @@ class UNetEngine:
                 raise L.BfmError("the fused pooling is the one-source F(2,3) kernel's")
             pooled, prow = pool
             if uni_flags is not None:
+                reads("uniform, pool", tag is not None and tag[1] is None and tag[0] is uni_flags)
                 scratch = torch.empty(self.lib.bfm_conv3x3x3_wino_uniform_scratch(ly.cout), dtype=torch.uint8,
                                       device=self.device)
                 L.check(self.lib.bfm_conv3x3x3_wino_uniform_pool(
                     L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked), ly.wexp,
-                    ly.cout, slope, self.passes, cfg[7] & 1, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
+                    ly.cout, slope, self.passes, fbit, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
                     L.ptr(uni_flags), L.ptr(scratch), L.ptr(pooled), L.ptr(prow[0]) if prow is not None else None, st),
                         "conv_wino(uniform, pool) " + ly.name)
             else:
+                if need is not None:
+                    raise L.BfmError("%s: stores by need without the uniform-box pair" % ly.name)
+                reads("pool")
                 L.check(self.lib.bfm_conv3x3x3_wino_pool(
                     L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked), ly.wexp,
                     ly.cout, slope, self.passes, cfg[7] & 1, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
                     L.ptr(pooled), L.ptr(prow[0]) if prow is not None else None, st), "conv_wino(pool) " + ly.name)
             return
-        if uni_flags is not None and cfg[6] == 4 and not self._same_boxes(dims):
+        if uni_flags is not None and not self._pair_ok(cfg[6], dims, cb):
             uni_flags = None                                # the flags are per box of conv_wino's grid: dense launch, same bits
-        if uni_flags is not None and v.uniform is not None and not cb:
+        if uni_flags is not None and v.uniform is not None:
+            reads("uniform", tag is not None and tag[1] is None and tag[0] is uni_flags)
             scratch = torch.empty(v.uniform_scratch(ly.cout), dtype=torch.uint8, device=self.device)
+            if need is not None and need is not True:
+                if cfg[6] != 4 or fbit != 3:
+                    raise L.BfmError("stores for a masked reader are the accumulating F(4,3) pair's")
+                L.check(self.lib.bfm_conv3x3x3_wino4_uniform_keep(
+                    L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked), ly.wexp,
+                    ly.cout, slope, self.passes, fbit, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
+                    L.ptr(uni_flags), L.ptr(scratch), L.ptr(need), st), "conv_wino4(uniform, keep) " + ly.name)
+                return
             L.check(v.uniform(L.ptr(A), ca, D, H, W, L.ptr(scale), L.ptr(shift), L.ptr(bound), groups, L.ptr(ly.wpacked),
-                              ly.wexp, ly.cout, slope, self.passes, cfg[7] & 1, L.ptr(out),
+                              ly.wexp, ly.cout, slope, self.passes, fbit, L.ptr(out),
                               L.ptr(rows[0]) if rows is not None else None, L.ptr(uni_flags), L.ptr(scratch), st),
                     "conv_wino(uniform) " + ly.name)
             return
+        if need is not None:
+            raise L.BfmError("%s: stores by need without the uniform-box pair" % ly.name)
+        reads("dense")
         if v.dense is not None:
             if cb:
                 raise L.BfmError("the Winograd variant takes one source" if cfg[6] == 3 else
@@ -697,6 +744,65 @@ class UNetEngine:
                   self._variant(4).box(dims[0], dims[1], dims[2], self.passes, b4) == 0)
             cache[key] = ok and list(b3) == list(b4)
         return cache[key]
+
+    def _pair_ok(self, ver, dims, cb=0, mask_img=None):
+        """A launch of variant `ver` that is handed uniform flags takes the _rest / _uniform pair: a one-source Winograd
+        launch that leaves no box out, F(4,3) only where its boxes are the flags' (single_conv, _single_conv_upfold and
+        _conv_launch decide by this, and so does a producer that stores by need for them: _need_reader)."""
+        return ver in (3, 4) and not cb and mask_img is None and (ver != 4 or self._same_boxes(dims))
+
+    def _known_variant(self, ly, tune_ly, key):
+        """The variant _f23_cfg(ly, _autotune(tune_ly, key, ...)) will return, when that is settled without timing anything
+        (pinned, timed before, or in the table); None: not known yet."""
+        self._plan(key[0], key[1], key[2], key[3], key[4])
+        ver = self._settled_variant(key)
+        if ver is None:
+            return None
+        cfg = (C.c_int * 8)()
+        cfg[6] = ver
+        return int(self._f23_cfg(ly, cfg)[6])
+
+    def _need_reader(self, reader, flags, dims, ca):
+        """Whether the one convolution that reads a (dims, ca) tensor will, in this pass, take the uniform-box pair on
+        `flags` -- then the tensor's producer may store its class mates by need.  reader: ("conv", layer, its flags): the next
+        SingleConv of the level; ("skip", decoder's first conv, its flags): the skip half of an up-folded decoder conv;
+        ("masked", layer, mask image): the network's last convolution, which computes the boxes that hold input."""
+        if (reader is None or flags is None or not self.uniform_need or self.tape is not None or not self.fuse_stats
+                or self.force_direct):
+            return False
+        kind, ly, arg = reader
+        if kind == "skip":
+            cb = ly.cin - ca
+            lo = tuple(v // 2 for v in dims)
+            if not (arg is flags and self._mfma_ok(ly, ca, cb) and self.use_upfold and all(v % 2 == 0 for v in dims)
+                    and lo[0] * lo[1] * lo[2] >= self.upfold_min):
+                return False
+            return self._pair_ok(self._known_variant(ly, self._skip_layer(ly, ca), (ca, ly.cout, tuple(dims), False, True)),
+                                 dims)
+        if not (ly.cin == ca and self._mfma_ok(ly, ca, 0)):
+            return False
+        ver = self._known_variant(ly, ly, (ly.cin, ly.cout, tuple(dims), False, False))
+        if kind == "conv":
+            return arg is flags and self._pair_ok(ver, dims)
+        # the masked form: its boxes must be the flags' (F(2,3)'s are), single_conv's own condition otherwise
+        return (arg is not None and self.mask_skip and ver in (3, 4) and (ver == 3 or self._same_boxes(dims))
+                and self._variant(ver).masked is not None)
+
+    def _complete(self, t, dims):
+        """A tensor stored by need for the pair, for a reader that looks at every voxel: the remaining class mates are
+        copied from their classes' first boxes (what the full launch does).  Not for an accumulated tensor.  The one reader
+        a producer cannot foresee is the GroupNorm of a decoder whose up-sampled source came without moment rows (a conv
+        variant that emits none): it reads the skip tensor in full.  need_completed counts these; the default flows leave
+        it at zero."""
+        tag = getattr(t, "_bfm_need", None)
+        if tag is None:
+            return
+        if tag[1] is not None:
+            raise L.BfmError("a tensor stored by need for the masked convolution cannot be completed")
+        L.check(self.lib.bfm_uniform_fill(L.ptr(t), dims[0], dims[1], dims[2], t.shape[-1], self.passes, L.ptr(tag[0]),
+                                          L.stream_ptr()), "uniform_fill")
+        t._bfm_need = None
+        self.need_completed += 1
 
     def _f23_cfg(self, ly, cfg):
         """A tuned choice of the F(4,3) kernel (variant 4) becomes F(2,3) for the uniform-box layers that feed another one
@@ -748,11 +854,14 @@ class UNetEngine:
         self.prof.append((ev[0], ev[1], flops, nbytes, reps, (tag, cin, cout, tuple(dims), tuple(cfg))))
 
     # ------------------------------------------------------------------ one SingleConv
-    def single_conv(self, ly, A, dims, B=None, lo_dims=None, mask_img=None, uni_flags=None, pool=False):
+    def single_conv(self, ly, A, dims, B=None, lo_dims=None, mask_img=None, uni_flags=None, pool=False, reader=None):
         """GroupNorm -> Conv3d(3,p=1) -> LeakyReLU on cat((A, nearest_up(B))).
         A: (D,H,W,CA) fp32, B: (d,h,w,CB) fp32 or None.  Returns (D,H,W,Cout).
         mask_img: (D,H,W) image; the caller promises to look at the output only where it is non-zero (the tile loop's
-        last convolution, see backbone_cl).  Honoured when the layer runs the 4-wave Winograd kernel, ignored otherwise."""
+        last convolution, see backbone_cl).  Honoured when the layer runs the 4-wave Winograd kernel, ignored otherwise.
+        reader: the one convolution that reads the output (_need_reader), when the caller knows it: where that one takes the
+        uniform-box pair on the same flags, the output's class mates are stored by need and the tensor is tagged with the
+        flags (_bfm_need); any other reader of a tagged tensor raises (_conv_launch) or completes it first (_complete)."""
         D, H, W = dims
         ca = A.shape[-1]
         cb = 0 if B is None else B.shape[-1]
@@ -766,7 +875,8 @@ class UNetEngine:
         mfma = self._mfma_ok(ly, ca, cb)
         if (mfma and B is not None and self.use_upfold and tuple(dims) == tuple(2 * v for v in lo_dims)
                 and lo_dims[0] * lo_dims[1] * lo_dims[2] >= self.upfold_min):
-            return self._single_conv_upfold(ly, A, dims, B, lo_dims, upp, scale, shift, bound, uni_flags=uni_flags)
+            return self._single_conv_upfold(ly, A, dims, B, lo_dims, upp, scale, shift, bound, uni_flags=uni_flags,
+                                            reader=reader)
         cfg = None
         wsc = 0
         if mfma:
@@ -782,7 +892,7 @@ class UNetEngine:
         if mfma:
             if mask_img is not None and not (cfg[6] in (3, 4) and B is None and self.tape is None):
                 mask_img = None
-            if uni_flags is not None and not (cfg[6] in (3, 4) and B is None and mask_img is None):
+            if uni_flags is not None and not self._pair_ok(cfg[6], dims, cb, mask_img):
                 uni_flags = None
             rows = self._rows_for(ly.cin, ly.cout, dims, cfg) if mask_img is None else None
             # pool: the caller pools this output next (an encoder level's second conv): where the F(2,3) kernel's box allows
@@ -792,6 +902,14 @@ class UNetEngine:
                     and min(dims) >= 2 and self.lib.bfm_conv3x3x3_wino_pool_ok(D, H, W, self.passes)):
                 pooled = torch.empty((D // 2, H // 2, W // 2, ly.cout), dtype=torch.float32, device=self.device)
                 pl = (pooled, self._rows_buf(ly.cout, 1, self.lib.bfm_conv3x3x3_wino_rows, D, H, W, self.passes))
+
+            # by need: the non-accumulating F(2,3) pair (class_fill); a pooling that is not fused would read every voxel
+            need = None
+            if (uni_flags is not None and cfg[6] == 3 and rows is not None and (pl is not None or not pool)
+                    and reader is not None and reader[0] != "masked" and self._need_reader(reader, uni_flags, dims, ly.cout)):
+                need = True
+                if self.poison_skipped:
+                    out.fill_(float("nan"))
 
             def _record():
                 nv = D * H * W
@@ -804,7 +922,9 @@ class UNetEngine:
                         self._tag(ly) + ("[masked]" if mask_img is not None else "[uniform]" if uni_flags is not None else ""),
                         ly.cin, ly.cout, dims, cfg)
             self._bracket(lambda: self._conv_launch(ly, A, ca, B, cb, dims, upp, scale, shift, bound, ly.groups, cfg, out, ws,
-                                                    rows, mask_img=mask_img, uni_flags=uni_flags, pool=pl), _record)
+                                                    rows, mask_img=mask_img, uni_flags=uni_flags, pool=pl, need=need), _record)
+            if need is not None:
+                out._bfm_need = (uni_flags, None)
             if rows is not None:
                 out._bfm_rows = rows
             if pl is not None:
@@ -933,7 +1053,7 @@ class UNetEngine:
             ly.skip = sk
         return ly.skip
 
-    def _single_conv_upfold(self, ly, A, dims, B, lo_dims, upp, scale, shift, bound, uni_flags=None):
+    def _single_conv_upfold(self, ly, A, dims, B, lo_dims, upp, scale, shift, bound, uni_flags=None, reader=None):
         """cat((skip, up2x(x))) -> GN -> conv -> LeakyReLU as: GN stats over the virtual concat, the upsampled
         channels through bfm_conv3x3x3_upfold (8 folded taps on the low-res tensor), the skip channels through
         bfm_conv3x3x3_mfma accumulating onto that."""
@@ -969,13 +1089,20 @@ class UNetEngine:
         self._bracket(_launch_up, lambda: (2.0 * 27 * cb * ly.cout * nv, 4.0 * (lo * cb + nv * ly.cout),
                                            self._tag(ly) + "up", cb, ly.cout, dims, (0,) * 8))
         rows = self._rows_for(ca, ly.cout, dims, cfg)
-        if uni_flags is not None and (cfg[6] not in (3, 4) or (cfg[6] == 4 and not self._same_boxes(dims))):
+        if uni_flags is not None and not self._pair_ok(cfg[6], dims):
             uni_flags = None
+        # by need: the accumulating F(4,3) pair, when the masked last convolution is all that reads the output
+        need = None
+        if (uni_flags is not None and cfg[6] == 4 and rows is not None and reader is not None and reader[0] == "masked"
+                and self._need_reader(reader, uni_flags, dims, ly.cout)):
+            need = reader[2]
         self._bracket(lambda: self._conv_launch(sk, A, ca, None, 0, dims, None, scale, shift, bound, ly.groups, cfg, out, ws,
-                                                rows, uni_flags=uni_flags),
+                                                rows, uni_flags=uni_flags, need=need),
                       lambda: (2.0 * 27 * ca * ly.cout * (nv if uni_flags is None else self.uniform_voxels(uni_flags, dims)),
                                4.0 * (nv * ca + 2 * nv * ly.cout),
                                self._tag(ly) + ("sk[uniform]" if uni_flags is not None else "sk"), ca, ly.cout, dims, cfg))
+        if need is not None:
+            out._bfm_need = (uni_flags, need)
         if rows is not None:
             out._bfm_rows = rows
         self._record(ly, A, B, dims, lo_dims, scale, shift, bound, out)
@@ -989,6 +1116,7 @@ class UNetEngine:
             return fused                                     # written by the producing conv's epilogue (single_conv(pool=True))
         if out is None:
             out = torch.empty((D // 2, H // 2, W // 2, c), dtype=torch.float32, device=self.device)
+        self._complete(X, dims)
         rows = self._rows_buf(c, 1, self.lib.bfm_maxpool2_rows, c, D, H, W)
         L.check(self.lib.bfm_maxpool2_ex(L.ptr(X), c, D, H, W, L.ptr(out), L.ptr(rows[0]) if rows is not None else None,
                                          L.stream_ptr()), "maxpool2")
@@ -1048,6 +1176,13 @@ class UNetEngine:
     # last decoder's conv 1) run a quarter of the matrix products in boxes that see nothing else (bfm_uniform_boxes,
     # bfm_conv3x3x3_wino_uniform; bit-identical).  BFM_UNIFORM_SKIP=0: every box in full.
     uniform_skip = os.environ.get("BFM_UNIFORM_SKIP", "1") != "0"
+    # A computed box stages its input with a one-voxel halo, so of a tensor that only a uniform-box layer on the same flags
+    # reads, the class mates with no computed box next to them are never read: its producer stores those boxes by need
+    # (the `need` table behind the flags; _need_reader).  BFM_UNIFORM_NEED=0: every box is stored; same bits wherever a
+    # later kernel looks.  BFM_POISON_SKIPPED=1 (debugging): such an output is filled with NaN before the launch.
+    uniform_need = os.environ.get("BFM_UNIFORM_NEED", "1") != "0"
+    poison_skipped = os.environ.get("BFM_POISON_SKIPPED", "0") == "1"
+    need_completed = 0          # tensors stored by need that a reader of every voxel had to complete (_complete)
 
     # A small tile's level deep_from - 1 is small too (80^3: 20^3 voxels of 256 channels -- launches of 60-100 us that
     # fill a fifth of the chip; round 6: the 160 x 80 x 80 class too, 40 x 20 x 20 = 16 000 voxels, 250 workgroups per
@@ -1404,9 +1539,14 @@ class UNetEngine:
                 if min(d) < 2:
                     raise L.BfmError("volume %s too small for %d pooling levels" % (dims, len(self.enc) - 1))
                 x, d = self.maxpool(x, d)
-            x = self.single_conv(l1, x, d, uni_flags=self._layer_flags(("enc", i, 0), x_cl, dims))
-            x = self.single_conv(l2, x, d, uni_flags=self._layer_flags(("enc", i, 1), x_cl, dims),
-                                 pool=i + 1 < nlev)              # (the region pools the last level itself)
+            f1, f2 = (self._layer_flags(("enc", i, j), x_cl, dims) for j in (0, 1))
+            x = self.single_conv(l1, x, d, uni_flags=f1, reader=("conv", l2, f2))
+            # read by the next level's pooling (fused: the pooled tensor is complete) and by the skip half of the decoder that
+            # ends here; the last level's output goes to the region or the first decoder, which read every voxel
+            rd = None
+            if i + 1 < nlev and i < len(self.dec):
+                rd = ("skip", self.dec[len(self.dec) - 1 - i][0], self._layer_flags(("dec", i), x_cl, dims))
+            x = self.single_conv(l2, x, d, uni_flags=f2, pool=i + 1 < nlev, reader=rd)   # (the region pools the last level itself)
             skips.append((x, d))
         return skips
 
@@ -1419,8 +1559,10 @@ class UNetEngine:
         for k, ((l1, l2), (skip, sd_)) in enumerate(zip(self.dec[ndeep:], reversed(skips))):
             lvl = nd - 1 - k                                  # the level this decoder ends at
             uf = self._layer_flags(("dec", lvl), image, tuple(image.shape[:3])) if image is not None else None
-            y = self.single_conv(l1, skip, sd_, B=x, lo_dims=d, uni_flags=uf)
-            x = self.single_conv(l2, y, sd_, mask_img=mask_img if k == nd - 1 else None)
+            mk = mask_img if k == nd - 1 else None
+            y = self.single_conv(l1, skip, sd_, B=x, lo_dims=d, uni_flags=uf,
+                                 reader=("masked", l2, mk) if (mk is not None and mk is image) else None)
+            x = self.single_conv(l2, y, sd_, mask_img=mk)
             d = sd_
             feats.append((x, d))
         return feats

@@ -151,7 +151,14 @@ int bfm_conv3x3x3_wino_ex(const float* A, int CA, int D, int H, int W, const flo
  * scratch: bfm_conv3x3x3_wino_uniform_scratch(Cout) bytes, 16-byte aligned (written by accumulating calls only).  The
  * caller passes radius = (number of 3x3x3
  * convolutions between the image and this layer's OUTPUT): 2 for encoders.0's second conv, 3 for the skip half of the last
- * decoder's first conv. */
+ * decoder's first conv.
+ * Stores by need (flags bit 1 of the _uniform entry points).  The flag buffer ends with a table need[box] = 1 for a flagged
+ * box that is not its class's first and has, among its up to 26 neighbours in the grid, a box that is computed in full
+ * (unflagged, or a class's first) -- a computed box stages its input with a one-voxel halo, so when the only reader of
+ * `out` is a _uniform launch on the SAME flag buffer, the other class mates' voxels are never read.  With bit 1 set,
+ * bfm_conv3x3x3_wino_uniform[_pool] without accumulation and bfm_conv3x3x3_wino4_uniform with it leave `out` untouched in
+ * those boxes (the other forms store every box as without the bit); every box that is stored holds the same bits, and the
+ * moment rows, the pooled tensor and its rows are complete either way.  The caller answers for the reader. */
 size_t bfm_uniform_boxes_bytes(int D, int H, int W, int passes);
 int bfm_uniform_boxes(const float* image, int D, int H, int W, int radius, int passes, unsigned char* flags,
                       bfm_stream_t stream);
@@ -170,6 +177,10 @@ int bfm_uniform_boxes_level(const float* image, int D, int H, int W, int level, 
  * its radius (nothing launched: ask level by level then). */
 int bfm_uniform_boxes_levels(const float* image, int D, int H, int W, int nlevels, const int* levels, const int* radii,
                              int passes, unsigned char* const* flags, int* ticket, bfm_stream_t stream);
+/* completes an `out` (D,H,W,Cout) that a non-accumulating bfm_conv3x3x3_wino_uniform[_pool] launch stored by need: every
+ * class mate's box becomes the copy of its class's first box that the launch without bit 1 makes */
+int bfm_uniform_fill(float* out, int D, int H, int W, int Cout, int passes, const unsigned char* uniform_flags,
+                     bfm_stream_t stream);
 size_t bfm_conv3x3x3_wino_uniform_scratch(int Cout);
 int bfm_conv3x3x3_wino_uniform(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
                                const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
@@ -365,6 +376,13 @@ int bfm_conv3x3x3_wino4_uniform(const float* A, int CA, int D, int H, int W, con
                                 const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
                                 int flags, float* out, void* moment_rows, const unsigned char* uniform_flags, void* scratch,
                                 bfm_stream_t stream);
+/* the same, accumulating by need (flags == 3), for an `out` that a MASKED convolution on the same box grid reads next, with
+ * keep_image (D,H,W) as its mask image: beside the class mates with `need`, the flagged boxes whose constant in keep_image is
+ * not zero are stored -- the boxes that reader computes, and their neighbours, hold what a full launch stores. */
+int bfm_conv3x3x3_wino4_uniform_keep(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
+                                     const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope,
+                                     int passes, int flags, float* out, void* moment_rows, const unsigned char* uniform_flags,
+                                     void* scratch, const float* keep_image, bfm_stream_t stream);
 int bfm_conv3x3x3_wino4_masked(const float* A, int CA, int D, int H, int W, const float* scale, const float* shift,
                                const float* bound, int G, const void* wpacked, int wexp, int Cout, float slope, int passes,
                                int flags, float* out, const float* mask_image, void* workspace, size_t workspace_bytes,
