@@ -280,6 +280,8 @@ SIGNATURES = {
     "bfm_ew_binary": (_I, [_I, _P, _L, _P, _L, _P, _L, _L, _F, _P]),
     "bfm_absmax_f32": (_I, [_P, _L, _L, _L, _P, _P]),
     "bfm_softmax_cl": (_I, [_P, _L, _I, _P, _L, _L, _P]),
+    "bfm_softmax_cl_bwd": (_I, [_P, _L, _P, _L, _I, _P, _L, _L, _P]),
+    "bfm_ew_unary_bwd": (_I, [_I, _P, _L, _P, _L, _P, _L, _L, _F, _F, _P]),
     "bfm_argmax_lut_cl": (_I, [_P, _L, _I, _P, _P, _L, _P]),
     "bfm_fake_cortical": (_I, [_P, _L, _I, _P, _L, _P]),
     "bfm_mask_concat2": (_I, [_P, _P, _L, _P, _P]),

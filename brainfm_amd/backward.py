@@ -328,11 +328,17 @@ def backbone_forward_train(eng, x_cl, dims, fast=None):
     return feats, tape
 
 
-def backbone_backward(eng, tape, dfeats, input_grad=None):
+def backbone_backward(eng, tape, dfeats, input_grad=None, want_input_grad=False):
     """dfeats: gradients w.r.t. the decoder feature maps returned by backbone_forward_train (same order, channels-last;
     None = zero).  Returns {parameter name: gradient}.
-    input_grad: an InputGrad for the first layer (default: no input gradient is delivered)."""
+    input_grad: an InputGrad for the first layer (default: no input gradient is delivered).
+    want_input_grad: returns ({parameter name: gradient}, dX) instead, dX (D,H,W,Cin) the gradient of the whole network
+    input: the first layer's dA off the generic kernels (autograd.py; not together with input_grad, whose fused route forms
+    one channel only)."""
+    if want_input_grad and input_grad is not None:
+        raise L.BfmError("backbone_backward: want_input_grad and an InputGrad request exclude each other")
     grads = OrderedDict()
+    dX = None
     nlev = len(tape["enc"])
     dskip = [None] * nlev                       # gradient flowing into encoder level i's output from its decoder use
     # decoders, last to first: dec[j] consumes skip level (nlev-2-j) and the previous x
@@ -356,15 +362,19 @@ def backbone_backward(eng, tape, dfeats, input_grad=None):
             g = _add(g, dskip[i]) if g is not None else dskip[i]
         dy, _, gr = backward_single_conv(eng, t2, g)
         grads.update(gr)
-        dx, _, gr = backward_single_conv(eng, t1, dy, need_input_grad=i > 0 or input_grad is not None,
+        dx, _, gr = backward_single_conv(eng, t1, dy, need_input_grad=i > 0 or input_grad is not None or want_input_grad,
                                          input_grad=input_grad if i == 0 else None)
         grads.update(gr)
+        if i == 0:
+            dX = dx
         if i > 0:
             xin, din = tape["pool"][i - 1]
             dIn = torch.empty_like(xin)
             L.check(eng.lib.bfm_maxpool2_bwd(L.ptr(xin), L.ptr(dx.contiguous()), xin.shape[-1], din[0], din[1], din[2],
                                              L.ptr(dIn), L.stream_ptr()), "maxpool2_bwd")
             g = dIn
+    if want_input_grad:
+        return grads, dX
     return grads
 
 

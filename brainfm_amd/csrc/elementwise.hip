@@ -90,6 +90,37 @@ __global__ void softmax_cl(const float* __restrict__ x, int64_t xrs, int C, floa
     }
 }
 
+// backward of softmax_cl from the stored posterior, one thread per voxel as the forward: s = sum_j p_j g_j summed in
+// channel order, then dx_c = p_c * (g_c - s).  dx is a buffer of its own: it overlaps neither p nor g.  The rows are read
+// twice (the second pass hits the cache the first one filled): 3 * C * 4 bytes of HBM traffic per voxel.
+__global__ void softmax_cl_bwd(const float* __restrict__ p, int64_t prs, const float* __restrict__ g, int64_t grs, int C,
+                               float* __restrict__ dx, int64_t drs, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float* pr = p + i * prs;
+        const float* gr = g + i * grs;
+        float* o = dx + i * drs;
+        float s = 0.f;
+        for (int c = 0; c < C; ++c) s += pr[c] * gr[c];
+        for (int c = 0; c < C; ++c) o[c] = pr[c] * (gr[c] - s);
+    }
+}
+
+// backward of the per-voxel processors' unary ops: sigmoid from its OUTPUT y, clamp from its INPUT x (edges inclusive,
+// a NaN input passes no gradient: both comparisons are false, as torch's mask (x >= a) & (x <= b))
+__device__ __forceinline__ float ew_u_bwd(int op, float v, float g, float a, float b) {
+    switch (op) {
+        case BFM_EW_SIGMOID: return g * v * (1.f - v);
+        case BFM_EW_CLAMP: return (v >= a && v <= b) ? g : 0.f;
+        default: return 0.f;
+    }
+}
+
+__global__ void ew_unary_bwd(int op, const float* __restrict__ v, int64_t vs, const float* __restrict__ g, int64_t gs,
+                             float* __restrict__ dx, int64_t ds, int64_t n, float a, float b) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dx[i * ds] = ew_u_bwd(op, v[i * vs], g[i * gs], a, b);
+}
+
 __global__ void argmax_lut_cl(const float* __restrict__ p, int64_t prs, int C, const int32_t* __restrict__ lut,
                               int64_t* __restrict__ out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -303,6 +334,23 @@ extern "C" int bfm_softmax_cl(const float* x, int64_t x_row_stride, int C, float
     if (!x || !y || n <= 0 || C <= 0 || x_row_stride < C || y_row_stride < C) return BFM_E_ARG;
     hipLaunchKernelGGL(softmax_cl, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), x, x_row_stride, C, y, y_row_stride,
                        n);
+    return bfm_launch_status();
+}
+
+extern "C" int bfm_softmax_cl_bwd(const float* p, int64_t p_row_stride, const float* g, int64_t g_row_stride, int C,
+                                  float* dx, int64_t dx_row_stride, int64_t n, bfm_stream_t stream) {
+    if (!p || !g || !dx || n <= 0 || C <= 0 || p_row_stride < C || g_row_stride < C || dx_row_stride < C) return BFM_E_ARG;
+    hipLaunchKernelGGL(softmax_cl_bwd, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), p, p_row_stride, g, g_row_stride, C,
+                       dx, dx_row_stride, n);
+    return bfm_launch_status();
+}
+
+extern "C" int bfm_ew_unary_bwd(int op, const float* x_or_y, int64_t stride, const float* g, int64_t g_stride, float* dx,
+                                int64_t dx_stride, int64_t n, float a, float b, bfm_stream_t stream) {
+    if (!x_or_y || !g || !dx || n <= 0 || stride <= 0 || g_stride <= 0 || dx_stride <= 0) return BFM_E_ARG;
+    if (op != BFM_EW_SIGMOID && op != BFM_EW_CLAMP) return BFM_E_ARG;
+    hipLaunchKernelGGL(ew_unary_bwd, dim3(grid_for(n)), dim3(256), 0, bfm_s(stream), op, x_or_y, stride, g, g_stride, dx,
+                       dx_stride, n, a, b);
     return bfm_launch_status();
 }
 

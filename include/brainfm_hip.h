@@ -586,6 +586,18 @@ int bfm_ew_binary(int op, const float* x, int64_t x_stride, const float* y, int6
 int bfm_absmax_f32(const float* x, int64_t rows, int64_t len, int64_t row_stride, float* out_zeroed, bfm_stream_t stream);
 int bfm_softmax_cl(const float* x, int64_t x_row_stride, int C, float* y, int64_t y_row_stride, int64_t n,
                    bfm_stream_t stream);
+/* The backward of the per-voxel processors for losses written in torch (brainfm_amd/autograd.py): what torch autograd
+ * derives from joiner.py:69-77 (softmax), :79-87 (sigmoid) and :149-157 (clamp).
+ * bfm_softmax_cl_bwd: dx[i][c] = p[i][c] * (g[i][c] - sum_j p[i][j] g[i][j]) from the stored posterior p; rows of C floats
+ * `*_row_stride` apart (views of wider buffers are read in place), one thread per row as bfm_softmax_cl, the sum taken in
+ * channel order in fp32.  dx overlaps neither p nor g.
+ * bfm_ew_unary_bwd: BFM_EW_SIGMOID reads the OUTPUT y: dx = g * y * (1 - y); BFM_EW_CLAMP reads the INPUT x: dx = g where
+ * a <= x <= b (both edges inclusive, as torch.clamp's backward), 0 elsewhere and for a NaN x.  Other ops: BFM_E_ARG.
+ * Strides in elements, as bfm_ew_unary. */
+int bfm_softmax_cl_bwd(const float* p, int64_t p_row_stride, const float* g, int64_t g_row_stride, int C, float* dx,
+                       int64_t dx_row_stride, int64_t n, bfm_stream_t stream);
+int bfm_ew_unary_bwd(int op, const float* x_or_y, int64_t stride, const float* g, int64_t g_stride, float* dx,
+                     int64_t dx_stride, int64_t n, float a, float b, bfm_stream_t stream);
 /* out[i] = lut[first maximum of row i] (lut NULL: the index).  A NaN is never greater than anything, so a row holding a NaN
  * gives the first maximum of its other members, unless the NaN is in column 0, which then stays the maximum: torch.argmax
  * picks a NaN, and this kernel does not unless it is in column 0.  The inference flow only sees all-NaN rows, where both
